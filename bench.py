@@ -2,7 +2,10 @@
 """Learner throughput bench: env-frames/s of the IMPALA learner step on MI355X
 (``--algo ppo`` / ``--algo sac``: the PPO / SAC learner steps of BASELINE configs 4 / 5).
 
-``python bench.py --gpus N --steps K --warmup W``.  N > 1: one rank per GPU.  Under
+``python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]``.  A plain run
+does what the headline needs and no more: set-up, W warm-up steps, the clock-settling steps, the
+K timed steps, the output files if asked for, the result line.  ``--full`` adds every other
+record listed below (each takes runs of its own).  N > 1: one rank per GPU.  Under
 torch.distributed.run (WORLD_SIZE set) it must equal --gpus; run directly with --gpus N > 1 it
 starts ``python -m torch.distributed.run --nproc-per-node N`` itself as a child process (before
 anything touches the GPU) and exits with the child's status.
@@ -16,7 +19,13 @@ full learner update (NatureCNN forward, log-softmax, V-trace, losses, backward, 
 is resident in HBM before the timed region.  Multi-GPU: data-parallel
 replicas, B=64 per GPU (weak scaling), one flat fp32 gradient bucket all-reduced over RCCL.
 
-Also reported, all from the same run:
+``--dump-outputs DIR`` writes what the last timed step left with its caller as DIR/<name>.npy
+(float32): the parameters, the gradient, the Adam moments and the metrics vector (SAC: the four
+networks, log alpha, the metrics, the priorities).  The timed region starts from the seed-0
+weights and a zeroed optimizer on the seeded batch, whatever ran before it, so two runs with
+the same arguments compute the same arrays.
+
+With ``--full`` also reported, all from the same run:
 * ``roofline`` / ``roofline_top2``: the two kernels with algorithmic work that take longest
   (chosen from every kernel's average over --steps untimed steps, ``kernel_us``), each timed
   live by hipExtLaunchKernel start/stop events (the kernel's own begin / end stamps, the
@@ -26,8 +35,8 @@ Also reported, all from the same run:
   profiles/*/summary.json.  The stamped run is separate because an event pair on a launch
   costs the step ≈4.7 µs (tools/stamp_cost.py: 105 µs unstamped, 115 µs with two kernels
   stamped, 143 µs with all eight); its step time is reported as ``ms_per_step_stamped``;
-* ``step_roofline``: SURVEY.md §8(d)'s step-level figure, frames/s x 17.74 MFLOP/frame vs
-  the dense MFMA peak;
+* ``step_roofline`` (plain runs too: it is arithmetic on ``value``): SURVEY.md §8(d)'s
+  step-level figure, frames/s x 17.74 MFLOP/frame vs the dense MFMA peak;
 * ``bf16_mode`` (``--dtype bf16``: ``fp32_parity_mode``): the same workload in the other
   operand precision;
 * ``host_staged``: the PCIe-inclusive rate (batches from page-locked host memory), never
@@ -735,6 +744,57 @@ def cpu_baseline_sac(N, D, K, seconds):
                       f"torch-CPU, {threads} threads) after 2 warm-up; median step {med * 1e3:.2f} ms"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: device or host tensor} as path/<name>.npy, float32 (every
+    array the steps leave is float32 already; the step counter in the metrics is exact there)."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes of outputs, over {DUMP_MAX_BYTES}")
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def restart_from(model, eng, flat0):
+    """Put the learner back where `flat0` was taken: those parameters, zeroed Adam moments,
+    step 0 (a checkpoint restore, ImpalaLearner.load_optimizer_state), the kernel-layout weights
+    re-derived here and not inside the first timed step.  The settle before a timed region
+    runs for a time, not for a count, so without this the region's inputs -- and what
+    --dump-outputs writes -- would differ from run to run."""
+    with torch.no_grad():
+        model.flat.copy_(flat0)
+        eng.exp_avg.zero_()
+        eng.exp_avg_sq.zero_()
+    eng.set_step(0)
+    model.params_changed()
+    eng.refresh_weights()
+
+
+def sac_roofline(rk, k_ms, k_n, work, N, dtype):
+    """Roofline of the SAC launch `rk` from its event-timed pass (--full)."""
+    k_avg_ms = k_ms / max(k_n, 1)
+    fpt, bpt, bpl = work[rk]
+    flops, nbytes = fpt * N, bpt * N + bpl
+    t_s = k_avg_ms * 1e-3
+    if flops / (PEAK_TFLOPS[dtype] * 1e12) >= nbytes / (PEAK_HBM_GBS * 1e9):
+        bound, unit, achieved, peak = "mfma", "TFLOP/s", flops / t_s / 1e12, PEAK_TFLOPS[dtype]
+    else:
+        bound, unit, achieved, peak = "hbm", "GB/s", nbytes / t_s / 1e9, PEAK_HBM_GBS
+    traffic, tsrc = profiled_traffic(rk, dtype, SAC_PROFILE_NAMES, algo="sac")
+    traffic_src = (f"profiles/{tsrc}/summary.json (rocprofv3 PMC FETCH_SIZE*2+WRITE_SIZE, "
+                   "bytes per launch)") if tsrc else None
+    return {"bound": bound, "kernel": rk, "achieved": round(achieved, 3), "peak": peak,
+            "unit": unit, "frac": round(achieved / peak, 5), "traffic": traffic,
+            "traffic_source": traffic_src,
+            "algorithmic": {"flops": flops, "bytes": nbytes},
+            "avg_launch_us": round(k_avg_ms * 1e3, 2), "launches": k_n,
+            "timing": "separate event-timed pass of --steps direct-launch steps"}
+
+
 def run_sac(args):
     """SAC learner step (BASELINE config 5): critic + actor + alpha updates and both Polyak
     averages on N sampled transitions, sampled on the device from an HBM replay each step."""
@@ -778,7 +838,7 @@ def run_sac(args):
     names = eng.phase_names()
     probe = {}
     rk = args.roofline_kernel
-    if rk is None:
+    if rk is None and args.full:
         for i, kname in enumerate(names):
             eng.timer_start(i, 3)
             for _ in range(3):
@@ -799,12 +859,18 @@ def run_sac(args):
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    # the dominant launch's duration: HIP events around it on its stream, over as many steps
-    # again (an armed timer launches directly -- a graph replay cannot carry per-launch events)
-    eng.timer_start(names.index(rk), args.steps)
-    for _ in range(args.steps):
-        step()
-    k_ms, k_n = eng.timer_read()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            "actor": actor.flat, "critic": critic.flat, "target_critic": critic.target_flat,
+            "target_actor": tactor.flat, "log_alpha": critic.la_buf[:1], "metrics": eng.metrics,
+            "priorities": prio})
+    if args.full:
+        # the dominant launch's duration: HIP events around it on its stream, over as many steps
+        # again (an armed timer launches directly -- a graph replay cannot carry per-launch events)
+        eng.timer_start(names.index(rk), args.steps)
+        for _ in range(args.steps):
+            step()
+        k_ms, k_n = eng.timer_read()
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -813,17 +879,6 @@ def run_sac(args):
     if not np.all(np.isfinite(met)):
         raise RuntimeError(f"non-finite metrics {met}")
     value = world * N * args.steps / elapsed
-    k_avg_ms = k_ms / max(k_n, 1)
-    fpt, bpt, bpl = work[rk]
-    flops, nbytes = fpt * N, bpt * N + bpl
-    t_s = k_avg_ms * 1e-3
-    if flops / (PEAK_TFLOPS[args.dtype] * 1e12) >= nbytes / (PEAK_HBM_GBS * 1e9):
-        bound, unit, achieved, peak = "mfma", "TFLOP/s", flops / t_s / 1e12, PEAK_TFLOPS[args.dtype]
-    else:
-        bound, unit, achieved, peak = "hbm", "GB/s", nbytes / t_s / 1e9, PEAK_HBM_GBS
-    traffic, tsrc = profiled_traffic(rk, args.dtype, SAC_PROFILE_NAMES, algo="sac")
-    traffic_src = (f"profiles/{tsrc}/summary.json (rocprofv3 PMC FETCH_SIZE*2+WRITE_SIZE, "
-                   "bytes per launch)") if tsrc else None
     # per-step algorithmic flops: the phases that ran (probe), else the fused step's phases
     ran = probe or ("critic_fwd_chain", "critic_loss_chain", "critic_wgrad", "actor_chain",
                     "actor_wgrad", "alpha_chain")
@@ -838,17 +893,14 @@ def run_sac(args):
         "config": {"workload": f"SAC learner step (twin Q, tanh-Normal actor, alpha tuning, Polyak "
                                f"0.005), obs {D}, action {K}, N={N} transitions/GPU",
                    "global_batch": N * world, "parallelism": f"replicas{world}"},
-        "roofline": {"bound": bound, "kernel": rk, "achieved": round(achieved, 3), "peak": peak,
-                     "unit": unit, "frac": round(achieved / peak, 5), "traffic": traffic,
-                     "traffic_source": traffic_src,
-                     "algorithmic": {"flops": flops, "bytes": nbytes},
-                     "avg_launch_us": round(k_avg_ms * 1e3, 2), "launches": k_n,
-                     "timing": "separate event-timed pass of --steps direct-launch steps"},
         "step_gflop": round(step_flops / 1e9, 3),
+        "full": args.full,
     }
+    if args.full:
+        out["roofline"] = sac_roofline(rk, k_ms, k_n, work, N, args.dtype)
     if probe:
         out["kernel_probe_us"] = {k: round(v * 1e3, 2) for k, v in sorted(probe.items(), key=lambda kv: -kv[1])}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_sac(N, D, K, args.cpu_seconds)
     if rank == 0:
         emit_line(json.dumps(out))
@@ -866,6 +918,14 @@ def main():
     ap.add_argument("--actions", type=int, default=15)
     ap.add_argument("--dtype", default="fp32", choices=["bf16", "fp32"],
                     help="operand precision of the headline step (fp32 = the reference's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel times and "
+                         "rooflines, the other precision, the learner loop, actor inference, "
+                         "host-staged batches, the all-reduce arrangements (N > 1), the CPU "
+                         "baseline (each can be left out with its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left with its caller (parameters, "
+                         "gradient, Adam moments, metrics) as DIR/<name>.npy, float32")
     ap.add_argument("--roofline-kernel", default=None)
     ap.add_argument("--settle-ms", type=float, default=250.0,
                     help="untimed steps for at least this much wall time (device synced) right "
@@ -950,6 +1010,7 @@ def main():
     if dist is not None:  # identical initial weights on every replica
         dist.broadcast(model.flat, 0)
         model.params_changed()
+    flat0 = model.flat.clone()
 
     # data parallel: the learner's default (torch.distributed all-reduce) unless
     # IMPALA_DP_NATIVE=1 selects the library's own RCCL communicator (impala_dp_train_step);
@@ -976,18 +1037,24 @@ def main():
         step()
     torch.cuda.synchronize()
     work = kernel_work(2 if args.dtype == "bf16" else 4)
-    kernel_us, top = select_kernels(eng, step, work, args)
+    kernel_us, top = select_kernels(eng, step, work, args) if args.full else ({}, [])
     settled = settle(step, args.settle_ms, dist, dev)
+    restart_from(model, eng, flat0)
     # --no-step-clock: the headline region without the device step clock, so that
     # IMPALA_GRAPH=1 runs it as graph replays (an armed clock makes steps launch directly)
     clock = None if args.no_step_clock else StepClock(eng, args.steps)
     elapsed, _ = timed_steps(eng, step, [], args, dist, dev, clock)  # the headline: no kernel stamps
     steps_stat = step_stats(clock, dist, dev) if clock is not None else {
         "ms_per_step_median": elapsed * 1e3 / args.steps, "step_clock": "off (--no-step-clock)"}
-    # the stamped run for the roofline kernels' live durations, after its own settle: the
-    # regions 5-10 ms after a settle ends run 5-7 % slow (tools/region_order.py, profiles/r05host)
-    settle(step, args.settle_ms, dist, dev)
-    elapsed_st, k_times = timed_steps(eng, step, top, args, dist, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            "params": model.flat, "grads": model.flat_grad, "exp_avg": eng.exp_avg,
+            "exp_avg_sq": eng.exp_avg_sq, "metrics": eng.metrics})
+    if args.full:
+        # the stamped run for the roofline kernels' live durations, after its own settle: the
+        # regions 5-10 ms after a settle ends run 5-7 % slow (tools/region_order.py, profiles/r05host)
+        settle(step, args.settle_ms, dist, dev)
+        elapsed_st, k_times = timed_steps(eng, step, top, args, dist, dev)
     met = eng.metrics.cpu().numpy()
     if not np.all(np.isfinite(met)):
         raise RuntimeError(f"non-finite metrics {met}")
@@ -996,7 +1063,6 @@ def main():
     value = frames / elapsed
     ms_step = elapsed * 1e3 / args.steps
     algo = args.algo
-    rooflines = [kernel_roofline(k, k_times[k], work, B * T, args.dtype, algo) for k in top]
     metric = "learner env-frames/sec (IMPALA procgen T=20 B=64) at 1/2/4/8 MI355X"
     workload = f"IMPALA procgen learner step, NatureCNN actor-critic, B={B}/GPU T={T} A={A}, " \
                f"global B={B * world}"
@@ -1016,23 +1082,40 @@ def main():
                    "allreduce": (None if dist is None else
                                  f"native RCCL communicator, {dp_buckets} bucket(s)" if native_dp
                                  else "torch.distributed (c10d) RCCL")},
-        "roofline": rooflines[0],
-        "roofline_top2": rooflines,
         "step_roofline": step_roofline(value / world, step_flops_pf, args.dtype),
-        "kernel_us": kernel_us,
         **steps_stat,
         "value_at_median": round(world * B * T / (steps_stat["ms_per_step_median"] * 1e-3), 1),
         "step_times": "device step clock (StepClock): each step's first kernel stamps the "
                       "device clock; no event or marker between the headline region's steps",
-        "ms_per_step_stamped": round(elapsed_st * 1e3 / args.steps, 4),
         "settle": {"min_ms": args.settle_ms, "steps": settled},
+        "full": args.full,
     }
+    if native_dp:
+        out["config"]["rccl_nranks"] = eng.dp_nranks
+    if args.full:
+        full_records(out, args, eng, model, batch, make_step, work, kernel_us, top, k_times,
+                     elapsed_st, dist, dev, world, ppo)
+    if rank == 0:
+        emit_line(json.dumps(out))
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_records(out, args, eng, model, batch, make_step, work, kernel_us, top, k_times,
+                 elapsed_st, dist, dev, world, ppo):
+    """--full: the records beside the headline, added to the result line `out`."""
+    B, T, A = args.batch, args.rollout, args.actions
+    rank = int(os.environ.get("RANK", "0"))
+    ms_step = out["ms_per_step"]
+    rooflines = [kernel_roofline(k, k_times[k], work, B * T, args.dtype, args.algo) for k in top]
+    out["roofline"] = rooflines[0]
+    out["roofline_top2"] = rooflines
+    out["kernel_us"] = kernel_us
+    out["ms_per_step_stamped"] = round(elapsed_st * 1e3 / args.steps, 4)
     if not args.no_alt_line:
         alt = "fp32" if args.dtype == "bf16" else "bf16"
         out["fp32_parity_mode" if alt == "fp32" else "bf16_mode"] = alt_line(
             alt, args, B, T, A, dev, dist, world, make_step, ppo)
-    if native_dp:
-        out["config"]["rccl_nranks"] = eng.dp_nranks
     if dist is not None and not args.no_dp_variants:
         # a sub-record: an error in it (raised on every rank alike, e.g. RCCL not loadable for
         # the native communicator) is recorded instead of losing the line
@@ -1065,10 +1148,6 @@ def main():
             cb["host"] = host
             cb["single_thread"] = cpu_baseline(B, T, A, args.cpu_seconds_1t, threads=1, warmup=1)
             out["cpu_baseline"] = cb
-    if rank == 0:
-        emit_line(json.dumps(out))
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 DP_VARIANTS = (("c10d_1bucket", False, 1), ("native_1bucket", True, 1),

@@ -109,7 +109,7 @@ def native_dp_enabled(group=None) -> bool:
     torch.distributed (c10d) all-reduce of ``compute_grads_allreduced``: the native path has
     run on one rank only (bitwise equal to ``train_step`` there), and stays opt-in until a
     multi-GPU run shows its replicas bit-identical to each other and to the c10d step
-    (``bench.py --gpus N`` records both checks, ``dp_variants``)."""
+    (``bench.py --full --gpus N`` records both checks, ``dp_variants``)."""
     import torch.distributed as dist
     if os.environ.get("IMPALA_DP_NATIVE", "0") != "1":
         return False

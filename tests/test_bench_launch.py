@@ -175,6 +175,61 @@ def test_step_time_stats_finds_the_stall():
     assert "step_ms" not in bench.step_time_stats([1.0] * 300)
 
 
+def test_dump_outputs_writes_float32_npy(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per array, the directory created, the size cap kept."""
+    import numpy as np
+    import torch
+    d = tmp_path / "a" / "b"
+    bench.dump_outputs(str(d), {"params": torch.arange(6, dtype=torch.float32).view(2, 3),
+                                "count": torch.tensor([3], dtype=torch.int64)})
+    assert sorted(os.listdir(d)) == ["count.npy", "params.npy"]
+    p = np.load(d / "params.npy")
+    assert p.dtype == np.float32 and p.shape == (2, 3) and p[1, 2] == 5.0
+    assert np.load(d / "count.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16)
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "c"), {"x": torch.zeros(5)})
+
+
+FULL_ONLY = ("roofline", "roofline_top2", "kernel_us", "ms_per_step_stamped", "bf16_mode",
+             "learner_loop", "actor_act", "host_staged", "cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_reproducible(tmp_path):
+    """A plain run times exactly --steps steps, carries none of the --full records, and with
+    the same arguments writes the same outputs bit for bit, although the settle before the
+    timed region runs for a time and not for a count."""
+    import json
+
+    import numpy as np
+    lines = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--gpus", "1",
+                            "--steps", "3", "--warmup", "1", "--settle-ms", "20",
+                            "--dump-outputs", str(tmp_path / name)],
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = r.stdout.strip().splitlines()
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    for d in lines:
+        assert d["steps"] == 3 and len(d["step_ms"]) == 3 and d["full"] is False
+        assert d["unit"] == "env-frames/s" and d["higher_is_better"] is True and d["dtype"] == "fp32"
+        assert abs(d["value"] - 64 * 20 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+        assert not [k for k in FULL_ONLY if k in d]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["exp_avg.npy", "exp_avg_sq.npy", "grads.npy", "metrics.npy", "params.npy"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.all(np.isfinite(a))
+        np.testing.assert_array_equal(a, b, err_msg=n)
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "metrics.npy")[7] == 3  # the Adam step counter: 3 timed steps
+
+
 def test_stdout_carries_only_the_json_line():
     """bench.py claims fd 1 before any GPU / RCCL work: whatever is printed to stdout afterwards
     (RCCL's version banner at communicator init, library prints) goes to stderr, and stdout

@@ -41,6 +41,24 @@ def test_seed0_init_matches_reference():
     np.testing.assert_allclose(ref_cpu.flat_params(m), d["params"], rtol=1e-6, atol=1e-9)
 
 
+def _assert_params_close(got, want):
+    """|got - want| <= max(1e-7, one float32 ulp of want).  The fixtures come from another
+    host, whose GEMMs sum in another order: the gradients agree to rtol 1e-5 (asserted beside
+    this), and where Adam's g / (|g| + eps) is sensitive to that (a LayerNorm weight at 1.0 with
+    |g| ~ 3e-6 < eps) the float32 result rounds to the neighbouring value.  Below 1.0 an ulp is
+    under the 1e-7 bound, so the bound alone holds as before; from 1.0 on an ulp is 1.19e-7,
+    and a bare 1e-7 would ask for bit-equality, which float32 arithmetic on two hosts cannot
+    give."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype == want.dtype == np.float32
+    err = np.abs(got.astype(np.float64) - want.astype(np.float64))
+    bound = np.maximum(1e-7, np.spacing(np.abs(want)).astype(np.float64))
+    bad = np.nonzero(err > bound)[0]
+    assert bad.size == 0, (f"{bad.size} of {got.size} parameters differ by more than "
+                           f"max(1e-7, 1 ulp): first at {bad[0]}, got {got[bad[0]]!r}, "
+                           f"want {want[bad[0]]!r}")
+
+
 @pytest.mark.parametrize("mode", ovt.GRAD_MODES)
 def test_train_steps_match_reference(mode):
     d = _load(f"train_step_{mode}.npz")
@@ -57,8 +75,8 @@ def test_train_steps_match_reference(mode):
         np.testing.assert_allclose(got, exp, rtol=1e-5, atol=1e-6)
         if i == 0:
             np.testing.assert_allclose(ref_cpu.flat_grads(m), d["grads1"], rtol=1e-5, atol=1e-8)
-            np.testing.assert_allclose(ref_cpu.flat_params(m), d["params1"], rtol=0, atol=1e-7)
-    np.testing.assert_allclose(ref_cpu.flat_params(m), d["params3"], rtol=0, atol=1e-7)
+            _assert_params_close(ref_cpu.flat_params(m), d["params1"])
+    _assert_params_close(ref_cpu.flat_params(m), d["params3"])
 
 
 @pytest.mark.parametrize("mode", ovt.GRAD_MODES)
