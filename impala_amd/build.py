@@ -13,9 +13,6 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC_DIR = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libimpala_hip.so")
-# A/B build: also compiles the measured-slower alternative kernels (csrc/common.h IMPALA_AB);
-# loaded only when IMPALA_HIP_LIB points at it
-OUT_AB = os.path.join(HERE, "libimpala_hip_ab.so")
 ARCH = os.environ.get("IMPALA_OFFLOAD_ARCH", "gfx950")
 
 
@@ -39,20 +36,19 @@ def needs_build(out: str = OUT) -> bool:
     return any(os.path.getmtime(s) > t for s in deps if os.path.exists(s))
 
 
-def build(force: bool = False, verbose: bool = True, ab: bool = False) -> str:
-    """Compile the product library (or, ab=True, the A/B library with the measured-slower
-    alternative kernels) in-tree."""
-    out = OUT_AB if ab else OUT
+def build(force: bool = False, verbose: bool = True) -> str:
+    """Compile the library in-tree."""
+    out = OUT
     if not force and not needs_build(out):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     tmp = out + ".tmp"
     flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall",
-             "-Wno-unused-function"] + (["-DIMPALA_AB=1"] if ab else [])
+             "-Wno-unused-function"]
     # the units compile in parallel (sac.hip dominates), then one link
     objs, procs = [], []
     for src in hip_units():
-        obj = os.path.join(HERE, os.path.basename(src) + (".ab.o" if ab else ".o"))
+        obj = os.path.join(HERE, os.path.basename(src) + ".o")
         objs.append(obj)
         cmd = [hipcc] + flags + ["-c", "-o", obj, src]
         if verbose:
@@ -72,4 +68,4 @@ def build(force: bool = False, verbose: bool = True, ab: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    print("built", build(force="--force" in sys.argv, ab="--ab" in sys.argv))
+    print("built", build(force="--force" in sys.argv))

@@ -15,14 +15,6 @@ typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 #define WAVE 64
-// IMPALA_AB=1 (python -m impala_amd.build --ab) also compiles the measured-slower alternative
-// kernels kept for A/B runs (fc_fwd_splitk_f32 / fc_fwd_wsplit_f32, fwd_chain_kernel,
-// reduce_adam_kernel, wgrad23r_kernel); the product library is built without them, and asking
-// a non-A/B library for one (IMPALA_FC_SPLITK, IMPALA_FWD_CHAIN, IMPALA_FUSED_UPDATE,
-// IMPALA_EARLY_RED) fails impala_create with IMPALA_E_UNSUPPORTED.
-#ifndef IMPALA_AB
-#define IMPALA_AB 0
-#endif
 #define DEV __device__ __forceinline__
 
 // ---------------------------------------------------------------------------------------

@@ -307,7 +307,6 @@ template <typename T> struct C3Tail {
   T* act3;           // nullptr: no tail (the separate conv3 launch runs)
   T* y;
   float* stats;
-  int y_sc1;         // y stored write-through (read by other workgroups of the same launch)
 };
 
 // LDS of the forward body (elements of T)
@@ -736,10 +735,7 @@ DEV void conv12_fwd_body(const uint8_t* __restrict__ x, const T* __restrict__ w1
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           *reinterpret_cast<f32x4*>(et + p * LDE + 16 * i + 4 * (lane >> 4)) = acc3[i];
-        if (c3.y_sc1)
-          ln_frame_epilogue<T, true>(et, LDE, f0 + gw, lane, lk, c3.act3, c3.y, c3.stats);
-        else
-          ln_frame_epilogue<T>(et, LDE, f0 + gw, lane, lk, c3.act3, c3.y, c3.stats);
+        ln_frame_epilogue<T>(et, LDE, f0 + gw, lane, lk, c3.act3, c3.y, c3.stats);
       }
     }
   }

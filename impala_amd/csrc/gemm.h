@@ -491,13 +491,7 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_tile(const Op op, int n_rti
 // issued unconditionally: rows past the split's end and chunks past the group's last one carry
 // an out-of-range offset and read as zero without touching memory (no branch around a load,
 // so the compiler's counted vmcnt waits stay exact).  The groups' accumulators are summed in
-// a fixed order at the end.  Output: fp32 partial slab [split][R][C] (+ per-split bias sums),
-// or, for an Op with DIRECT (one split: the tile is final), the canonical gradient itself plus
-// the workgroup's sum of squares in op.sumsq[workgroup].
-template <class Op, class = void> struct wg_direct { static constexpr bool value = false; };
-template <class Op> struct wg_direct<Op, decltype(void(Op::DIRECT))> {
-  static constexpr bool value = Op::DIRECT;
-};
+// a fixed order at the end.  Output: fp32 partial slab [split][R][C] (+ per-split bias sums).
 // The body runs as virtual workgroup `lin` of a gx x gy x gz grid on 256 * G threads, with the
 // LDS passed in (gemm_wg_smem elements).
 // bf16 rows are stored bit-2/3 swapped (wg_row) at a pitch of BR / BC + 16 (conflict-free
@@ -538,8 +532,8 @@ DEV void gemm_wg_body(const Op& op, float* __restrict__ slab, float* __restrict_
   static_assert(TRW >= 1 && TCW >= 1 && BR % 16 == 0 && BC % 16 == 0, "tile");
   static_assert(BM % F::KSTEP == 0, "chunk");
   static_assert(PD >= 1, "prefetch depth");
-  // the LDS is reused for the fixed-order group reduction (G > 1) and the bias / sum-of-squares
-  // combines (256 floats)
+  // the LDS is reused for the fixed-order group reduction (G > 1) and the bias combine
+  // (256 floats)
   static_assert((G == 1 || (size_t)STAGE * 2 * G * sizeof(T) >= (size_t)256 * (NACC + 1) * sizeof(float)) &&
                     (size_t)STAGE * 2 * G * sizeof(T) >= 256 * sizeof(float),
                 "LDS reuse for the group reduction");
@@ -553,8 +547,7 @@ DEV void gemm_wg_body(const Op& op, float* __restrict__ slab, float* __restrict_
   const int m_beg = split * m_per_split;
   const int m_end = min(op.M, m_beg + m_per_split);
   const int wr = wave / WC, wc = wave % WC;
-  constexpr bool DIRECT = wg_direct<Op>::value;
-  const bool do_bias = (DIRECT || slab_bias != nullptr) && bx == 0;
+  const bool do_bias = slab_bias != nullptr && bx == 0;
   const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<T*>(op.x), 0, op.M * op.x_ld * (int)sizeof(T), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(
@@ -706,7 +699,6 @@ DEV void gemm_wg_body(const Op& op, float* __restrict__ slab, float* __restrict_
       __syncthreads();
     }
   }
-  float bias_sq = 0.f;  // DIRECT: this thread's final bias element, squared
   if (do_bias) {  // combine the (256/BR) row groups of group 0's bias sums, fixed order
     constexpr int RG = 256 / BR;
     float* redb = reinterpret_cast<float*>(smem);
@@ -716,41 +708,8 @@ DEV void gemm_wg_body(const Op& op, float* __restrict__ slab, float* __restrict_
       float bsum = 0.f;
 #pragma unroll
       for (int g = 0; g < RG; ++g) bsum += redb[g * BR + tid];
-      if constexpr (DIRECT) {
-        op.grads[op.bias_canon(r0 + tid)] = bsum;
-        bias_sq = bsum * bsum;
-      } else {
-        slab_bias[(size_t)split * op.R + r0 + tid] = bsum;
-      }
+      slab_bias[(size_t)split * op.R + r0 + tid] = bsum;
     }
-  }
-  if constexpr (DIRECT) {
-    __syncthreads();  // the bias sums above are read from smem before it is reused below
-    float sq = 0.f;
-    if (grp == 0) {
-#pragma unroll
-      for (int j = 0; j < TCW; ++j) {
-        const int c = c0 + (wc * TCW + j) * 16 + (lane & 15);
-#pragma unroll
-        for (int i = 0; i < TRW; ++i) {
-          const int r = r0 + (wr * TRW + i) * 16 + 4 * (lane >> 4);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float v = acc[i][j][q] * op.out_scale;
-            if (c < op.C) {
-              op.grads[op.canon(r + q, c)] = v;
-              sq += v * v;
-            }
-          }
-        }
-      }
-      sq = wave_sum(sq + bias_sq);
-    }
-    float* redq = reinterpret_cast<float*>(smem);
-    if (grp == 0 && lane == 0) redq[wave] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) op.sumsq[lin] = (redq[0] + redq[1]) + (redq[2] + redq[3]);
-    return;
   }
   if (grp != 0) return;
   const float sc = op.out_scale;

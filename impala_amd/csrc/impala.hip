@@ -79,8 +79,6 @@ inline double dec(float x) {
 struct Split {
   int S = 1, mps = 32;  // splits, m per split
 };
-// direct (one-split) FC weight-gradient tile: BR x BC outputs, WR x WC waves, G 4-wave groups
-constexpr int FCD_BR = 32, FCD_BC = 64, FCD_WR = 2, FCD_WC = 2, FCD_G = 4, FCD_PD = 2;
 // fp32 FC forward K loop: chunks held ahead, accumulator chains (gemm.h gemm_tile_body).
 // PF / KACC 1 / 1: 13.97 us, 2 / 1: 13.40, 1 / 2: 14.20, 2 / 2: 13.67-13.69 (r04v2,
 // tools/var_specs/fcpf.py); 2 / 1 keeps the summation order, so the output bits are unchanged
@@ -110,15 +108,14 @@ Split plan_split(long M, int tiles, int target_wgs, int chunk = 64) {
 enum KernelId {
   K_CONV1_FWD = 0, K_CONV2_FWD, K_CONV12_FWD, K_CONV3_FWD, K_FC_FWD, K_HEADS_FWD, K_HEAD_STEP, K_FC_DGRAD,
   K_LN_BWD, K_CONV3_DGRAD, K_LNC3_BWD, K_FC_WGRAD, K_CONV3_WGRAD, K_CONV2_WGRAD, K_CONV12_BWD, K_REDUCE,
-  K_SUMSQ, K_ADAM, K_REDUCE_ADAM, K_FC_BWD, K_WGRAD23, K_CONV123_FWD, K_LNC12_BWD, K_FWD_CHAIN,
+  K_SUMSQ, K_ADAM, K_FC_BWD, K_WGRAD23, K_CONV123_FWD, K_LNC12_BWD,
   K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "conv1_fwd", "conv2_fwd", "conv1_fwd_conv2_fwd", "conv3_fwd", "fc_fwd", "heads_fwd", "head_step", "fc_dgrad",
     "ln_bwd", "conv3_dgrad", "ln_bwd_conv3_dgrad", "fc_wgrad", "conv3_wgrad", "conv2_wgrad",
-    "conv2_dgrad_conv1_wgrad", "reduce_grads", "sumsq", "adam", "reduce_grads_adam", "fc_wgrad_fc_dgrad",
-    "conv3_wgrad_conv2_wgrad", "conv1_conv2_conv3_fwd", "ln_conv3_conv2_dgrad_conv1_wgrad",
-    "conv123_fwd_fc_fwd"};
+    "conv2_dgrad_conv1_wgrad", "reduce_grads", "sumsq", "adam", "fc_wgrad_fc_dgrad",
+    "conv3_wgrad_conv2_wgrad", "conv1_conv2_conv3_fwd", "ln_conv3_conv2_dgrad_conv1_wgrad"};
 
 struct impala_learner {
   impala_config cfg;
@@ -141,51 +138,23 @@ struct impala_learner {
   size_t ws_bytes = 0;
   void* shadow = nullptr;
   float* vecs = nullptr;
-  void *act1, *act2, *act3, *y, *h, *dH, *dz, *dact3, *dact2;
+  void *act1, *act2, *act3, *y, *h, *dz, *dact3, *dact2;
   uint32_t* mask1;  // conv1 ReLU bit mask [N][225]
   float *lnstat, *zg, *heads, *dy;  // zg = gelu'(FC pre-activation)
   float *s_w1, *s_b1, *s_w2, *s_b2, *s_w3, *s_b3, *s_ln, *s_fc, *s_bfc, *s_h, *s_bh;
   float *loss_part, *sumsq_part, *adam_sc;
   int64_t* step;
-  FusedSync fsync{};  // reduce_adam_kernel's granules, epoch counter and fault word
-  bool fused_update = false;  // world_size 1: slab reduction + clip + Adam in one launch
   bool fc_merged = true;      // FC weight + input gradients in one launch (fc_bwd_kernel)
   bool wg23_merged = true;    // conv3 + conv2 weight gradients in one launch (wgrad23_kernel)
   bool c3_tail = true;        // bf16: conv3 + LayerNorm as the tail of the fused conv1/conv2 forward
   bool lc12 = true;           // LayerNorm/conv3 dgrad + conv2 dgrad/conv1 wgrad in one launch
-  // the already-final slabs reduced inside the conv wgrad launch (opt-in IMPALA_EARLY_RED=1):
-  // bitwise equal, but the merged launch grew by 5.5 us and reduce_grads shrank by only 2 us
-  // (0.1214 / 0.1225 vs 0.1195 ms, reduction blocks last / first)
-  bool early_red = false;
-  // trunk forward + FC forward in one launch with per-producer flags (fwd_chain_kernel,
-  // opt-in IMPALA_FWD_CHAIN=1): bitwise equal, but 30.6 us against 22.8 + 5.8 us -- the FC
-  // tiles only start on CUs the conv workgroups free, all at the end (step 0.1202 vs 0.1180 ms)
-  bool fwd_chain = false;
-  unsigned* chain_flags = nullptr;  // [N] one word per conv workgroup
-  int fc_splitk = 0;                // fp32 FC forward: 1 = K split over workgroups (in-launch
-                                    // combine), 2 = K split over the waves of a workgroup
-  int fcsk_pub = 1;                 // its publish form (ops.h fc_fwd_splitk_f32)
-  float* fcsk_slab = nullptr;       // [tiles][4 splits][64 x 80] fp32 partials
-  unsigned* fcsk_cnt = nullptr;     // [tiles] ticket counters (grow by 4 per launch)
-  unsigned chain_epoch = 0;
   Split sp1, sp2, sp3, spfc, sph;
-  int n_ln_wg = 0, ln_fpw = 2, n_loss_wg = 0, S_seg = 32, n_red_wg = 0, n_adam_wg = 256;
-  // FC weight gradient in one split written straight into the canonical gradient (gemm_wg
-  // direct mode, no slab); its workgroups' sums of squares follow the reduction's partials
-  bool fc_direct = false;
-  int n_fc_wg = 0;
-  int n_norm_part = 0;  // clip-norm partials: n_red_wg (+ n_fc_wg)
+  // n_red_wg: slab-reduction workgroups = clip-norm partials (one sum of squares each)
+  int n_ln_wg = 0, ln_fpw = 2, n_loss_wg = 0, S_seg = 32, n_red_wg = 0;
   RedArgs red{};
-  // side stream for the weight-gradient branches (fork/join with events, graph-capturable)
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_join = nullptr;
-  bool use_side = true;
-  // live launch timer: hipEvent pairs around every launch of one kernel id
   int n_cu = 256;
   bool lnc3_fused = true;      // LayerNorm backward + conv3 dgrad in one per-frame kernel
   bool fwd_fused = true;       // conv1 + conv2 forward in one per-frame kernel
-  int red_mode = 0;           // slab reductions: 0 all at the end, 1 per branch, 2 side + conv1
   int c1_fpw = 1, c1_wg = 1;  // conv1 wgrad: frames per workgroup, workgroups (= splits)
   int c12f_fpw = 0;           // conv1+conv2 forward frames per workgroup (0: N / CUs)
   float* vt_dbg = nullptr;    // impala_set_debug_vtrace: the step's V-trace outputs
@@ -311,26 +280,6 @@ int launch_forward(impala_learner* h, const uint8_t* obs, int n, hipStream_t st,
       c3.act3 = (T*)h->act3; c3.y = (T*)h->y; c3.stats = h->lnstat;
       conv3_done = true;
     }
-    // training forward (no heads launch after it): the FC forward joins the launch, each FC
-    // tile waiting on flags of the conv workgroups that produce its frames (not under graph
-    // capture: the epoch argument changes every launch)
-#if IMPALA_AB
-    if (sizeof(T) == 2 && conv3_done && !with_heads && h->fwd_chain && !h->use_graph) {
-      if (++h->chain_epoch == 0) h->chain_epoch = 1;
-      c3.y_sc1 = 1;
-      using CC = FwdChainCfg<T>;
-      FcFwd<T> fop{n, sw + sh.wfc, vv + Vecs::bfc, (const T*)h->y, h->zg, (T*)h->h};
-      const int n_conv = cdiv(n, fpw), n_fc = (HID / CC::FR) * cdiv(n, CC::FC);
-      if constexpr (sizeof(T) == 2) {
-        if (int r = klaunch(h, K_FWD_CHAIN, "conv123_fwd_fc_fwd", fwd_chain_kernel<T>,
-                            dim3(n_conv + n_fc), dim3(512), st, obs, sw + sh.w1, vv + Vecs::b1,
-                            sw + sh.w2, vv + Vecs::b2, (T*)h->act1, h->mask1, (T*)h->act2, n, fpw,
-                            c3, n_conv, fop, h->chain_flags, h->chain_epoch, h->fsync.fault))
-          return r;
-      }
-      return 0;
-    }
-#endif
     // the frames from the batch arrays, or (impala_train_step_rows) from a replay ring in place
     auto fwd = [&](const auto& rm) {
       using O = std::decay_t<decltype(rm)>;
@@ -363,25 +312,6 @@ int launch_forward(impala_learner* h, const uint8_t* obs, int n, hipStream_t st,
                         dim3(persist_grid(h, cdiv((long)n * P3, 64))), dim3(256), st, op, 1))
       return r;
   }
-#if IMPALA_AB
-  if (sizeof(T) == 4 && h->fc_splitk == 2) {
-    FcFwd<float> op{n, (const float*)(sw + sh.wfc), vv + Vecs::bfc, (const float*)h->y, h->zg,
-                    (float*)h->h};
-    const int grid = (HID / fcwk::ROWS) * cdiv(n, fcwk::COLS);
-    if (int r = klaunch(h, K_FC_FWD, "fc_fwd_wsplit", fc_fwd_wsplit_f32, dim3(grid), dim3(256), st, op))
-      return r;
-  } else if (sizeof(T) == 4 && h->fc_splitk == 1) {
-    // fp32: 64 x 80 tiles, K split 4 ways, combined by each tile's last split (ops.h)
-    FcFwd<float> op{n, (const float*)(sw + sh.wfc), vv + Vecs::bfc, (const float*)h->y, h->zg,
-                    (float*)h->h};
-    const int grid = (HID / fcsk::ROWS) * cdiv(n, fcsk::COLS) * fcsk::NS;
-    auto kern = h->fcsk_pub == 0 ? fc_fwd_splitk_f32<0>
-                : h->fcsk_pub == 2 ? fc_fwd_splitk_f32<2> : fc_fwd_splitk_f32<1>;
-    if (int r = klaunch(h, K_FC_FWD, "fc_fwd_splitk", kern, dim3(grid), dim3(256), st, op,
-                        h->fcsk_slab, h->fcsk_cnt))
-      return r;
-  } else
-#endif
   {
     FcFwd<T> op{n, sw + sh.wfc, vv + Vecs::bfc, (const T*)h->y, h->zg, (T*)h->h};
     // 32 x 32 tiles: 320 workgroups (5.9 vs 6.7 us for 64 x 32, tools/var_specs/fcfwd.py);
@@ -414,22 +344,43 @@ int reduce_segments(impala_learner* h, int s_lo, int s_hi, hipStream_t st, int f
                  s_lo, fin);
 }
 
-// part: -1 = the whole backward; 0 = through the conv3 weight gradient, ending with the
-// reduction of gradient bucket 1 (conv3 .. heads, canonical [cn.w3, total)); 1 = the rest
-// (conv2 weight gradient, conv2 dgrad + conv1 wgrad, bucket 0 = conv1 + conv2, loss metrics).
-// Data-parallel replicas all-reduce bucket 1 while part 1 runs.  Three-bucket split: 2 = heads
-// step, FC weight gradient and FC dgrad, ending with the reduction of [cn.wfc, total) (FC +
-// heads); 3 = LayerNorm backward + conv3 dgrad and the conv3 weight gradient, ending with
-// [cn.w3, cn.wfc) (conv3 + LayerNorm); 4 = part 1.  Any split gives bit-identical gradients
-// (each reduction workgroup owns a fixed sum-of-squares slot).
+// The backward is three stages on one stream:
+//   head_fc  head_step_kernel (heads forward, loss, dz, heads weight gradient), then the FC
+//            weight and input gradients (fc_bwd_kernel, or gemm_wg<FcWgrad> + gemm_tile<FcDgrad>)
+//   ln_c3    LayerNorm backward + conv3 dgrad, and the conv3 weight gradient
+//   c2_c1    conv2 weight gradient, and conv2 dgrad + conv1 wgrad
+// A part runs a range of stages, then one reduction of the slab segments those stages (and no
+// earlier part) completed; `fin` also finalises the loss metrics and the step counter.  -1 is
+// the whole backward.  Data-parallel replicas all-reduce a reduced gradient bucket while the
+// next part runs: 0 then 1 (buckets [cn.w3, total) and [0, cn.w3)), 2 / 3 / 4 (FC + heads,
+// conv3 + LayerNorm, conv1 + conv2), or 2 then 6 (the native step: [cn.wfc, total) and
+// [0, cn.wfc)).  Any split gives bit-identical gradients (each reduction workgroup owns a
+// fixed sum-of-squares slot).
+enum BwdStage { BS_HEAD_FC = 0, BS_LN_C3, BS_C2_C1 };
+struct BwdPart {
+  int part, first, last, red_lo, red_hi, fin;
+};
+constexpr BwdPart kBwdParts[] = {
+    {-1, BS_HEAD_FC, BS_C2_C1, RS_CONV1, RS_END, 1},
+    {0, BS_HEAD_FC, BS_LN_C3, RS_CONV3, RS_END, 0},
+    {1, BS_C2_C1, BS_C2_C1, RS_CONV1, RS_CONV3, 1},
+    {2, BS_HEAD_FC, BS_HEAD_FC, RS_FC, RS_END, 0},
+    {3, BS_LN_C3, BS_LN_C3, RS_CONV3, RS_FC, 0},
+    {4, BS_C2_C1, BS_C2_C1, RS_CONV1, RS_CONV3, 1},
+    {6, BS_LN_C3, BS_C2_C1, RS_CONV1, RS_FC, 1},
+};
+const BwdPart* bwd_part(int part) {
+  for (const BwdPart& p : kBwdParts)
+    if (p.part == part) return &p;
+  return nullptr;
+}
+
 template <typename T>
-int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, int part = -1) {
+int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, const BwdPart* bp) {
   using namespace net;
   const int N = h->N, B = h->cfg.batch_size, Tl = h->cfg.rollout_length;
   const T* sw = reinterpret_cast<const T*>(h->shadow);
   const Shadow& sh = h->sh;
-  // ---- dgrad chain on `st`; each weight-gradient branch forks onto the side stream as soon
-  // as its inputs exist and joins before the slab reduction ----
   // gemm_wg: 32-row m-chunks, several 4-wave groups per workgroup on interleaved chunks (more
   // chunk loads in flight per CU); fp32 keeps one group for its LDS budget.  The bf16 conv
   // weight gradients run 2 groups (56 KB of LDS: two workgroups per CU) rather than 4 (112 KB:
@@ -437,30 +388,16 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, in
   // -> 0.1000 ms (tools/var_specs/bfg.py, profiles/r05bg).  The bf16 FC weight gradient keeps 2
   // (one group: 8.2 -> 8.9 us).
   constexpr int WG4 = sizeof(T) == 2 ? 2 : 1, WG2 = sizeof(T) == 2 ? 2 : 1;
-  hipStream_t ss = h->use_side ? h->side : st;
-  auto fork = [&](int i) -> int {
-    if (!h->use_side) return 0;
-    CK(hipEventRecord(h->ev_fork[i], st));
-    CK(hipStreamWaitEvent(ss, h->ev_fork[i], 0));
-    return 0;
-  };
-  // FC weight and input gradients in one launch (single stream, slab FC weight gradient)
-  const bool fc_merged = h->fc_merged && !h->fc_direct && !h->use_side && h->red_mode != 1;
-  // conv3 + conv2 weight gradients in one launch (whole backward only: the data-parallel parts
-  // end a gradient bucket between them)
-  const bool whole = part == -1 || part == 5 || part == 6;  // the backward after the FC bucket
-  const bool wg23 = h->wg23_merged && whole && !h->use_side && h->red_mode == 0;
-  // the two per-frame backward chains in one launch (whole backward, same frame runs)
-  const bool lc12 = h->lc12 && h->lnc3_fused && h->ln_fpw == h->c1_fpw && whole &&
-                    !h->use_side && h->red_mode == 0;
-  // with the per-frame backward fused ahead of the merged conv weight gradients, every slab
-  // but conv2 / conv3 is final when the latter start: reduce those inside that launch
-  // (not for part 5: the fused reduce + Adam reduces every unit itself)
-  const bool early = h->early_red && lc12 && wg23 && part != 5;
-  if (part == 1 || part == 4) goto part1;
-  if (part == 3 || part == 6) goto stage_b;
-  // ---- fused head: heads fwd, log-softmax / V-trace / loss, dz, heads weight gradient ----
-  {
+  // The two cross-stage fusions need ln_c3 and c2_c1 in one range (the data-parallel parts 0 / 1
+  // and 3 / 4 end a gradient bucket between them): conv3 + conv2 weight gradients in one launch,
+  // and the two per-frame chains in one launch (same frame runs)
+  const bool both = bp->first <= BS_LN_C3 && bp->last == BS_C2_C1;
+  const bool wg23 = h->wg23_merged && both;
+  const bool lc12 = h->lc12 && h->lnc3_fused && h->ln_fpw == h->c1_fpw && both;
+
+  // ---- head_fc: heads fwd, log-softmax / V-trace / loss, dz, heads weight gradient; then the
+  // FC weight and input gradients ----
+  auto head_fc = [&]() -> int {
     HeadArgs ha{};
     ha.h = h->h; ha.zg = h->zg; ha.wh = sw + sh.wh; ha.wht = sw + sh.wht;
     ha.bh = h->vecs + Vecs::bh;
@@ -485,207 +422,115 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, in
                     : klaunch(h, K_HEAD_STEP, "head_step", head_step_kernel<T, false>, hg, dim3(256), st, ha,
                               ObsDirect{}))
       return r;
-  }
-  if (int r = fork(1)) return r;  // dz ready
-  if (fc_merged) {
     FcWgrad<T> ow{};
     ow.M = N; ow.x = (const T*)h->dz; ow.y = (const T*)h->y;
     FcDgrad<T> od{N, sw + sh.wfc, (const T*)h->dz, h->dy};
-    using C = FcBwdCfg<T, WG2>;
-    const int gx = FLAT / C::WBC, gy = HID / 64, gz = h->spfc.S;
-    const int n_rt = FLAT / C::DR, n_dt = n_rt * cdiv(N, C::DC);
-    if (int r = klaunch(h, K_FC_BWD, "fc_wgrad_fc_dgrad", fc_bwd_kernel<T, WG2>,
-                        dim3(gx * gy * gz + n_dt), dim3(256 * WG2), st, ow, h->s_fc, h->s_bfc,
-                        h->spfc.mps, gx, gy, gz, od, n_rt))
-      return r;
-  } else if (h->fc_direct) {
-    FcWgradDirect<T> op{};
-    op.M = N; op.x = (const T*)h->dz; op.y = (const T*)h->y;
-    op.grads = h->grads; op.wcanon = (long long)h->cn.wfc; op.sumsq = h->sumsq_part + h->n_red_wg;
-    constexpr int G = sizeof(T) == 2 ? FCD_G : 1;
-    if (int r = klaunch(h, K_FC_WGRAD, "fc_wgrad",
-                        gemm_wg<T, FCD_BR, FCD_BC, FCD_WR, FCD_WC, 32, G, FcWgradDirect<T>, FCD_PD>,
-                        dim3(FLAT / FCD_BC, HID / FCD_BR, 1), dim3(256 * G), ss, op, nullptr,
-                        nullptr, N))
-      return r;
-  } else {
-    FcWgrad<T> op{};
-    op.M = N; op.x = (const T*)h->dz; op.y = (const T*)h->y;
+    if (h->fc_merged) {  // both in one launch
+      using C = FcBwdCfg<T, WG2>;
+      const int gx = FLAT / C::WBC, gy = HID / 64, gz = h->spfc.S;
+      const int n_rt = FLAT / C::DR, n_dt = n_rt * cdiv(N, C::DC);
+      return klaunch(h, K_FC_BWD, "fc_wgrad_fc_dgrad", fc_bwd_kernel<T, WG2>,
+                     dim3(gx * gy * gz + n_dt), dim3(256 * WG2), st, ow, h->s_fc, h->s_bfc,
+                     h->spfc.mps, gx, gy, gz, od, n_rt);
+    }
     if (int r = klaunch(h, K_FC_WGRAD, "fc_wgrad", gemm_wg<T, 64, 256, 1, 4, 32, WG2, FcWgrad<T>>,
-                        dim3(FLAT / 256, HID / 64, h->spfc.S), dim3(256 * WG2), ss, op, h->s_fc,
+                        dim3(FLAT / 256, HID / 64, h->spfc.S), dim3(256 * WG2), st, ow, h->s_fc,
                         h->s_bfc, h->spfc.mps))
       return r;
-  }
-  {
-    if (h->red_mode == 1)
-      if (int r = reduce_segments(h, RS_FC, RS_END, ss, 0)) return r;  // fc + heads slabs
-  }
-  if (!fc_merged) {
-    FcDgrad<T> op{N, sw + sh.wfc, (const T*)h->dz, h->dy};
-    if (int r = klaunch(h, K_FC_DGRAD, "fc_dgrad", gemm_tile<T, 64, 64, BK(128), 2, 2, FcDgrad<T>>,
-                        dim3(persist_grid(h, (long)cdiv(N, 64) * (FLAT / 64))), dim3(256), st, op,
-                        FLAT / 64))
-      return r;
-  }
-  if (part == 2) {  // bucket FC + heads complete
-    if (h->use_side) {
-      CK(hipEventRecord(h->ev_join, ss));
-      CK(hipStreamWaitEvent(st, h->ev_join, 0));
+    return klaunch(h, K_FC_DGRAD, "fc_dgrad", gemm_tile<T, 64, 64, BK(128), 2, 2, FcDgrad<T>>,
+                   dim3(persist_grid(h, (long)cdiv(N, 64) * (FLAT / 64))), dim3(256), st, od,
+                   FLAT / 64);
+  };
+
+  // ---- ln_c3: LayerNorm backward + conv3 dgrad (with lc12, c2_c1's per-frame kernel too), and
+  // the conv3 weight gradient (with wg23, conv2's too) ----
+  auto ln_c3 = [&]() -> int {
+    if (lc12) {
+      auto bwd = [&](const auto& rm) {
+        using O = std::decay_t<decltype(rm)>;
+        return klaunch(h, K_LNC12_BWD, "ln_conv3_conv2_dgrad_conv1_wgrad", lnc3_conv12_bwd<T, O>,
+                       dim3(h->n_ln_wg), dim3(lnc3_threads<T>()), st, (const float*)h->dy,
+                       (const T*)h->act3, (const float*)h->lnstat,
+                       (const float*)(h->vecs + Vecs::lng), sw + sh.w3, sw + sh.w3t,
+                       (const T*)h->act2, (T*)h->dact3, (T*)h->dact2, h->s_ln, b->obs,
+                       sw + sh.w2, sw + sh.w2t, (const uint32_t*)h->mask1, h->s_w1, h->s_b1, N,
+                       h->ln_fpw, rm);
+      };
+      if (int r = h->rows_on ? bwd(h->obs_rows) : bwd(ObsDirect{})) return r;
+    } else if (h->lnc3_fused) {  // LayerNorm backward + conv3 dgrad per frame
+      if (int r = klaunch(h, K_LNC3_BWD, "ln_bwd_conv3_dgrad", lnc3_bwd<T>, dim3(h->n_ln_wg),
+                          dim3(lnc3_threads<T>()), st, (const float*)h->dy, (const T*)h->act3,
+                          (const float*)h->lnstat, (const float*)(h->vecs + Vecs::lng), sw + sh.w3,
+                          sw + sh.w3t, (const T*)h->act2, (T*)h->dact3, (T*)h->dact2, h->s_ln, N,
+                          h->ln_fpw))
+        return r;
+    } else {
+      if (int r = klaunch(h, K_LN_BWD, "ln_bwd", ln_bwd_kernel<T>, dim3(h->n_ln_wg), dim3(256), st,
+                          (const float*)h->dy, (const T*)h->act3, (const float*)h->lnstat,
+                          (const float*)(h->vecs + Vecs::lng), (T*)h->dact3, h->s_ln, N, h->ln_fpw))
+        return r;
     }
-    return reduce_segments(h, RS_FC, RS_END, st, 0);
-  }
-stage_b:
-  if (lc12) {
-    auto bwd = [&](const auto& rm) {
-      using O = std::decay_t<decltype(rm)>;
-      return klaunch(h, K_LNC12_BWD, "ln_conv3_conv2_dgrad_conv1_wgrad", lnc3_conv12_bwd<T, O>,
-                     dim3(h->n_ln_wg), dim3(lnc3_threads<T>()), st, (const float*)h->dy,
-                     (const T*)h->act3, (const float*)h->lnstat,
-                     (const float*)(h->vecs + Vecs::lng), sw + sh.w3, sw + sh.w3t,
-                     (const T*)h->act2, (T*)h->dact3, (T*)h->dact2, h->s_ln, b->obs,
-                     sw + sh.w2, sw + sh.w2t, (const uint32_t*)h->mask1, h->s_w1, h->s_b1, N,
-                     h->ln_fpw, rm);
+    // IMPALA_LNC3_FUSED=0: dact2 comes from a separate conv3 dgrad
+    auto conv3_dgrad = [&]() -> int {
+      if (h->lnc3_fused) return 0;
+      Conv3Dgrad<T> op{N * P2, sw + sh.w3, (const T*)h->dact3, (const T*)h->act2, (T*)h->dact2};
+      return klaunch(h, K_CONV3_DGRAD, "conv3_dgrad", gemm_tile<T, 64, 128, BK(64), 1, 4, Conv3Dgrad<T>>,
+                     dim3(persist_grid(h, cdiv((long)N * P2, 128))), dim3(256), st, op, 1);
     };
-    if (int r = h->rows_on ? bwd(h->obs_rows) : bwd(ObsDirect{})) return r;
-  } else if (h->lnc3_fused) {  // LayerNorm backward + conv3 dgrad per frame
-    if (int r = klaunch(h, K_LNC3_BWD, "ln_bwd_conv3_dgrad", lnc3_bwd<T>, dim3(h->n_ln_wg),
-                        dim3(lnc3_threads<T>()), st, (const float*)h->dy, (const T*)h->act3,
-                        (const float*)h->lnstat, (const float*)(h->vecs + Vecs::lng), sw + sh.w3,
-                        sw + sh.w3t, (const T*)h->act2, (T*)h->dact3, (T*)h->dact2, h->s_ln, N,
-                        h->ln_fpw))
-      return r;
-  } else {
-    if (int r = klaunch(h, K_LN_BWD, "ln_bwd", ln_bwd_kernel<T>, dim3(h->n_ln_wg), dim3(256), st,
-                        (const float*)h->dy, (const T*)h->act3, (const float*)h->lnstat,
-                        (const float*)(h->vecs + Vecs::lng), (T*)h->dact3, h->s_ln, N, h->ln_fpw))
-      return r;
-  }
-  if (int r = fork(2)) return r;  // dact3 ready
-  if (wg23) {
     Conv3Wgrad<T> o3{};
     o3.M = N * P3; o3.x = (const T*)h->dact3; o3.in = (const T*)h->act2;
-    Conv2Wgrad<T> o2{};
-    o2.M = N * P2; o2.x = (const T*)h->dact2; o2.in = (const T*)h->act1;
-    if (!h->lnc3_fused) {  // dact2 comes from the separate conv3 dgrad
-      Conv3Dgrad<T> op{N * P2, sw + sh.w3, (const T*)h->dact3, (const T*)h->act2, (T*)h->dact2};
-      if (int r = klaunch(h, K_CONV3_DGRAD, "conv3_dgrad", gemm_tile<T, 64, 128, BK(64), 1, 4, Conv3Dgrad<T>>,
-                          dim3(persist_grid(h, cdiv((long)N * P2, 128))), dim3(256), st, op, 1))
-        return r;
+    if (wg23) {  // conv2's weight gradient reads dact2: after the conv3 dgrad
+      if (int r = conv3_dgrad()) return r;
+      Conv2Wgrad<T> o2{};
+      o2.M = N * P2; o2.x = (const T*)h->dact2; o2.in = (const T*)h->act1;
+      const int g3x = K3 / 64, g3z = h->sp3.S, g2x = K2 / Wg2Tile<T>::BC, g2z = h->sp2.S;
+      return klaunch(h, K_WGRAD23, "conv3_wgrad_conv2_wgrad", wgrad23_kernel<T, WG4>,
+                     dim3(g3x * g3z + g2x * g2z), dim3(256 * WG4), st, o3, h->s_w3, h->s_b3,
+                     h->sp3.mps, g3x, g3z, o2, h->s_w2, h->s_b2, h->sp2.mps, g2x, g2z);
     }
-    const int g3x = K3 / 64, g3z = h->sp3.S, g2x = K2 / Wg2Tile<T>::BC, g2z = h->sp2.S;
-#if IMPALA_AB
-    if (early) {
-      // conv1 + b1 and LayerNorm (+ FC and heads unless part 2 reduced them) units ride along
-      const int* ws = h->red.wg_start;
-      const int u0 = ws[RS_CONV1], n0 = ws[RS_CONV2] - ws[RS_CONV1];
-      const int u1 = ws[RS_LN], n1 = (part == 6 ? ws[RS_FC] : ws[RS_END]) - ws[RS_LN];
-      if (int r = klaunch(h, K_WGRAD23, "conv3_wgrad_conv2_wgrad", wgrad23r_kernel<T, WG4>,
-                          dim3(g3x * g3z + g2x * g2z + cdiv(n0 + n1, WG4)), dim3(256 * WG4), st,
-                          o3, h->s_w3, h->s_b3, h->sp3.mps, g3x, g3z, o2, h->s_w2, h->s_b2,
-                          h->sp2.mps, g2x, g2z, h->red, u0, n0, u1, n1))
-        return r;
-    } else
-#endif
-    if (int r = klaunch(h, K_WGRAD23, "conv3_wgrad_conv2_wgrad", wgrad23_kernel<T, WG4>,
-                               dim3(g3x * g3z + g2x * g2z), dim3(256 * WG4), st, o3, h->s_w3,
-                               h->s_b3, h->sp3.mps, g3x, g3z, o2, h->s_w2, h->s_b2, h->sp2.mps,
-                               g2x, g2z)) {
-      return r;
-    }
-    goto conv12b;
-  }
-  {
-    Conv3Wgrad<T> op{};
-    op.M = N * P3; op.x = (const T*)h->dact3; op.in = (const T*)h->act2;
     // 64 x 64 tiles (9 column tiles x ~28 splits): 4.1 MB of partial slabs instead of 9.4 MB
     // for 64 x 192 tiles x 64 splits, and 9.1 vs 9.8 us (profiles/r02b)
     if (int r = klaunch(h, K_CONV3_WGRAD, "conv3_wgrad", gemm_wg<T, 64, 64, 2, 2, 32, WG4, Conv3Wgrad<T>>,
-                        dim3(K3 / 64, 1, h->sp3.S), dim3(256 * WG4), ss, op, h->s_w3, h->s_b3,
+                        dim3(K3 / 64, 1, h->sp3.S), dim3(256 * WG4), st, o3, h->s_w3, h->s_b3,
                         h->sp3.mps))
       return r;
-    if (h->red_mode == 1)
-      if (int r = reduce_segments(h, RS_CONV3, RS_FC, ss, 0)) return r;  // conv3 + LayerNorm
-  }
-  if (!h->lnc3_fused) {
-    Conv3Dgrad<T> op{N * P2, sw + sh.w3, (const T*)h->dact3, (const T*)h->act2, (T*)h->dact2};
-    if (int r = klaunch(h, K_CONV3_DGRAD, "conv3_dgrad", gemm_tile<T, 64, 128, BK(64), 1, 4, Conv3Dgrad<T>>,
-                        dim3(persist_grid(h, cdiv((long)N * P2, 128))), dim3(256), st, op, 1))
-      return r;
-  }
-  if (part == 0 || part == 3) {  // bucket 1 (or conv3 + LayerNorm) complete
-    if (h->use_side) {
-      CK(hipEventRecord(h->ev_join, ss));
-      CK(hipStreamWaitEvent(st, h->ev_join, 0));
+    return conv3_dgrad();
+  };
+
+  // ---- c2_c1: conv2 weight gradient (unless wg23 ran it), then conv2 input gradient
+  // (ReLU-masked) + conv1 weight gradient fused per frame (unless lc12 ran it) ----
+  auto c2_c1 = [&]() -> int {
+    if (!wg23) {
+      Conv2Wgrad<T> op{};
+      op.M = N * P2; op.x = (const T*)h->dact2; op.in = (const T*)h->act1;
+      if (int r = klaunch(h, K_CONV2_WGRAD, "conv2_wgrad", gemm_wg<T, 64, 128, 1, 4, 32, WG4, Conv2Wgrad<T>>,
+                          dim3(K2 / 128, 1, h->sp2.S), dim3(256 * WG4), st, op, h->s_w2, h->s_b2,
+                          h->sp2.mps))
+        return r;
     }
-    return reduce_segments(h, RS_CONV3, part == 0 ? RS_END : RS_FC, st, 0);
+    if (lc12) return 0;
+    return klaunch(h, K_CONV12_BWD, "conv2_dgrad_conv1_wgrad", conv12_bwd_s2d<T>, dim3(h->c1_wg),
+                   dim3(256 * c12_groups<T>()), st, b->obs, sw + sh.w2, sw + sh.w2t,
+                   (const T*)h->dact2, (const uint32_t*)h->mask1, h->s_w1, h->s_b1, N, h->c1_fpw);
+  };
+
+  for (int s = bp->first; s <= bp->last; ++s) {
+    int r = 0;
+    switch (s) {
+      case BS_HEAD_FC: r = head_fc(); break;
+      case BS_LN_C3: r = ln_c3(); break;
+      case BS_C2_C1: r = c2_c1(); break;
+    }
+    if (r) return r;
   }
-part1:
-  if (int r = fork(3)) return r;  // dact2 ready
-  {
-    Conv2Wgrad<T> op{};
-    op.M = N * P2; op.x = (const T*)h->dact2; op.in = (const T*)h->act1;
-    if (int r = klaunch(h, K_CONV2_WGRAD, "conv2_wgrad", gemm_wg<T, 64, 128, 1, 4, 32, WG4, Conv2Wgrad<T>>,
-                        dim3(K2 / 128, 1, h->sp2.S), dim3(256 * WG4), ss, op, h->s_w2, h->s_b2,
-                        h->sp2.mps))
-      return r;
-    if (h->red_mode == 1) {
-      if (int r = reduce_segments(h, RS_CONV2, RS_CONV3, ss, 0)) return r;
-    } else if (h->red_mode == 2 && part != 1 && part != 4 && part != 6) {
-      // (parts 1 / 4 / 6: conv3 .. heads, or FC + heads, were reduced by an earlier part and
-      // may be in an all-reduce right now; the final reduction below covers the rest)
-      if (int r = reduce_segments(h, RS_CONV2, RS_END, ss, 0)) return r;
-    }
-  }
-conv12b:
-  // conv2 input gradient (ReLU-masked) + conv1 weight gradient, fused per frame
-  if (!lc12)
-    if (int r = klaunch(h, K_CONV12_BWD, "conv2_dgrad_conv1_wgrad", conv12_bwd_s2d<T>,
-                        dim3(h->c1_wg), dim3(256 * c12_groups<T>()), st, b->obs, sw + sh.w2,
-                        sw + sh.w2t, (const T*)h->dact2, (const uint32_t*)h->mask1, h->s_w1, h->s_b1, N,
-                        h->c1_fpw))
-      return r;
-  // ---- last slab reduction (conv1) + loss metrics + step += 1; the other branches were
-  // reduced on the side stream right after their weight gradients ----
-  if (part == 6) {  // the conv + LayerNorm bucket [0, cn.wfc) + loss metrics + step
-    if (h->use_side) {
-      CK(hipEventRecord(h->ev_join, ss));
-      CK(hipStreamWaitEvent(st, h->ev_join, 0));
-    }
-    return early ? reduce_segments(h, RS_CONV2, RS_LN, st, 1) : reduce_segments(h, RS_CONV1, RS_FC, st, 1);
-  }
-  if (part == 1 || part == 4) {
-    if (h->use_side) {
-      CK(hipEventRecord(h->ev_join, ss));
-      CK(hipStreamWaitEvent(st, h->ev_join, 0));
-    }
-    return reduce_segments(h, RS_CONV1, RS_CONV3, st, 1);
-  }
-  if (h->red_mode == 0) {
-    if (h->use_side) {  // join
-      CK(hipEventRecord(h->ev_join, ss));
-      CK(hipStreamWaitEvent(st, h->ev_join, 0));
-    }
-    if (part == 5) return 0;  // the fused update kernel reduces the slabs
-    if (early) {  // conv1, LayerNorm, FC and heads were reduced beside the conv weight gradients
-      if (int r = reduce_segments(h, RS_CONV2, RS_LN, st, 1)) return r;
-    } else if (int r = reduce_segments(h, RS_CONV1, RS_END, st, 1)) {
-      return r;
-    }
-  } else {
-    if (int r = reduce_segments(h, RS_CONV1, RS_CONV2, st, 1)) return r;
-    if (h->use_side) {  // join
-      CK(hipEventRecord(h->ev_join, ss));
-      CK(hipStreamWaitEvent(st, h->ev_join, 0));
-    }
-  }
-  return 0;
+  return reduce_segments(h, bp->red_lo, bp->red_hi, st, bp->fin);
 }
 
 template <typename T>
 int launch_adam(impala_learner* h, hipStream_t st) {
   AdamArgs aa{};
   aa.params = h->params; aa.grads = h->grads; aa.m = h->exp_avg; aa.v = h->exp_avg_sq;
-  aa.metrics = h->metrics; aa.sumsq_part = h->sumsq_part; aa.n_part = h->n_norm_part;
+  aa.metrics = h->metrics; aa.sumsq_part = h->sumsq_part; aa.n_part = h->n_red_wg;
   aa.metrics_host = h->metrics_host;
   aa.step = h->step;
   aa.sc = h->adam_sc; aa.b1 = dec(h->cfg.adam_beta1); aa.b2 = dec(h->cfg.adam_beta2);
@@ -698,25 +543,6 @@ int launch_adam(impala_learner* h, hipStream_t st) {
   return klaunch(h, K_ADAM, "adam", adam_kernel<T>, dim3(net::HID + cdiv(rest, 256)),
                  dim3(256), st, aa);
 }
-
-#if IMPALA_AB
-// slab reduction + clip + Adam in one launch (world_size 1; backward run with part 5)
-template <typename T>
-int launch_reduce_adam(impala_learner* h, hipStream_t st) {
-  AdamArgs aa{};
-  aa.params = h->params; aa.grads = h->grads; aa.m = h->exp_avg; aa.v = h->exp_avg_sq;
-  aa.metrics = h->metrics; aa.sumsq_part = h->sumsq_part; aa.n_part = h->n_norm_part;
-  aa.step = h->step;
-  aa.sc = h->adam_sc; aa.b1 = dec(h->cfg.adam_beta1); aa.b2 = dec(h->cfg.adam_beta2);
-  aa.eps = h->cfg.adam_eps; aa.max_norm = h->cfg.max_grad_norm;
-  aa.inv_world = 1.f / (float)h->cfg.world_size;
-  aa.sp = ShadowPtrs{h->shadow, h->vecs, h->A};
-  aa.cn = h->cn; aa.sh = h->sh;
-  return klaunch(h, K_REDUCE_ADAM, "reduce_grads_adam", reduce_adam_kernel<T>,
-                 dim3(cdiv(h->n_red_wg, FU_MAX_UNITS)),
-                 dim3(256), st, h->red, aa, h->fsync);
-}
-#endif  // IMPALA_AB
 
 template <typename T>
 int launch_pack(impala_learner* h, hipStream_t st) {
@@ -869,19 +695,6 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
   if (cfg->dtype != IMPALA_DTYPE_F32 && cfg->dtype != IMPALA_DTYPE_BF16)
     return fail(IMPALA_E_INVALID, "unknown dtype");
   if (cfg->world_size < 1) return fail(IMPALA_E_INVALID, "world_size must be >= 1");
-#if !IMPALA_AB
-  // the measured-slower alternatives are compiled into A/B builds only (common.h IMPALA_AB)
-  for (const char* v : {"IMPALA_FC_SPLITK", "IMPALA_FWD_CHAIN", "IMPALA_FUSED_UPDATE",
-                        "IMPALA_EARLY_RED"}) {
-    // the split-K FC forward is an fp32-only variant: bf16 handles ignore the switch, as the
-    // A/B build does
-    if (cfg->dtype != IMPALA_DTYPE_F32 && std::string(v) == "IMPALA_FC_SPLITK") continue;
-    const char* e = std::getenv(v);
-    if (e && e[0] && e[0] != '0')
-      return fail(IMPALA_E_UNSUPPORTED, std::string(v) + " selects an A/B variant this library "
-                                        "was built without (python -m impala_amd.build --ab)");
-  }
-#endif
   CK(hipSetDevice(device));
   impala_learner* h = new (std::nothrow) impala_learner();
   if (!h) return fail(IMPALA_E_INVALID, "out of host memory");
@@ -920,14 +733,6 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
   int fc_wg = h->bf16 ? 96 : 128;
   if (const char* e = std::getenv("IMPALA_FC_WG")) fc_wg = std::max(16, std::atoi(e));
   h->spfc = plan_split(N, (FLAT / 256) * (HID / 64), fc_wg);
-  // one-split FC weight gradient written straight into the canonical gradient (opt-in,
-  // IMPALA_FC_DIRECT=1, up to 8192 frames): it drops the 6.3 MB FC slab and 256 reduction
-  // workgroups, but the one-split GEMM is latency-bound on its per-CU load concurrency and the
-  // step measured 0.1340-0.1368 ms in every tile shape against 0.1325-0.1330 ms for the split
-  // slab (profiles/r02d/fc_direct_variants.txt)
-  h->fc_direct = false;
-  if (const char* e = std::getenv("IMPALA_FC_DIRECT")) h->fc_direct = N <= 8192 && e[0] == '1';
-  h->n_fc_wg = (FLAT / FCD_BC) * (HID / FCD_BR);
   // the conv weight gradients' m splits: ~256 workgroups each (IMPALA_WG3_TARGET /
   // IMPALA_WG2_TARGET override the count for A/B runs; more splits, more slab bytes to reduce)
   int wg3 = 256, wg2 = 256;
@@ -955,7 +760,6 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
   const size_t o_act3 = take((size_t)N * FLAT * es);
   const size_t o_y = take((size_t)N * YLD * es);
   const size_t o_h = take((size_t)N * HID * es);
-  const size_t o_dH = take((size_t)N * HPAD * es);
   const size_t o_dz = take((size_t)N * HID * es);
   const size_t o_dact3 = take((size_t)N * FLAT * es);
   const size_t o_dact2 = take((size_t)N * P2 * OC2 * es);
@@ -979,13 +783,6 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
   const size_t o_spart = take((size_t)(h->n_red_wg + 3) / 4 * 16);  // zero tail: float4 reads
   const size_t o_adsc = take(2 * 4);
   const size_t o_step = take(8);
-  const size_t o_gran = take((size_t)h->n_red_wg * 8);  // fused update granules (upper bound)
-  const size_t o_fsync = take(16);                       // epoch counter, fault word
-  const size_t o_chain = take((size_t)N * 4);            // forward-chain producer flags
-  if (const char* e = std::getenv("IMPALA_FC_SPLITK")) h->fc_splitk = es == 4 ? std::atoi(e) : 0;
-  const size_t fcsk_tiles = h->fc_splitk == 1 ? (size_t)(HID / fcsk::ROWS) * cdiv(N, fcsk::COLS) : 0;
-  const size_t o_fcsk = take(fcsk_tiles * fcsk::NS * fcsk::PART * 4);  // opt-in split-K partials
-  const size_t o_fcskc = take(fcsk_tiles * 4);
   h->ws_bytes = off;
   hipError_t e = hipMalloc(&h->ws, off);
   if (e != hipSuccess) {
@@ -1002,7 +799,7 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
   h->shadow = w + o_shadow;
   h->vecs = (float*)(w + o_vecs);
   h->act1 = w + o_act1; h->act2 = w + o_act2; h->act3 = w + o_act3; h->y = w + o_y;
-  h->h = w + o_h; h->dH = w + o_dH; h->dz = w + o_dz; h->dact3 = w + o_dact3;
+  h->h = w + o_h; h->dz = w + o_dz; h->dact3 = w + o_dact3;
   h->dact2 = w + o_dact2; h->mask1 = (uint32_t*)(w + o_mask1);
   h->lnstat = (float*)(w + o_lnstat); h->zg = (float*)(w + o_z); h->heads = (float*)(w + o_heads);
   h->dy = (float*)(w + o_dy);
@@ -1014,21 +811,11 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
   h->loss_part = (float*)(w + o_lpart); h->sumsq_part = (float*)(w + o_spart);
   h->adam_sc = (float*)(w + o_adsc);
   h->step = (int64_t*)(w + o_step);
-  h->fsync.gran = (unsigned long long*)(w + o_gran);
-  h->fsync.epoch_ctr = (unsigned*)(w + o_fsync);
-  h->fsync.fault = (unsigned*)(w + o_fsync + 4);
-  h->chain_flags = (unsigned*)(w + o_chain);
-  h->fcsk_slab = (float*)(w + o_fcsk);
-  h->fcsk_cnt = (unsigned*)(w + o_fcskc);
-  if (const char* e = std::getenv("IMPALA_FCSK_PUB")) h->fcsk_pub = std::atoi(e);
-  if (const char* rm = std::getenv("IMPALA_RED_MODE")) h->red_mode = std::atoi(rm);
   if (const char* ff = std::getenv("IMPALA_FWD_FUSED")) h->fwd_fused = ff[0] != '0';
   if (const char* e = std::getenv("IMPALA_FC_MERGED")) h->fc_merged = e[0] != '0';
   if (const char* e = std::getenv("IMPALA_WG23_MERGED")) h->wg23_merged = e[0] != '0';
   if (const char* e = std::getenv("IMPALA_C3_TAIL")) h->c3_tail = e[0] != '0';
   if (const char* e = std::getenv("IMPALA_LC12")) h->lc12 = e[0] != '0';
-  if (const char* e = std::getenv("IMPALA_EARLY_RED")) h->early_red = e[0] == '1';
-  if (const char* e = std::getenv("IMPALA_FWD_CHAIN")) h->fwd_chain = e[0] == '1';
   // hipGraph replay of whole steps (opt-in): it cuts the host enqueue cost of a step ~3x, but
   // on MI355X / ROCm 7 the replayed step ran slower on the device than direct launches
   // (174 vs 165 us), so direct launches are the default
@@ -1038,22 +825,6 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
   if (h->use_graph && hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking) != hipSuccess) {
     impala_destroy(h);
     return fail(IMPALA_E_STATE, "hipStreamCreate (capture stream) failed");
-  }
-  // The weight-gradient branches may run on a side stream (IMPALA_SIDE_STREAM=1).  Measured on
-  // MI355X the kernels do not overlap usefully and the fork / join costs more than it hides
-  // (DESIGN.md §7), so one stream is the default.
-  const char* side = std::getenv("IMPALA_SIDE_STREAM");
-  if (!side || side[0] != '1') {
-    h->use_side = false;
-  } else if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess) {
-    h->use_side = false;
-    h->side = nullptr;
-  } else {
-    for (int i = 0; i < 4; ++i)
-      if (hipEventCreateWithFlags(&h->ev_fork[i], hipEventDisableTiming) != hipSuccess)
-        h->use_side = false;
-    if (hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess)
-      h->use_side = false;
   }
   {
     RedArgs& ra = h->red;
@@ -1077,18 +848,15 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
     add(h->s_w3, h->sp3.S, OC3 * K3, RK_CONV3, (long long)h->cn.w3);
     add(h->s_b3, h->sp3.S, OC3, RK_ID, (long long)h->cn.b3);
     add(h->s_ln, h->n_ln_wg, 2 * FLAT, RK_LN, (long long)h->cn.lng);
-    // (direct FC: empty segments, so the segment indices stay fixed)
-    add(h->s_fc, h->spfc.S, h->fc_direct ? 0 : HID * FLAT, RK_FC, (long long)h->cn.wfc);
-    add(h->s_bfc, h->spfc.S, h->fc_direct ? 0 : HID, RK_ID, (long long)h->cn.bfc);
+    add(h->s_fc, h->spfc.S, HID * FLAT, RK_FC, (long long)h->cn.wfc);
+    add(h->s_bfc, h->spfc.S, HID, RK_ID, (long long)h->cn.bfc);
     add(h->s_h, h->sph.S, HEADS * HID, RK_HEADS_W, 0);
     add(h->s_bh, h->sph.S, HEADS, RK_HEADS_B, 0);
     h->n_red_wg = ra.wg_start[ns];
-    h->n_norm_part = h->n_red_wg + (h->fc_direct ? h->n_fc_wg : 0);
     if (ns != RS_END) {
       impala_destroy(h);
       return fail(IMPALA_E_STATE, "reduce segment table out of sync");
     }
-    ra.nseg = ns;
     ra.cn = h->cn;
     ra.sumsq_part = h->sumsq_part;
     ra.loss_part = h->loss_part;
@@ -1102,19 +870,6 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
     ra.lr = dec(cfg->lr); ra.b1 = dec(cfg->adam_beta1); ra.b2 = dec(cfg->adam_beta2);
     ra.adam_sc = h->adam_sc;
   }
-  // fused slab reduction + clip + Adam (reduce_adam_kernel, IMPALA_FUSED_UPDATE=1): world_size
-  // 1, the single-stream end-of-backward reduction, and every reduction unit on a resident
-  // workgroup.  Opt-in: bitwise equal to reduce_grads + adam but slower on MI355X (20 vs
-  // 10.3 + 6.0 us at B=64 T=20 bf16; the all-gather of the norm partials alone takes ~4.5 us
-  // after the last unit publishes, more than the kernel boundary it removes: DESIGN.md §7)
-  h->fsync.n_units = h->n_red_wg;
-  h->fsync.n_part = h->n_norm_part;
-  h->fsync.part = h->sumsq_part;
-  if (const char* e = std::getenv("IMPALA_FUSED_UPDATE")) h->fused_update = e[0] == '1';
-  // (it updates exactly the elements it reduces, so the direct FC gradient is off with it)
-  if (h->fused_update && h->fc_direct) h->fused_update = false;
-  if (cfg->world_size != 1 || h->red_mode != 0 || h->n_red_wg > 3 * FU_MAX_UNITS * h->n_cu)
-    h->fused_update = false;
   *out = h;
   return 0;
 }
@@ -1187,13 +942,6 @@ int impala_destroy(impala_learner* h) {
     delete[] t.ev;
   }
   if (h->cap) (void)hipStreamDestroy(h->cap);
-  for (int i = 0; i < 4; ++i)
-    if (h->ev_fork[i]) (void)hipEventDestroy(h->ev_fork[i]);
-  if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  if (h->side) {
-    (void)hipStreamSynchronize(h->side);
-    (void)hipStreamDestroy(h->side);
-  }
   dp_release(h);
   delete h->stager;  // (free_ring above already waited for its jobs)
   delete h->pool;
@@ -1228,8 +976,6 @@ int impala_set_metrics(impala_learner* h, float* metrics) {
 int impala_set_metrics_host(impala_learner* h, float* host) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
   if (host) {
-    if (h->fused_update)  // the A/B fused reduce + Adam launch does not write it
-      return fail(IMPALA_E_UNSUPPORTED, "impala_set_metrics_host: not with IMPALA_FUSED_UPDATE");
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, host) != hipSuccess || at.type != hipMemoryTypeHost) {
       (void)hipGetLastError();
@@ -1308,17 +1054,19 @@ int impala_act(impala_learner* h, const uint8_t* obs, int n, const uint8_t* dete
 extern "C++" {
 namespace {
 int enqueue_grads(impala_learner* h, const impala_batch* b, hipStream_t st, int part = -1) {
-  if (part == -1 || part == 0 || part == 2 || part == 5) {  // (parts 1, 3, 4, 6 continue a backward)
+  const BwdPart* bp = bwd_part(part);
+  if (!bp) return fail(IMPALA_E_INVALID, "unknown backward part");
+  if (bp->first == BS_HEAD_FC) {  // (the other parts continue a backward)
     int r = h->bf16 ? launch_forward<__bf16>(h, b->obs, h->N, st, false)
                     : launch_forward<float>(h, b->obs, h->N, st, false);
     if (r) return r;
   }
-  return h->bf16 ? launch_backward<__bf16>(h, b, st, part) : launch_backward<float>(h, b, st, part);
+  return h->bf16 ? launch_backward<__bf16>(h, b, st, bp) : launch_backward<float>(h, b, st, bp);
 }
 
 int enqueue_update(impala_learner* h, hipStream_t st) {
   if (h->cfg.world_size > 1) {
-    if (int r = klaunch(h, K_SUMSQ, "sumsq", sumsq_kernel, dim3(h->n_norm_part), dim3(256), st,
+    if (int r = klaunch(h, K_SUMSQ, "sumsq", sumsq_kernel, dim3(h->n_red_wg), dim3(256), st,
                         (const float*)h->grads, (size_t)h->cn.total, h->sumsq_part))
       return r;
   }
@@ -1366,7 +1114,7 @@ int run_graphed(impala_learner* h, int kind, const impala_batch* b, hipStream_t 
   CK(hipGraphLaunch(exec, st));
   return 0;
 }
-enum { G_GRADS = 0, G_UPDATE = 1, G_STEP = 2, G_GRADS0 = 3 };  // G_GRADS0 + part (0..4)
+enum { G_GRADS = 0, G_UPDATE = 1, G_STEP = 2, G_GRADS0 = 3 };  // G_GRADS0 + part (0..4, 6)
 }  // namespace
 }  // extern "C++"
 
@@ -1508,12 +1256,6 @@ int impala_train_step(impala_learner* h, const impala_batch* b, void* stream) {
   if (int r = check_batch(b, h->cfg.algo == IMPALA_ALGO_PPO)) return r;
   CK(hipSetDevice(h->device));
   return run_graphed(h, G_STEP, b, (hipStream_t)stream, [&](hipStream_t s) {
-#if IMPALA_AB
-    if (h->fused_update) {
-      if (int r = enqueue_grads(h, b, s, 5)) return r;
-      return h->bf16 ? launch_reduce_adam<__bf16>(h, s) : launch_reduce_adam<float>(h, s);
-    }
-#endif
     if (int r = enqueue_grads(h, b, s)) return r;
     return enqueue_update(h, s);
   });
@@ -1526,8 +1268,7 @@ int impala_train_step_rows(impala_learner* h, const impala_batch* ring, const in
     return fail(IMPALA_E_UNSUPPORTED, "impala_train_step_rows: IMPALA handles of world_size 1");
   // only the default launches read the batch through the row map: the fused forward
   // (conv12_fwd_s2d), the fused head and the fused per-frame backward (lnc3_conv12_bwd)
-  const bool default_path = h->fwd_fused && h->lc12 && h->lnc3_fused && h->ln_fpw == h->c1_fpw &&
-                            !h->use_side && h->red_mode == 0 && !h->fused_update && !h->fwd_chain;
+  const bool default_path = h->fwd_fused && h->lc12 && h->lnc3_fused && h->ln_fpw == h->c1_fpw;
   if (!default_path)
     return fail(IMPALA_E_UNSUPPORTED, "impala_train_step_rows: not on the default kernel path");
   if (n != h->cfg.batch_size || n > kObsRowsMax)
@@ -2124,8 +1865,6 @@ int impala_timer_read_kernel(impala_learner* h, int kernel_id, float* total_ms, 
 int impala_step_clock(impala_learner* h, unsigned long long* stamps, int n) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
   if (n < 0 || (n > 0 && !stamps)) return fail(IMPALA_E_INVALID, "bad step clock buffer / count");
-  if (n > 0 && h->fwd_chain)  // the A/B forward-chain launch takes no stamp
-    return fail(IMPALA_E_UNSUPPORTED, "the step clock does not stamp the IMPALA_FWD_CHAIN forward");
   h->clock_buf = n > 0 ? stamps : nullptr;
   h->clock_n = n;
   h->clock_i = 0;

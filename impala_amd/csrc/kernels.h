@@ -597,7 +597,6 @@ struct RedSeg {
 struct RedArgs {
   RedSeg seg[MAX_RED_SEGS];
   int wg_start[MAX_RED_SEGS + 1];  // first workgroup of each segment
-  int nseg;
   float* grads;
   Canon cn;
   float* sumsq_part;
@@ -734,36 +733,6 @@ DEV float reduce_unit(const RedArgs& a, int wg, f32x4* part, f32x4& acc, long lo
   return reduce_unit_finish(a, r, part, acc, ci);
 }
 
-// Reduction units run by extra blocks of another launch (one unit per 256-thread quarter of a
-// 256*Q-thread block; u < 0: the quarter has none but still takes part in the barriers).  Same
-// arithmetic and sum-of-squares slot (the unit's global index) as reduce_grads_kernel.
-template <int Q>
-DEV void reduce_units_quarters(const RedArgs& a, int u, f32x4* part_all, float* red_all) {
-  const int q = (int)threadIdx.x >> 8, tid = (int)threadIdx.x & 255;
-  f32x4* part = part_all + q * 256;
-  float* red = red_all + q * 4;
-  RedUnit r{};
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (u >= 0) {
-    r = reduce_unit_at(a, u, tid);
-    acc = reduce_unit_sum(a, r);
-  }
-  part[tid] = acc;
-  __syncthreads();
-  long long ci[4];
-  float sq = 0.f;
-  if (u >= 0) {
-    sq = reduce_unit_finish(a, r, part, acc, ci);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (ci[i] >= 0) a.grads[ci[i]] = acc[i];
-  }
-  sq = wave_sum(sq);
-  if ((tid & 63) == 0) red[tid >> 6] = sq;
-  __syncthreads();
-  if (u >= 0 && tid == 0) a.sumsq_part[u] = red[0] + red[1] + red[2] + red[3];
-}
-
 // Each segment is processed by workgroups of 256 threads = (256/SG) float4 columns x SG
 // split groups; split group g sums splits g, g+SG, ... and the SG partials are combined in
 // LDS in a fixed order (deterministic for a given SG).  wg_start[] holds each segment's
@@ -833,12 +802,11 @@ struct AdamArgs {
 };
 
 // torch.optim.Adam's update of one element (lerp form of exp_avg, sqrt(v) / sqrt(bc2) + eps),
-// on the clipped gradient g * gscale; shared by the unfused and the fused update kernels so both
-// compile the same arithmetic
+// on the clipped gradient g * gscale
 DEV void adam_elem(const AdamArgs& a, float gscale, float step_size, float bc2s, float& g,
                    float& m, float& v, float& p) {
   // every multiply and add rounded on its own, as written: no FMA contraction, whose choice
-  // depends on the surrounding code and would make the two kernels differ in the last bit
+  // depends on the surrounding code
 #pragma clang fp contract(off)
   const float w1 = (float)(1.0 - a.b1), b2f = (float)a.b2, w2 = (float)(1.0 - a.b2);
   g = g * gscale;
@@ -958,169 +926,6 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
     for (int k = 0; k < n; ++k) write_shadow<T>(a.sp, a.cn, a.sh, i0 + k, p[k]);
   }
 }
-
-// =========================================================================================
-// Fused slab reduction + clip + Adam (world_size 1): one launch instead of reduce_grads and
-// adam.  The workgroups run the reduction units of reduce_grads_kernel (unit u on workgroup
-// u % grid, at most FU_MAX_UNITS each), keep each thread's reduced values and canonical indices in
-// registers and issue that element's parameter / moment loads at once.  Each unit's sum of
-// squares is published as one 8-byte {epoch, value} granule (an agent-scope relaxed atomic store:
-// the data is its own flag, MI355X_MICROARCH.md "R2"); every workgroup then sweeps all granules
-// until each carries this launch's epoch, sums them in adam_kernel's order (same norm bits), and
-// updates its own elements -- no grid barrier and no other cross-workgroup payload.  Every
-// workgroup must be resident at once: the grid is the CU count (one 256-thread workgroup per
-// CU), and the sweep is bounded (a timeout sets `fault` and a NaN grad_norm instead of hanging).
-// epoch = *epoch_ctr + 1 (never 0), read by every workgroup before it publishes; workgroup 0
-// stores it back after its sweep has seen every granule, i.e. after every read.  The Adam step
-// counter is handled the same way.  Bitwise equal to reduce_grads + adam (tests).
-// =========================================================================================
-constexpr int FU_MAX_UNITS = 1;  // units per workgroup (the grid is the unit count)
-struct FusedSync {
-  unsigned long long* gran;  // [n_units] {epoch << 32 | float bits}
-  unsigned* epoch_ctr;
-  unsigned* fault;
-  int n_units;
-  int n_part;          // clip-norm partials: the n_units granules, then part[n_units, n_part)
-  const float* part;   // partials written by earlier launches (direct-mode weight gradients)
-};
-
-#if IMPALA_AB  // reduce_adam_kernel: measured slower, A/B builds only
-template <typename T>
-__global__ __launch_bounds__(256) void reduce_adam_kernel(const RedArgs a, const AdamArgs aa,
-                                                          const FusedSync fs) {
-  __shared__ f32x4 part[256];
-  __shared__ float red[4];
-  __shared__ unsigned s_epoch;
-  __shared__ long long s_step;
-  // the epoch counter and the step are read first but only waited for after the reduction
-  unsigned e_ld = 0u;
-  unsigned long long st_ld = 0ull;
-  if (threadIdx.x == 0) {
-    e_ld = __hip_atomic_load(fs.epoch_ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    st_ld = __hip_atomic_load(reinterpret_cast<unsigned long long*>(a.step), __ATOMIC_RELAXED,
-                              __HIP_MEMORY_SCOPE_AGENT);
-  }
-  float g[FU_MAX_UNITS][4], m[FU_MAX_UNITS][4], v[FU_MAX_UNITS][4], p[FU_MAX_UNITS][4];
-  long long ci[FU_MAX_UNITS][4];
-  // ---- reduction units; the Adam operands of each element are loaded beside its slabs ----
-#pragma unroll
-  for (int j = 0; j < FU_MAX_UNITS; ++j) {
-    const int u = (int)blockIdx.x + j * (int)gridDim.x;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ci[j][i] = -1;
-    if (u >= fs.n_units) continue;  // uniform over the workgroup
-    {  // this thread's canonical indices (reduce_unit's column mapping) -> p, m, v loads now
-      int s = 0;
-      while (u >= a.wg_start[s + 1]) ++s;
-      const RedSeg& sg = a.seg[s];
-      const int cols = 256 / sg.sg, col = threadIdx.x % cols, grp = threadIdx.x / cols;
-      const int v4 = (u - a.wg_start[s]) * cols + col;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const long long c = grp == 0 && v4 * 4 < sg.count ? canon_index(a, sg, v4 * 4 + i) : -1;
-        const long long cc = c >= 0 ? c : 0;  // clamped address, value dropped later
-        p[j][i] = aa.params[cc];
-        m[j][i] = aa.m[cc];
-        v[j][i] = aa.v[cc];
-      }
-    }
-    f32x4 acc;
-    float sq = reduce_unit(a, u, part, acc, ci[j]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) g[j][i] = acc[i];
-    if (j == 0 && threadIdx.x == 0) {
-      s_epoch = e_ld + 1u == 0u ? 1u : e_ld + 1u;
-      s_step = (long long)st_ld;
-    }
-    sq = wave_sum(sq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float part_sq = red[0] + red[1] + red[2] + red[3];
-      __hip_atomic_store(fs.gran + u,
-                         ((unsigned long long)s_epoch << 32) | (unsigned long long)__float_as_uint(part_sq),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();  // part / red are reused by the next unit
-  }
-  const unsigned epoch = s_epoch;
-  const int64_t t = (int64_t)s_step + 1;
-  if (blockIdx.x == 0 && (threadIdx.x >> 6) == 1) {  // wave 1
-    if (a.algo == 1)
-      finalize_ppo_metrics(a.loss_part, a.n_loss_part, a.B * a.T, a.ent_coef, a.metrics, threadIdx.x & 63);
-    else
-      finalize_loss_metrics(a.loss_part, a.n_loss_part, a.B, a.T, a.ent_coef, a.metrics, threadIdx.x & 63);
-  }
-  // step size and bias correction (double pow) by one lane, while the others start sweeping
-  __shared__ float s_sc[2];
-  if (threadIdx.x == 0) adam_scalars(a, t, s_sc[0], s_sc[1]);
-  // ---- sweep the granules: thread q holds partials 4q .. 4q+3 (adam_kernel's float4 q) ----
-  const int nq = (fs.n_part + 3) / 4;
-  float x[4] = {0.f, 0.f, 0.f, 0.f};
-  if ((int)threadIdx.x < nq) {  // partials of earlier launches (no wait needed)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int q = 4 * (int)threadIdx.x + k;
-      if (q >= fs.n_units && q < fs.n_part) x[k] = fs.part[q];
-    }
-  }
-  bool timed_out = false;
-  for (unsigned spins = 0;; ++spins) {
-    bool ok = true;
-    if ((int)threadIdx.x < nq) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int q = 4 * (int)threadIdx.x + k;
-        if (q < fs.n_units) {
-          const unsigned long long w = __hip_atomic_load(fs.gran + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = ok && (unsigned)(w >> 32) == epoch;
-          x[k] = __uint_as_float((unsigned)w);
-        }
-      }
-    }
-    if (__syncthreads_and(ok)) break;
-    if (spins > (1u << 22)) {  // ~0.1 s: a workgroup never ran; give up instead of hanging
-      timed_out = true;
-      break;
-    }
-    __builtin_amdgcn_s_sleep(10);
-  }
-  float sq = 0.f;
-  if ((int)threadIdx.x < nq) sq += (x[0] + x[1]) + (x[2] + x[3]);
-  sq = wave_sum(sq);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-  __syncthreads();
-  float norm = sqrtf(red[0] + red[1] + red[2] + red[3]) * aa.inv_world;
-  if (timed_out) {
-    norm = __builtin_nanf("");
-    if (threadIdx.x == 0) __hip_atomic_store(fs.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  const float coef = fminf(aa.max_norm / (norm + 1e-6f), 1.f);
-  const float step_size = s_sc[0], bc2s = s_sc[1];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    aa.metrics[6] = norm;
-    aa.metrics[7] = (float)t;
-    *a.step = t;
-    a.adam_sc[0] = step_size;
-    a.adam_sc[1] = bc2s;
-    __hip_atomic_store(fs.epoch_ctr, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  const float gscale = aa.inv_world * coef;
-#pragma unroll
-  for (int j = 0; j < FU_MAX_UNITS; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const long long c = ci[j][i];
-      if (c < 0) continue;
-      adam_elem(aa, gscale, step_size, bc2s, g[j][i], m[j][i], v[j][i], p[j][i]);
-      aa.grads[c] = g[j][i];
-      aa.m[c] = m[j][i];
-      aa.v[c] = v[j][i];
-      aa.params[c] = p[j][i];
-      write_shadow<T>(aa.sp, aa.cn, aa.sh, (size_t)c, p[j][i]);
-    }
-}
-#endif  // IMPALA_AB
 
 // heads output [n][16] -> logits [n][A], values [n]
 __global__ void split_heads_kernel(const float* __restrict__ heads, int n, int A,
@@ -1288,36 +1093,3 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
       reinterpret_cast<float*>(d)[v] = reinterpret_cast<const float*>(s)[v];
   }
 }
-
-#if IMPALA_AB  // wgrad23r_kernel: measured slower, A/B builds only
-// conv3 + conv2 weight gradients (wgrad23_kernel's blocks) plus the reduction units of the
-// slabs that are already final when they start -- conv1 / LayerNorm (the per-frame backward)
-// and FC / heads -- as extra blocks, one unit per 256-thread quarter: the conv weight
-// gradients' second round of blocks leaves CUs free, and the final reduce_grads launch keeps
-// only the conv2 / conv3 units.  Units are the global indices [u0, u0 + n0) then [u1, u1 + n1).
-template <typename T, int G>
-__global__ __launch_bounds__(256 * G) void wgrad23r_kernel(
-    const Conv3Wgrad<T> o3, float* __restrict__ s_w3, float* __restrict__ s_b3, int mps3, int g3x,
-    int g3z, const Conv2Wgrad<T> o2, float* __restrict__ s_w2, float* __restrict__ s_b2, int mps2,
-    int g2x, int g2z, const RedArgs ra, int u0, int n0, int u1, int n1) {
-  constexpr int SM = Wg23Cfg<T, G>::SMEM * (int)sizeof(T);
-  constexpr int SR = G * 256 * 16 + G * 4 * 4;
-  __shared__ __attribute__((aligned(16))) char lds[SM > SR ? SM : SR];
-  // the reduction blocks first: they are short, and the weight-gradient blocks fill the CUs
-  // they free
-  const int nr = (n0 + n1 + G - 1) / G;
-  const int n3 = g3x * g3z, n2 = g2x * g2z, b = (int)blockIdx.x - nr;
-  if (b < 0) {
-    const int i = (int)blockIdx.x * G + ((int)threadIdx.x >> 8);
-    const int u = i < n0 ? u0 + i : (i - n0 < n1 ? u1 + i - n0 : -1);
-    reduce_units_quarters<G>(ra, u, reinterpret_cast<f32x4*>(lds),
-                             reinterpret_cast<float*>(lds + G * 256 * 16));
-  } else if (b < n3) {
-    gemm_wg_body<T, 64, 64, 2, 2, 32, G, Conv3Wgrad<T>>(o3, s_w3, s_b3, mps3, b, g3x, 1, g3z,
-                                                        reinterpret_cast<T*>(lds));
-  } else if (b < n3 + n2) {
-    gemm_wg_body<T, 64, Wg2Tile<T>::BC, Wg2Tile<T>::WR, Wg2Tile<T>::WC, 32, G, Conv2Wgrad<T>>(o2, s_w2, s_b2, mps2, b - n3, g2x, 1, g2z,
-                                                         reinterpret_cast<T*>(lds));
-  }
-}
-#endif  // IMPALA_AB

@@ -100,209 +100,6 @@ template <typename T> struct FcFwd {
   }
 };
 
-// fp32 FC forward as a split-K GEMM with its combine in the same launch.  The 32 x 32 tile
-// kernel (320 workgroups, whole K each) streams 256 KB per workgroup for 1 M MACs and leaves
-// 64 CUs with a second tile; here a workgroup owns a 64 (hidden) x 80 (frame) tile over one
-// quarter of K: 144 KB streamed for 1.3 M MACs, and 256 workgroups at B*T = 1280 (one per CU).
-// Wave w holds rows 16w..16w+15 of the tile as 16 float4 A fragments in registers; the tile's
-// 80 frames x 256 k of y sit in LDS.  Each workgroup stores its fp32 partial (20 KB, in the
-// accumulator layout) and takes a ticket on its tile's counter; the one that draws the 4th
-// ticket sums the four partials in split order ((p0 + p1) + p2) + p3 -- whichever arrives
-// last, so the result is deterministic -- and runs FcFwd's bias + GELU epilogue.  Hand-off:
-// cdna_hip_programming.md's split-K recipe (plain slab stores, agent release before the
-// ticket, agent acquire in the reducer).  The counters only ever grow by 4 per tile per launch
-// (zeroed once at create), so no reset is needed.  The 4 splits and the 4 row tiles of a
-// column tile run on one XCD when the tile count allows (speed only, not correctness).
-namespace fcsk {
-constexpr int ROWS = 64, COLS = 80, NS = 4, KS = FLAT / NS, LDB = KS + 4, PART = ROWS * COLS;
-constexpr int NCF = COLS / 16, NKB = KS / 16;
-}  // namespace fcsk
-#if IMPALA_AB  // fc_fwd_splitk_f32 / fc_fwd_wsplit_f32: measured slower, A/B builds only
-// PUB (publish form): 1 = write-through (sc1) slab stores and sc1 slab loads, no fences
-// (the default); 0 = plain stores, agent release before the ticket, agent acquire in the
-// reducer; 2 = measurement knock-out (partials stored, no combine: wrong results).
-DEV void st_sc1(float* p, f32x4 v) {
-  const unsigned long long lo = __builtin_bit_cast(unsigned long long, float2{v[0], v[1]});
-  const unsigned long long hi = __builtin_bit_cast(unsigned long long, float2{v[2], v[3]});
-  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p) + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-DEV f32x4 ld_sc1(const float* p) {
-  auto* q = reinterpret_cast<unsigned long long*>(const_cast<float*>(p));
-  const float2 lo = __builtin_bit_cast(float2, __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  const float2 hi = __builtin_bit_cast(float2, __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  return f32x4{lo.x, lo.y, hi.x, hi.y};
-}
-template <int PUB>
-__global__ __launch_bounds__(256) void fc_fwd_splitk_f32(const FcFwd<float> op, float* __restrict__ slab,
-                                                         unsigned* __restrict__ cnt) {
-  using namespace fcsk;
-  __shared__ __attribute__((aligned(16))) float sb[COLS * LDB + 4];
-  const int nb = (int)gridDim.x, b = (int)blockIdx.x, n_tiles = nb / NS;
-  int tile, s;
-  if (n_tiles % 8 == 0) {
-    const int x = b % 8, l = b / 8;
-    tile = x * (n_tiles / 8) + l / NS;
-    s = l % NS;
-  } else {
-    tile = b / NS;
-    s = b % NS;
-  }
-  constexpr int NRT = HID / ROWS;
-  const int r0 = (tile % NRT) * ROWS, c0 = (tile / NRT) * COLS, k0 = s * KS;
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // A fragments: row r0 + 16w + (lane & 15), k = k0 + 16 kb + 4 (lane >> 4) + e
-  f32x4 a[NKB];
-  const float* ap = op.w + (size_t)(r0 + wave * 16 + (lane & 15)) * FLAT + k0 + 4 * (lane >> 4);
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb) a[kb] = *reinterpret_cast<const f32x4*>(ap + kb * 16);
-  // y tile -> LDS: column (frame) rows of 256 k, padded by 4 floats (conflict-free b128 reads)
-#pragma unroll
-  for (int i = 0; i < COLS / 4; ++i) {
-    const int col = i * 4 + wave, k = lane * 4;
-    const int c = min(c0 + col, op.C - 1);  // frames past C: any valid row, results dropped
-    *reinterpret_cast<f32x4*>(sb + col * LDB + k) =
-        *reinterpret_cast<const f32x4*>(op.y + (size_t)c * YLD + k0 + k);
-  }
-  __syncthreads();
-  f32x4 acc[NCF];
-#pragma unroll
-  for (int cf = 0; cf < NCF; ++cf) acc[cf] = Frag<float>::zero();
-  const float* bp = sb + (lane & 15) * LDB + 4 * (lane >> 4);
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb) {
-    f32x4 bv[NCF];
-#pragma unroll
-    for (int cf = 0; cf < NCF; ++cf) bv[cf] = *reinterpret_cast<const f32x4*>(bp + cf * 16 * LDB + kb * 16);
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int cf = 0; cf < NCF; ++cf) acc[cf] = Frag<float>::mma_e(e, a[kb], bv[cf], acc[cf]);
-  }
-  // publish this split's partial, take a ticket
-  float* tp = slab + (size_t)tile * NS * PART;
-#pragma unroll
-  for (int cf = 0; cf < NCF; ++cf) {
-    float* dst = tp + (size_t)s * PART + ((wave * NCF + cf) * 64 + lane) * 4;
-    if constexpr (PUB == 1) st_sc1(dst, acc[cf]);
-    else *reinterpret_cast<f32x4*>(dst) = acc[cf];
-  }
-  if constexpr (PUB == 2) return;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  int* last = reinterpret_cast<int*>(sb + COLS * LDB);
-  if (tid == 0) {
-    if constexpr (PUB == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const unsigned old = __hip_atomic_fetch_add(cnt + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int is_last = (old % NS) == NS - 1;
-    if (PUB == 0 && is_last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    *last = is_last;
-  }
-  __syncthreads();
-  if (!*last) return;
-  const int o = r0 + wave * 16 + 4 * (lane >> 4);
-  const auto ep = op.epi(o, 0);
-  // every partial load of the tile in flight at once (the own split's too: same bits as acc)
-  f32x4 p[NCF][NS];
-#pragma unroll
-  for (int cf = 0; cf < NCF; ++cf)
-#pragma unroll
-    for (int q = 0; q < NS; ++q) {
-      const float* src = tp + (size_t)q * PART + ((wave * NCF + cf) * 64 + lane) * 4;
-      p[cf][q] = PUB == 1 ? ld_sc1(src) : *reinterpret_cast<const f32x4*>(src);
-    }
-#pragma unroll
-  for (int cf = 0; cf < NCF; ++cf) {
-    f32x4 v = p[cf][0] + p[cf][1];
-#pragma unroll
-    for (int q = 2; q < NS; ++q) v += p[cf][q];
-    const int c = c0 + cf * 16 + (lane & 15);
-    if (c < op.C) {
-      float vv[4] = {v[0], v[1], v[2], v[3]};
-      op.store(o, c, vv, ep);
-    }
-  }
-}
-
-// fp32 FC forward, K split over the 4 waves of a workgroup instead of over workgroups: a
-// workgroup owns 16 hidden x 80 frames over all of K (256 workgroups at B*T = 1280, one per
-// CU, 384 KB streamed each against 2 x 256 KB on the CUs that get two 32 x 32 tiles), wave w
-// takes k in [256 w, 256 w + 256) with its B fragments straight from global (no operand is
-// shared between the waves), and the four 16 x 80 partials meet in LDS, summed in wave order
-// ((w0 + w1) + w2) + w3 before FcFwd's bias + GELU epilogue.
-namespace fcwk {
-constexpr int ROWS = 16, COLS = 80, KW = FLAT / 4, NCF = COLS / 16, NKB = KW / 16, CH = 4;
-}  // namespace fcwk
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void fc_fwd_wsplit_f32(
-    const FcFwd<float> op) {
-  using namespace fcwk;
-  __shared__ __attribute__((aligned(16))) float red[4 * NCF * 64 * 4];
-  constexpr int NRT = HID / ROWS;
-  const int t = xcd_swizzle((int)blockIdx.x, (int)gridDim.x);
-  const int r0 = (t % NRT) * ROWS, c0 = (t / NRT) * COLS;
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, k0 = wave * KW;
-  f32x4 a[NKB];
-  const float* ap = op.w + (size_t)(r0 + (lane & 15)) * FLAT + k0 + 4 * (lane >> 4);
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb) a[kb] = *reinterpret_cast<const f32x4*>(ap + kb * 16);
-  const float* bp[NCF];
-#pragma unroll
-  for (int cf = 0; cf < NCF; ++cf)
-    bp[cf] = op.y + (size_t)min(c0 + cf * 16 + (lane & 15), op.C - 1) * YLD + k0 + 4 * (lane >> 4);
-  f32x4 acc[NCF];
-#pragma unroll
-  for (int cf = 0; cf < NCF; ++cf) acc[cf] = Frag<float>::zero();
-  // B in chunks of CH k-steps, double-buffered: chunk c + 1 in flight under chunk c's MFMAs
-  f32x4 bq[2][CH][NCF];
-#pragma unroll
-  for (int j = 0; j < CH; ++j)
-#pragma unroll
-    for (int cf = 0; cf < NCF; ++cf) bq[0][j][cf] = *reinterpret_cast<const f32x4*>(bp[cf] + j * 16);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int ch = 0; ch < NKB / CH; ++ch) {
-    if (ch + 1 < NKB / CH) {
-#pragma unroll
-      for (int j = 0; j < CH; ++j)
-#pragma unroll
-        for (int cf = 0; cf < NCF; ++cf)
-          bq[(ch + 1) & 1][j][cf] = *reinterpret_cast<const f32x4*>(bp[cf] + ((ch + 1) * CH + j) * 16);
-    }
-    __builtin_amdgcn_sched_barrier(0);  // keep the next chunk's loads ahead of these MFMAs
-#pragma unroll
-    for (int j = 0; j < CH; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int cf = 0; cf < NCF; ++cf)
-          acc[cf] = Frag<float>::mma_e(e, a[ch * CH + j], bq[ch & 1][j][cf], acc[cf]);
-  }
-#pragma unroll
-  for (int cf = 0; cf < NCF; ++cf)
-    *reinterpret_cast<f32x4*>(red + ((wave * NCF + cf) * 64 + lane) * 4) = acc[cf];
-  __syncthreads();
-  for (int i = tid; i < NCF * 64; i += 256) {
-    const int cf = i >> 6, ln = i & 63;
-    const float* q = red + (cf * 64 + ln) * 4;
-    constexpr int WS = NCF * 64 * 4;  // one wave's partial
-    f32x4 v = *reinterpret_cast<const f32x4*>(q) + *reinterpret_cast<const f32x4*>(q + WS);
-    v += *reinterpret_cast<const f32x4*>(q + 2 * WS);
-    v += *reinterpret_cast<const f32x4*>(q + 3 * WS);
-    const int o = r0 + 4 * (ln >> 4), c = c0 + cf * 16 + (ln & 15);
-    if (c < op.C) {
-      float vv[4] = {v[0], v[1], v[2], v[3]};
-      op.store(o, c, vv, op.epi(o, c));
-    }
-  }
-}
-#endif  // IMPALA_AB
-
 // actor ‖ critic heads fused into one 16-row GEMM (models/models.py:69-70, 76).
 template <typename T> struct HeadsFwd {
   static constexpr bool A_KMAJOR = false;
@@ -420,20 +217,6 @@ template <typename T> struct FcWgrad {  // dWfc[o][j] = sum_n dz[n][o] y[n][j]
   DEV int y_coff(int c) const { return c; }
   DEV int y_bytes() const { return M * YLD * (int)sizeof(T); }
   DEV const T* ybase() const { return y; }
-};
-// The FC weight gradient over the whole batch in one split (gemm_wg direct mode): the tile is
-// final, so it is written straight into the canonical gradient (o*1024 + c*16 + p for kernel
-// column j = p*64 + c; the bias into bfc) and the workgroup's sum of squares goes to its own
-// clip-norm partial slot -- no fp32 partial slab and no reduction pass for this layer.
-template <typename T> struct FcWgradDirect : FcWgrad<T> {
-  static constexpr bool DIRECT = true;
-  float* grads;       // canonical gradient buffer
-  long long wcanon;   // canonical offset of wfc (bfc follows at wcanon + HID * FLAT)
-  float* sumsq;       // [workgroups] partial sums of squares
-  DEV long long canon(int o, int j) const {
-    return wcanon + (long long)o * FLAT + (j & 63) * 16 + (j >> 6);
-  }
-  DEV long long bias_canon(int o) const { return wcanon + (long long)HID * FLAT + o; }
 };
 
 template <typename T> struct Conv3Wgrad {  // m = (n, oy, ox) in N*16; c = (kh*3+kw)*64 + ci
@@ -568,67 +351,3 @@ __global__ __launch_bounds__(256 * G) void wgrad23_kernel(const Conv3Wgrad<T> o3
     gemm_wg_body<T, 64, Wg2Tile<T>::BC, Wg2Tile<T>::WR, Wg2Tile<T>::WC, 32, G, Conv2Wgrad<T>>(
         o2, s_w2, s_b2, mps2, (int)blockIdx.x - n3, g2x, 1, g2z, smem);
 }
-
-#if IMPALA_AB  // fwd_chain_kernel: measured slower, A/B builds only
-// The trunk forward and the FC forward in ONE launch (bf16, conv3 tail on): blocks [0, n_conv)
-// run the per-frame conv1 / conv2 / conv3+LayerNorm body and publish a flag each; the FC tile
-// blocks after them (64 hidden units x 32 frames, 8 waves, one tile per block) wait only for
-// the conv blocks that produce their 32 frames of y, then run the FC body.  Hand-off
-// (MI355X_MICROARCH.md, inter-workgroup visibility, R1): the producer stores y write-through
-// (sc1), every storing wave drains, and one lane stores flag = epoch (relaxed, agent); the
-// consumer polls relaxed, acquires at agent scope once, then a barrier, then plain loads.  The FC blocks are dispatched after every
-// conv block, so a waiting block never holds a slot a producer needs; the poll is bounded (a
-// timeout sets *fault and continues).  epoch changes every launch (never 0).
-template <typename T> struct FwdChainCfg {
-  static constexpr int FR = 64, FC = 32, FK = 256, FWR = 4, FWC = 2;  // FC tile, 8 waves
-  static constexpr int SD = gemm_tile_smem<T, FR, FC, FK, FWR, FWC, FcFwd<T>>();
-  static constexpr int SMEM = C12FLds<T>::ELEMS > SD ? C12FLds<T>::ELEMS : SD;
-};
-template <typename T>
-__global__ __launch_bounds__(512) void fwd_chain_kernel(
-    const uint8_t* __restrict__ x, const T* __restrict__ w1, const float* __restrict__ b1,
-    const T* __restrict__ w2, const float* __restrict__ b2, T* __restrict__ act1,
-    uint32_t* __restrict__ mask, T* __restrict__ act2, int N, int fpw, const C3Tail<T> c3,
-    int n_conv, const FcFwd<T> fc, unsigned* __restrict__ flags, unsigned epoch,
-    unsigned* __restrict__ fault) {
-  static_assert(c12f_groups<T>() == 2, "512-thread conv body (bf16)");
-  using C = FwdChainCfg<T>;
-  __shared__ __attribute__((aligned(16))) T smem[C::SMEM];
-  const int b = (int)blockIdx.x;
-  if (b < n_conv) {
-    // y is the only payload the FC blocks read; c3.y_sc1 stores it write-through, so the
-    // publish is: every storing wave drains, a barrier, one lane stores the flag (R1)
-    conv12_fwd_body<T>(x, w1, b1, w2, b2, act1, mask, act2, N, fpw, c3, b, smem);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave
-    __syncthreads();
-    if (threadIdx.x == 0)
-      __hip_atomic_store(flags + b, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
-  // FC tile of this block (gemm_tile_body's tile order: row tile fastest)
-  const int vb = b - n_conv, vg = (int)gridDim.x - n_conv;
-  const int n_rt = HID / C::FR;
-  const int t = xcd_swizzle(vb, vg);
-  const int c0 = (t / n_rt) * C::FC;
-  if (threadIdx.x < 64) {  // wave 0: lane i polls producer p0 + i
-    const int p0 = c0 / fpw, p1 = (min(N, c0 + C::FC) - 1) / fpw;
-    const int p = p0 + (int)threadIdx.x;
-    bool ok = p > p1 ||
-              __hip_atomic_load(flags + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch;
-    for (unsigned spins = 0; !__all(ok); ++spins) {
-      if (spins > (1u << 22)) {  // ~0.1 s: a producer never finished; do not hang the GPU
-        if (threadIdx.x == 0) __hip_atomic_store(fault, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(2);
-      ok = ok || __hip_atomic_load(flags + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch;
-    }
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-  }
-  __syncthreads();
-  gemm_tile_body<T, C::FR, C::FC, C::FK, C::FWR, C::FWC, FcFwd<T>>(fc, n_rt, vb, vg, smem);
-}
-#endif  // IMPALA_AB

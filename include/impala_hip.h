@@ -149,8 +149,7 @@ int impala_set_metrics(impala_learner* h, float* metrics);
  * the IMPALA_NUM_METRICS values there, then sets the 32-bit word host[15] to 1 after a system
  * fence.  A caller that zeroes host[15] before enqueueing the step reads `float(v)` of every
  * metric (agents/distributed_agent.py:29-31) from host memory as soon as it sees the word (or
- * after an event recorded behind the step), with no device-to-host copy enqueued.  Not with the
- * A/B fused update. */
+ * after an event recorded behind the step), with no device-to-host copy enqueued. */
 int impala_set_metrics_host(impala_learner* h, float* host);
 /* Re-derive the kernel-layout weights after the caller changed `params` (load_state_dict). */
 int impala_refresh_weights(impala_learner* h, void* stream);
@@ -249,7 +248,8 @@ int impala_gather_rows_hidx(const void* const* src, void* const* dst, const size
  * enqueued; the forward, the fused head and the per-frame backward read the ring's rows
  * through a row map in their launch arguments.  Bitwise equal to impala_train_step on the
  * gathered batch.  IMPALA_E_UNSUPPORTED when the handle does not run the default fused
- * kernels (A/B knobs), world_size > 1 or PPO: gather, then impala_train_step. */
+ * kernels (an unfuse switch: IMPALA_FWD_FUSED, IMPALA_LNC3_FUSED or IMPALA_LC12 = 0),
+ * world_size > 1 or PPO: gather, then impala_train_step. */
 int impala_train_step_rows(impala_learner* h, const impala_batch* ring, const int64_t* rows, int n,
                            int64_t capacity, void* stream);
 

@@ -319,26 +319,6 @@ def test_step_clock(dtype):
     np.testing.assert_array_equal(flats[0][1], flats[1][1])
 
 
-@pytest.mark.parametrize("var", ["IMPALA_FC_SPLITK", "IMPALA_FWD_CHAIN", "IMPALA_FUSED_UPDATE",
-                                 "IMPALA_EARLY_RED"])
-def test_product_library_refuses_ab_variants(var, monkeypatch):
-    """The measured-slower alternatives are compiled into the A/B library only
-    (tests/test_gpu_ab_variants.py runs them against it): the product library refuses the switch
-    at create, loudly, instead of silently running the default path."""
-    from impala_amd import _lib
-    if _lib.LIB_PATH.endswith("_ab.so"):
-        pytest.skip("the A/B library is loaded")
-    dev = _dev()
-    monkeypatch.setenv(var, "1")
-    with pytest.raises(RuntimeError, match="A/B variant"):
-        _engine(_model(dev, "fp32", seed=0), 8, 20)
-    if var == "IMPALA_FC_SPLITK":  # an fp32-only variant: bf16 handles ignore the switch
-        _engine(_model(dev, "bf16", seed=0), 8, 20).close()
-    else:
-        with pytest.raises(RuntimeError, match="A/B variant"):
-            _engine(_model(dev, "bf16", seed=0), 8, 20)
-
-
 @pytest.mark.parametrize("env,exact", [({"IMPALA_GRAPH": "1"}, True),
                                        ({"IMPALA_FC_DIRECT": "1"}, False),
                                        ({"IMPALA_FC_MERGED": "0"}, True),
@@ -349,9 +329,10 @@ def test_product_library_refuses_ab_variants(var, monkeypatch):
                                        ({"IMPALA_FWD_FUSED": "0"}, True),
                                        ({"IMPALA_LNC3_FUSED": "0"}, False)])
 def test_launch_modes_agree(env, exact, monkeypatch):
-    """hipGraph replay (opt-in), the single-stream schedule and the unfused conv1/conv2 forward
-    give bit-identical steps to the default; the unfused LayerNorm backward sums its per-frame
-    reductions in another order, so it agrees to fp32 rounding (params after 3 Adam steps)."""
+    """hipGraph replay (opt-in), the separate (unmerged) launches and the unfused conv1/conv2
+    forward give bit-identical steps to the default; the unfused LayerNorm backward sums its
+    per-frame reductions in another order, so it agrees to fp32 rounding (params after 3 Adam
+    steps)."""
     dev = _dev()
     batch = [_t(x, dev) for x in ref_cpu.synthetic_batch(8, 20, 15, seed=6)]
 
@@ -383,8 +364,7 @@ def test_launch_modes_agree(env, exact, monkeypatch):
 
 @pytest.mark.parametrize("env", [{"IMPALA_GRAPH": "1"}, {"IMPALA_FC_MERGED": "0"},
                                  {"IMPALA_WG23_MERGED": "0"}, {"IMPALA_C3_TAIL": "0"},
-                                 {"IMPALA_LC12": "0"}, {"IMPALA_SIDE_STREAM": "1"},
-                                 {"IMPALA_FWD_FUSED": "0"}],
+                                 {"IMPALA_LC12": "0"}, {"IMPALA_FWD_FUSED": "0"}],
                          ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()))
 def test_launch_modes_agree_fp32(env, monkeypatch):
     """The fp32 headline path (the reference's arithmetic): every fused / merged launch --
