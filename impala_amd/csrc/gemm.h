@@ -488,10 +488,22 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_tile(const Op op, int n_rti
 // flight in a register ring (the chunk it multiplies was issued PD chunks earlier): the MFMA
 // work per chunk is a few hundred cycles against a ~2 us loaded memory round trip, so the
 // kernel is bound by how many chunk loads are in flight per CU.  All loads are buffer loads
-// issued unconditionally: rows past the split's end and chunks past the group's last one carry
-// an out-of-range offset and read as zero without touching memory (no branch around a load,
-// so the compiler's counted vmcnt waits stay exact).  The groups' accumulators are summed in
-// a fixed order at the end.  Output: fp32 partial slab [split][R][C] (+ per-split bias sums).
+// issued unconditionally (no branch around a load, so the compiler's counted vmcnt waits stay
+// exact), and the bounds are the descriptors', not per-lane selects:
+//   X  its descriptor ends at this split's last row, so rows past the split's end -- the ragged
+//      tail of the last chunk and the chunks that pad the trip count -- read as zero;
+//   Y  needs no bound of its own for those rows: they are multiplied by X's zeros, and they are
+//      either finite activations of the next split or past the Y descriptor (zero).  Chunks
+//      past the group's last one must not cost traffic: their Y descriptor has zero records
+//      (a scalar select on the wave-uniform chunk index).
+// Every staging offset is computed once in the prologue and then advanced per chunk (BM * G
+// rows): X by a constant, Y by the constant Op::y_stride<BM * G>() where the op has one (FC;
+// conv3 when the stride is whole frames), else by the op's per-lane cursor (conv2: deltas chosen
+// by two compares; no division, no 64-bit multiply).  Per chunk that is one add per load (for
+// the cursor about 8 VALU per advance and 5 per further row of the same chunk) beside the
+// MFMAs; DESIGN.md 4.0.3 has the instruction table.
+// The groups' accumulators are summed in a fixed order at the end.  Output: fp32 partial slab
+// [split][R][C] (+ per-split bias sums).
 // The body runs as virtual workgroup `lin` of a gx x gy x gz grid on 256 * G threads, with the
 // LDS passed in (gemm_wg_smem elements).
 // bf16 rows are stored bit-2/3 swapped (wg_row) at a pitch of BR / BC + 16 (conflict-free
@@ -500,7 +512,7 @@ template <class Op, class = void> struct wg_ycur { static constexpr bool value =
 template <class Op> struct wg_ycur<Op, decltype(void(Op::YCUR))> {
   static constexpr bool value = Op::YCUR;
 };
-template <class Op, bool = wg_ycur<Op>::value> struct WgYCur { struct type { int n, p; }; };
+template <class Op, bool = wg_ycur<Op>::value> struct WgYCur { struct type { int off; }; };
 template <class Op> struct WgYCur<Op, true> { typedef typename Op::YCur type; };
 template <typename T> constexpr int wg_pad() { return sizeof(T) == 2 ? 16 : 4; }
 template <typename T, int BR, int BC, int BM, int G>
@@ -526,8 +538,11 @@ DEV void gemm_wg_body(const Op& op, float* __restrict__ slab, float* __restrict_
   // piece of a line per row: the TA's per-line rate, not bytes, bounded the row-per-lane form
   // (24 B/cycle per CU, profiles/r02c).
   constexpr int YV = BC / VEC, NYV = BM * YV, NY = (NYV + 255) / 256;
-  constexpr int OOB = 0x7ffffff0;  // buffer offset past any extent: the load returns zero
-  static_assert(256 % BM == 0, "Y staging");
+  // Y row offset advance per chunk in elements, where the op's is a constant (else its cursor)
+  constexpr int YADV = Op::template y_stride<BM * G>();
+  constexpr bool YC = wg_ycur<Op>::value;
+  static_assert(YADV > 0 || YC, "Y rows advance by a constant per chunk or by the op's cursor");
+  static_assert(256 % BM == 0 && NXV % 256 == 0 && NYV % 256 == 0, "whole staging passes");
   static_assert(WR * WC == 4, "4 waves per group");
   static_assert(TRW >= 1 && TCW >= 1 && BR % 16 == 0 && BC % 16 == 0, "tile");
   static_assert(BM % F::KSTEP == 0, "chunk");
@@ -538,7 +553,12 @@ DEV void gemm_wg_body(const Op& op, float* __restrict__ slab, float* __restrict_
                     (size_t)STAGE * 2 * G * sizeof(T) >= 256 * sizeof(float),
                 "LDS reuse for the group reduction");
   static_assert(STAGE * 2 * G == gemm_wg_smem<T, BR, BC, BM, G>(), "LDS size");
-  const int grp = threadIdx.x >> 8, tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
+  // group and wave are wave-uniform; readfirstlane says so to the compiler, which otherwise
+  // treats anything derived from threadIdx as divergent and puts the per-chunk `active` /
+  // `do_bias` tests on the exec mask (s_and_saveexec / s_cbranch_execz) instead of scalar branches
+  const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
+  const int tid = threadIdx.x & 255, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // work item (column tile fastest) from the XCD-swizzled dispatch id
   const int nwg = gx * gy * gz;
   const int wid = xcd_swizzle(lin, nwg);
@@ -548,65 +568,74 @@ DEV void gemm_wg_body(const Op& op, float* __restrict__ slab, float* __restrict_
   const int m_end = min(op.M, m_beg + m_per_split);
   const int wr = wave / WC, wc = wave % WC;
   const bool do_bias = slab_bias != nullptr && bx == 0;
+  // X ends at this split's last row: the hardware range check zero-fills every row past it
   const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(op.x), 0, op.M * op.x_ld * (int)sizeof(T), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(op.ybase()), 0, op.y_bytes(), 0x00020000);
+      const_cast<T*>(op.x), 0, m_end * op.x_ld * (int)sizeof(T), 0x00020000);
+  const int y_bytes = op.y_bytes();
   f32x4 acc[TRW][TCW];
 #pragma unroll
   for (int i = 0; i < TRW; ++i)
 #pragma unroll
     for (int j = 0; j < TCW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   float bias_acc = 0.f;
-  // per-thread constant parts of the staging addresses (bytes)
-  int xcol[NX], ycol[NY];
+  // per-thread staging offsets (bytes) of this group's chunk 0, computed once; fetch() is called
+  // with it = 0, 1, 2, ... in order and advances them by one chunk (BM * G rows) per call.
+  // The first row of a thread can lie past M (short splits): X then starts out of its
+  // descriptor's range; y_roff / ycur of such a row give an offset past Y's extent.
+  int xoff[NX];
+  const int x_adv = BM * G * op.x_ld * (int)sizeof(T);
 #pragma unroll
   for (int i = 0; i < NX; ++i) {
-    const int e = min(tid + i * 256, NXV - 1);
-    xcol[i] = (r0 + (e % (BR / VEC)) * VEC) * (int)sizeof(T);
+    const int e = tid + i * 256;
+    xoff[i] = ((m_beg + grp * BM + e / (BR / VEC)) * op.x_ld + r0 + (e % (BR / VEC)) * VEC) * (int)sizeof(T);
   }
+  // Y: a constant-stride op keeps one running offset per load; a cursor op one cursor per
+  // thread, on the row of its load 0 -- load i stages the row i * (256 / YV) further down the
+  // same column, at the cursor's offset plus ycur_peek(i * (256 / YV)) (no state of its own)
+  constexpr int NCUR = YADV > 0 ? NY : 1;
+  static_assert(YADV > 0 || 256 % YV == 0, "a thread's staging rows share one column");
+  typename WgYCur<Op>::type ycur[NCUR];
 #pragma unroll
-  for (int i = 0; i < NY; ++i) ycol[i] = op.y_coff(c0 + ((tid + i * 256) % YV) * VEC) * (int)sizeof(T);
+  for (int i = 0; i < NCUR; ++i) {
+    const int v = tid + i * 256, m = m_beg + grp * BM + v / YV, c = c0 + (v % YV) * VEC;
+    if constexpr (YADV > 0)
+      ycur[i].off = (op.y_roff(m) + op.y_coff(c)) * (int)sizeof(T);
+    else
+      ycur[i] = op.ycur(m, c);
+  }
   V rx[PD][NX], ry[PD][NY];
-  // YCUR ops: the Y rows this thread stages, as cursors advanced by one chunk (BM * G rows) per
-  // fetch -- fetch(d, it) is called with it = 0, 1, 2, ... in order -- instead of y_roff's
-  // divisions per load (which the compiler put behind a branch each: 4 of them per chunk)
-  constexpr bool YC = wg_ycur<Op>::value;
-  typename WgYCur<Op>::type ycur[YC ? NY : 1];
-  int ym[YC ? NY : 1];
-  if constexpr (YC) {
-#pragma unroll
-    for (int i = 0; i < NY; ++i) {
-      ym[i] = m_beg + grp * BM + min(tid + i * 256, NYV - 1) / YV;
-      ycur[i] = op.ycur(ym[i]);
-    }
-  }
-  // chunk `it` of this group -> ring slot d.  Offsets are computed for a clamped row and
-  // replaced by OOB with a select afterwards (unsigned: OOB + a column offset stays out of
-  // range), so no load sits behind a branch.
+  // chunk `it` of this group -> ring slot d
   auto fetch = [&](int d, int it) {
-    const int m0 = m_beg + (it * G + grp) * BM;
+    // a chunk past the group's last one (the prologue of a short split, the PD padding): zero
+    // records for Y, so it returns zeros without traffic; X is past its descriptor by itself
+    const bool live = m_beg + (it * G + grp) * BM < m_end;
+    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<T*>(op.ybase()), 0, live ? y_bytes : 0, 0x00020000);
+    // (the empty asm pins each running offset in its register: without it the compiler folds
+    // the ring's offsets into shared induction variables and re-derives every address with an
+    // add of its own, two VALU per load instead of one)
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
-      const int m = m0 + (tid + i * 256) / (BR / VEC);
-      const uint32_t off = (uint32_t)(min(m, m_end - 1) * op.x_ld * (int)sizeof(T) + xcol[i]);
-      rx[d][i] = __builtin_bit_cast(
-          V, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)(m < m_end ? off : (uint32_t)OOB), 0, 0));
+      rx[d][i] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rs_x, xoff[i], 0, 0));
+      xoff[i] += x_adv;
+      asm volatile("" : "+v"(xoff[i]));
     }
 #pragma unroll
     for (int i = 0; i < NY; ++i) {
-      uint32_t yr;
-      if constexpr (YC) {
-        // rows past the split's end read as zero (OOB), whatever the cursor's offset
-        const uint32_t o = (uint32_t)(op.ycur_off(ycur[i]) * (int)sizeof(T));
-        yr = ym[i] < m_end ? o : (uint32_t)OOB;
-        ym[i] += BM * G;
+      int yo;
+      if constexpr (YADV > 0)
+        yo = ycur[i].off;
+      else
+        yo = i == 0 ? ycur[0].off : ycur[0].off + op.ycur_peek(ycur[0], i * (256 / YV));
+      ry[d][i] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rs_y, yo, 0, 0));
+    }
+#pragma unroll
+    for (int i = 0; i < NCUR; ++i) {
+      if constexpr (YADV > 0)
+        ycur[i].off += YADV * (int)sizeof(T);
+      else
         op.template ycur_adv<BM * G>(ycur[i]);
-      } else {
-        const int m = m0 + min(tid + i * 256, NYV - 1) / YV;
-        yr = m < m_end ? (uint32_t)(op.y_roff(min(m, m_end - 1)) * (int)sizeof(T)) : (uint32_t)OOB;
-      }
-      ry[d][i] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rs_y, (int)(yr + (uint32_t)ycol[i]), 0, 0));
+      asm volatile("" : "+v"(ycur[i].off));
     }
   };
   auto stash = [&](int d, T* Xs) {
@@ -635,9 +664,10 @@ DEV void gemm_wg_body(const Op& op, float* __restrict__ slab, float* __restrict_
     for (int d = 0; d < PD; ++d) {
       const int it = it0 + d;
       // no early exit: the trip count is padded to a multiple of PD and chunks past n_it are
-      // all-OOB (zero, no memory traffic, MFMAs skipped).  An exit from the middle of the
-      // unrolled ring is funnelled through the loop latch by the CFG structurizer, which merges
-      // a rotated ring state into the loop header and forces vmcnt(0) at every stash.
+      // all out of range (zero, no memory traffic, MFMAs skipped).  An exit from the middle of
+      // the unrolled ring is funnelled through the loop latch by the CFG structurizer, which
+      // merges a rotated ring state into the loop header and forces vmcnt(0) at every stash.
+      // `active` is wave-uniform (grp is): a scalar branch around the MFMAs, no exec masking.
       const int m0 = m_beg + (it * G + grp) * BM;
       const bool active = m0 < m_end;
       T* Xs = smem + (grp * 2 + (it & 1)) * STAGE;

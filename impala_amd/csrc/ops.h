@@ -217,6 +217,9 @@ template <typename T> struct FcWgrad {  // dWfc[o][j] = sum_n dz[n][o] y[n][j]
   DEV int y_coff(int c) const { return c; }
   DEV int y_bytes() const { return M * YLD * (int)sizeof(T); }
   DEV const T* ybase() const { return y; }
+  // gemm_wg_body: elements the Y row offset advances for a stride of D rows, where that is a
+  // constant (> 0); 0 where it is not (the op then has a row cursor, YCUR)
+  template <int D> static constexpr int y_stride() { return D * YLD; }
 };
 
 template <typename T> struct Conv3Wgrad {  // m = (n, oy, ox) in N*16; c = (kh*3+kw)*64 + ci
@@ -236,19 +239,12 @@ template <typename T> struct Conv3Wgrad {  // m = (n, oy, ox) in N*16; c = (kh*3
   }
   DEV int y_bytes() const { return (M / P3) * (H2 * H2 * OC2) * (int)sizeof(T); }
   DEV const T* ybase() const { return in; }
-  // row cursor (gemm_wg_body YCUR): (frame, pixel) of row m, advanced by a chunk stride without
-  // the divisions of y_roff (which the compiler also put behind a branch per staging load)
-  static constexpr bool YCUR = true;
-  struct YCur { int n, p; };
-  DEV YCur ycur(int m) const { const int n = m / P3; return YCur{n, m - n * P3}; }
-  template <int D> DEV void ycur_adv(YCur& c) const {
-    c.p += D % P3;
-    c.n += D / P3;
-    if (c.p >= P3) { c.p -= P3; c.n += 1; }
-  }
-  DEV int ycur_off(const YCur& c) const {
-    const int oy = c.p / H3, ox = c.p - oy * H3;
-    return ((c.n * H2 + oy) * H2 + ox) * OC2;
+  // a stride of whole frames keeps the pixel and moves the frame: the row offset advances by a
+  // constant wherever the row starts (the chunk strides in use, 32 and 64 rows, are 2 and 4
+  // frames), so y_roff's divisions run once per thread, in the prologue
+  template <int D> static constexpr int y_stride() {
+    static_assert(D % P3 == 0, "conv3 weight gradient: the chunk stride must be whole frames");
+    return (D / P3) * (H2 * H2 * OC2);
   }
 };
 template <typename T> struct Conv2Wgrad {  // m = (n, oy, ox) in N*36; c = (kh*4+kw)*32 + ci
@@ -268,17 +264,36 @@ template <typename T> struct Conv2Wgrad {  // m = (n, oy, ox) in N*36; c = (kh*4
   }
   DEV int y_bytes() const { return (M / P2) * (H1 * H1 * OC1) * (int)sizeof(T); }
   DEV const T* ybase() const { return in; }
-  static constexpr bool YCUR = true;  // see Conv3Wgrad
-  struct YCur { int n, p; };
-  DEV YCur ycur(int m) const { const int n = m / P2; return YCur{n, m - n * P2}; }
-  template <int D> DEV void ycur_adv(YCur& c) const {
-    c.p += D % P2;
-    c.n += D / P2;
-    if (c.p >= P2) { c.p -= P2; c.n += 1; }
+  // 36 pixels per frame: no chunk stride is whole frames, so each staged row keeps a cursor
+  // (gemm_wg_body YCUR): the running byte offset (column included) with the pixel index p and
+  // its column ox.  A stride of D = (dn, dy, dx) in (frame, row, column) adds the constant
+  // offset of (dn, dy, dx) plus one correction where ox wraps (a carry into the row) and one
+  // where p wraps (a carry into the frame): p + D % 36 >= 36 exactly when the row carries,
+  // whatever the column did.  Two compares and selects per advance; y_roff's divisions run
+  // once per thread, in ycur().  ycur_peek gives the same delta for a row D further down
+  // without moving the cursor (a thread's other staging rows of the same chunk).
+  template <int D> static constexpr int y_stride() { return 0; }
+  static constexpr bool YCUR = true;
+  struct YCur { int off, p, ox; };
+  DEV YCur ycur(int m, int c) const {
+    const int n = m / P2, p = m - n * P2;
+    return YCur{(y_roff(m) + y_coff(c)) * (int)sizeof(T), p, p % H2};
   }
-  DEV int ycur_off(const YCur& c) const {
-    const int oy = c.p / H2, ox = c.p - oy * H2;
-    return ((c.n * H1 + ST2 * oy) * H1 + ST2 * ox) * OC1;
+  // byte offset of the row D (a constant once inlined) after the cursor's, less the cursor's
+  DEV int ycur_peek(const YCur& c, int D) const {
+    constexpr int ES = (int)sizeof(T);
+    constexpr int RX = ST2 * OC1 * ES, RY = ST2 * H1 * OC1 * ES, FR = H1 * H1 * OC1 * ES;
+    const int dn = D / P2, r = D % P2, dy = r / H2, dx = r % H2;
+    return dn * FR + dy * RY + dx * RX + (c.ox + dx >= H2 ? RY - H2 * RX : 0) +
+           (c.p + r >= P2 ? FR - H2 * RY : 0);
+  }
+  template <int D> DEV void ycur_adv(YCur& c) const {
+    constexpr int r = D % P2, dx = r % H2;
+    c.off += ycur_peek(c, D);
+    c.ox += dx;
+    c.ox -= c.ox >= H2 ? H2 : 0;
+    c.p += r;
+    c.p -= c.p >= P2 ? P2 : 0;
   }
 };
 
@@ -296,6 +311,8 @@ template <typename T> struct Conv2Wgrad {  // m = (n, oy, ox) in N*36; c = (kh*4
 // at one per CU, 19.7; this 16.7)
 // bf16 (G = 2, 8 waves): 64 x 64 dgrad tiles on 2 x 4 waves (320) beside 64 x 128 weight-gradient
 // workgroups (192 at the same 6 splits), 78 KB: 512 workgroups, two per CU (8.4 -> 6.8 us)
+// With the weight-gradient loop's staging offsets advanced instead of recomputed (gemm.h):
+// fp32 17.89 -> 17.49 us, bf16 7.31 -> 7.23 (profiles/wgloop, parent -> this tree)
 constexpr int FCB_DR32 = 64, FCB_DC32 = 80, FCB_DWR32 = 4, FCB_DWC32 = 1;
 constexpr int FCB_WBC32 = 128;
 template <typename T, int G> struct FcBwdCfg {
@@ -330,6 +347,9 @@ __global__ __launch_bounds__(256 * G) void fc_bwd_kernel(const FcWgrad<T> ow, fl
 // conv2 weight-gradient tile of the merged launch: fp32 64 x 64 on 2 x 2 waves -- 512 workgroups
 // of conv3's size (64 splits as before, so the same slab and per-element sums), three per CU
 // beside conv3's 252, instead of 256 64 x 128 workgroups of twice conv3's MFMA work; bf16 64 x 128
+// Per 32-row chunk a wave issues 32 (fp32) MFMAs and, beside them, 16 (conv2) or 4 (conv3) VALU
+// of staging addresses (40 and 44 before the offsets were advanced instead of recomputed):
+// fp32 51.77 -> 47.90 us, bf16 15.04 -> 14.07 (profiles/wgloop, parent -> this tree)
 template <typename T> struct Wg2Tile {
   static constexpr int BC = sizeof(T) == 4 ? 64 : 128, WR = sizeof(T) == 4 ? 2 : 1, WC = 4 / WR;
 };
