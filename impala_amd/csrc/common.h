@@ -52,10 +52,6 @@ template <> struct Frag<float> {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[e], c, 0, 0, 0);
   }
   static DEV vec load(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-  static DEV vec from_u8(uint32_t w) {  // 4 bytes -> 4 floats (raw 0..255)
-    return vec{(float)(w & 255u), (float)((w >> 8) & 255u), (float)((w >> 16) & 255u),
-               (float)(w >> 24)};
-  }
 };
 
 template <> struct Frag<__bf16> {
@@ -74,14 +70,6 @@ template <> struct Frag<__bf16> {
   static constexpr int NE = 1;  // one MFMA per k-step (see Frag<float>::mma_e)
   static DEV f32x4 mma_e(int, const vec& a, const vec& b, f32x4 c) { return mma(a, b, c); }
   static DEV vec load(const __bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
-  static DEV vec from_u8_2(uint32_t lo, uint32_t hi) {  // 8 bytes -> 8 bf16 (exact: <= 255)
-    vec v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (__bf16)(float)((lo >> (8 * i)) & 255u);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[4 + i] = (__bf16)(float)((hi >> (8 * i)) & 255u);
-    return v;
-  }
 };
 
 // An fp32 value split exactly into three bf16 terms x = hi + mid + lo (round-to-nearest 8-bit
@@ -104,7 +92,6 @@ DEV int xcd_swizzle(int bid, int nb) {
 }
 
 template <typename T> DEV T to_t(float x) { return (T)x; }
-template <typename T> DEV float to_f(T x) { return (float)x; }
 
 // store 4 consecutive values (rows r..r+3 of one output column) to a channels-last row
 DEV void store4(float* p, const float v[4]) { *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]}; }
@@ -134,9 +121,6 @@ DEV void load4(const __bf16* p, float v[4]) {
 // lanes end with the bit-identical result (and runs are deterministic). ----
 template <int CTRL> DEV float dppf(float v) {  // lanes without a source read 0
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-template <int CTRL> DEV uint32_t dppu(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
 }
 enum : int { DPP_QP_1032 = 0xB1, DPP_QP_2301 = 0x4E, DPP_ROW_MIRROR = 0x140,
              DPP_ROW_HALF_MIRROR = 0x141, DPP_WAVE_SHL1 = 0x130, DPP_WAVE_SHR1 = 0x138 };
@@ -199,12 +183,6 @@ DEV float row16_sum(float v) {
   v += dppf<DPP_ROW_MIRROR>(v);
   return v;
 }
-DEV float row16_max(float v) {
-  v = fmaxf(v, dppf<DPP_QP_1032>(v));
-  v = fmaxf(v, dppf<DPP_QP_2301>(v));
-  v = fmaxf(v, dppf<DPP_ROW_HALF_MIRROR>(v));
-  return fmaxf(v, dppf<DPP_ROW_MIRROR>(v));
-}
 // over the 4 lanes of each quad (all four get the bit-identical result)
 DEV float quad_sum(float v) {
   v += dppf<DPP_QP_1032>(v);
@@ -234,12 +212,6 @@ DEV float shift_down1(float v) { return dppf<DPP_WAVE_SHL1>(v); }
 DEV float shift_up1(float v) { return dppf<DPP_WAVE_SHR1>(v); }
 
 // exact (erf) GELU, models/models.py:68 nn.GELU() default approximate='none'
-DEV float gelu_f(float z) { return 0.5f * z * (1.f + erff(z * 0.70710678118654752440f)); }
-DEV float gelu_grad(float z) {
-  const float cdf = 0.5f * (1.f + erff(z * 0.70710678118654752440f));
-  const float pdf = 0.39894228040143267794f * expf(-0.5f * z * z);
-  return cdf + z * pdf;
-}
 // GELU and its derivative from one erf (the FC forward epilogue keeps gelu'(z) for the backward)
 DEV void gelu_fwd_grad(float z, float& h, float& g) {
   const float e = erff(z * 0.70710678118654752440f);

@@ -39,7 +39,6 @@ template <> struct L<float> { static constexpr int LDI = 52; };
 namespace c1 {
 template <typename T> struct LB;
 template <> struct LB<__bf16> { static constexpr int LDI = 52, LDX = 36, LD2 = 80; };
-template <> struct LB<float> { static constexpr int LDI = 52, LDX = 36, LD2 = 68; };
 template <typename T> struct LF;
 template <> struct LF<__bf16> { static constexpr int LDI = 48; };
 template <> struct LF<float> { static constexpr int LDI = 52; };
@@ -326,7 +325,7 @@ template <typename T> struct C12FLds {
 // (C12FLds<T>::ELEMS elements)
 // act1's store cache policy: bf16 streams it non-temporally (nt: it is re-read only by the
 // conv2 weight gradient two launches later), forward 22.8 -> 22.0 us, step 0.1035-0.1039 ->
-// 0.1027-0.1031 ms; fp32 unchanged within noise, so it keeps the default (tools/var_specs/ntst.py,
+// 0.1027-0.1031 ms; fp32 unchanged within noise, so it keeps the default (A/B in
 // profiles/r05nt; nt on every activation store made the fp32 forward 60 -> 66 us)
 template <typename T> constexpr int kAct1Cpol = sizeof(T) == 2 ? 2 : 0;
 
@@ -384,7 +383,7 @@ DEV void conv12_fwd_body(const uint8_t* __restrict__ x, const T* __restrict__ w1
   float bb1[2][4], bb2[4];
   // fp32: the conv2 bias of this lane's 4x4x1-block output channel (loaded in the frame loop, it
   // cost a wait for every load in flight there, the next frame's image included: 0.7-1.3k
-  // clocks per frame, tools/var_specs/fwdstash32.py r04v4)
+  // clocks per frame, in-kernel stamps, profiles/r04v)
   const float bb2q = b2[16 * wq + 4 * ((lane >> 2) & 3) + (lane >> 4)];
   {
     const f32x4 u0 = *reinterpret_cast<const f32x4*>(b1 + 4 * (lane >> 4));
@@ -594,7 +593,7 @@ DEV void conv12_fwd_body(const uint8_t* __restrict__ x, const T* __restrict__ w1
       f32x4 accA[2][NI], accB[2][NI];
       // issued here, 4.6k clocks ahead of their use: loaded at the top of the conv2 loop, the
       // first MFMA of every frame waited a whole L2 round trip (forward 60.2 -> 58.8 us,
-      // tools/var_specs/w2early.py r04v7)
+      // A/B r04v7, profiles/r04v)
       if constexpr (!W2REG) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) ar0[d] = F::load(w2row + d * KS);
@@ -874,7 +873,7 @@ constexpr int NCELL = QG * QG;
 // G 4-wave groups per workgroup take alternating frames of the run (G frames in flight per CU
 // on top of the one-frame register prefetch); their partials are summed in a fixed order.
 // (fp32: two 4-wave groups with different roles, see conv12_bwd_body_f32)
-template <typename T> constexpr int c12_groups() { return 2; }
+constexpr int C12_GROUPS = 2;
 
 // fp32 body (conv12_bwd_body_f32) LDS, in 4-byte words, double-buffered per frame where the
 // two groups overlap: the frame's s2d image as BYTES (the raw 0..255 values, converted when
@@ -883,7 +882,7 @@ template <typename T> constexpr int c12_groups() { return 2; }
 // ix = 15 a zero pad) x 2, dY2 rows (36) x 2, one half-Z tile per stride-parity class (2 taps x 32 channels; row 36
 // stays zero: the gather's out-of-range taps read it), the mask words x 2.
 // The Z rows are 64 floats = 16 chunks of 16 B, unpadded; chunk c of row r is stored at chunk
-// c ^ zswz(r) (ZSWZ).  The Z stores write 8 consecutive rows at one chunk per ds_write_b128 lane
+// c ^ zswz(r).  The Z stores write 8 consecutive rows at one chunk per ds_write_b128 lane
 // group (bank = address mod 128 B: zswz(r) mod 8 is a permutation of r mod 8), and a gather
 // read's 16-lane group (ds_read_b128 groups, MI355X_MICROARCH.md §LDS) takes chunks 0..3 of row r,
 // 4..7 of rows r + 1 and r + 2, 0..3 of row r + 3 (+ 8 per tap j2), for any r: bit 3 and bit 2
@@ -891,32 +890,29 @@ template <typename T> constexpr int c12_groups() { return 2; }
 // the 256-byte bank row.  With the round-3 pitch (68 floats) the same reads overlapped by up to
 // 3 chunks (39 % of the backward's LDS cycles were conflict cycles, profiles/r04pmc).
 struct C12B32 {
-  static constexpr bool ZSWZ = true;
-  // group B's conv1 weight gradient split over k (WKS): wave w takes k-blocks 2 w, 2 w + 1 of
-  // all four taps (the dY1 split into bf16 terms done once per value, not once per tap), the
-  // partials summed in wave order at the end; else wave w takes tap w over all eight k-blocks
-  static constexpr bool WKS = true;
-  static constexpr int XP = 20, LDX = c1::LB<float>::LDX;  // image row bytes (X 0..16), dY1 row
-  static constexpr int NROW = 240, LDD = OC2 + 4, DROWS = P2, LDZ = 2 * OC1 + (ZSWZ ? 0 : 4),
-                       ZROWS = P2 + 1;
+  static constexpr int XP = 20, LDX = 36;  // image row bytes (X 0..16), dY1 row
+  static constexpr int NROW = 240, LDD = OC2 + 4, DROWS = P2, LDZ = 2 * OC1, ZROWS = P2 + 1;
   static_assert(2 * OC1 == 64, "Z rows of 16 chunks");
-  __device__ static constexpr int zswz(int r) { return ZSWZ ? ((r & 1) * 12) | ((r >> 1) & 3) : 0; }
+  __device__ static constexpr int zswz(int r) { return ((r & 1) * 12) | ((r >> 1) & 3); }
   static constexpr int IMGW = c1::GRID * c1::CH * XP / 4, DYW = NROW * LDX, D2W = DROWS * LDD;
   static constexpr int IMG = 0, DYT = IMG + 2 * IMGW, D2S = DYT + 2 * DYW;
   static constexpr int Z0 = D2S + 2 * D2W, ZSZ = ZROWS * LDZ, MSK = Z0 + 4 * ZSZ;
   static constexpr int BYTES = (MSK + 2 * c1::NPIX) * 4;
 };
 
-// LDS of the body (bytes): per-group image / dY1 / dY2 tiles, the ReLU mask words, bias sums
-template <typename T> struct C12BLds {
-  static constexpr int VEC = 16 / (int)sizeof(T), LDX = c1::LB<T>::LDX, LD2 = c1::LB<T>::LD2;
-  static constexpr int IMGSZ = c1::GRID * c1::GRID * c1::LB<T>::LDI, DYSZ = c1::NPAD * LDX;
-  static constexpr int G = c12_groups<T>();
-  static constexpr int GSZ = IMGSZ + DYSZ + c12::NCELL * LD2;
-  static constexpr int MSK = (G * GSZ * (int)sizeof(T) + 15) / 16 * 16;
+// LDS of conv12_bwd_body (bytes).  bf16: per-group image / dY1 / dY2 tiles, the ReLU mask words,
+// bias sums; fp32: C12B32
+template <typename T> struct C12BLds;
+template <> struct C12BLds<__bf16> {
+  using L = c1::LB<__bf16>;
+  static constexpr int IMGSZ = c1::GRID * c1::GRID * L::LDI, DYSZ = c1::NPAD * L::LDX;
+  static constexpr int G = C12_GROUPS;
+  static constexpr int GSZ = IMGSZ + DYSZ + c12::NCELL * L::LD2;
+  static constexpr int MSK = (G * GSZ * (int)sizeof(__bf16) + 15) / 16 * 16;
   static constexpr int BRED = MSK + (G * c1::NPIX * 4 + 15) / 16 * 16;
-  static constexpr int BYTES = sizeof(T) == 4 ? C12B32::BYTES : BRED + 4 * G * OC1 * 4;
+  static constexpr int BYTES = BRED + 4 * G * OC1 * 4;
 };
+template <> struct C12BLds<float> { static constexpr int BYTES = C12B32::BYTES; };
 
 // The W2 fragments of stride-parity class `cls` (conv12_bwd_body_f32's group A wave):
 // B[k = oc][n = ci] = W2[oc][kh][kw][ci] for the class's 4 taps, 16-byte loads from the
@@ -999,11 +995,12 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
   float bsum[4] = {0.f, 0.f, 0.f, 0.f};    // A: conv1 bias partials of this lane's 4 channels
   // A: W2 fragments wb[tap j1*2+j2][k-step][ci tile] (c12_load_w2; loaded here if load_w2)
   // ---- group B state ----
-  // B: conv1 weight gradient [tap (WKS) ][oc tile i][ch tile j]
-  constexpr int NTB = L::WKS ? 4 : 1;
-  f32x4 acc[NTB][2][3];
+  // B: conv1 weight gradient [tap][oc tile i][ch tile j], split over k: wave w takes k-blocks
+  // 2 w, 2 w + 1 of all four taps (the dY1 split into bf16 terms done once per value, not once
+  // per tap), the partials summed in wave order at the end
+  f32x4 acc[4][2][3];
 #pragma unroll
-  for (int t = 0; t < NTB; ++t)
+  for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1052,7 +1049,7 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
   // group B's staging split in two for its loop: the loads issued at the top of a step, under
   // its weight-gradient MFMAs, the LDS stores after them (loads followed at once by their stores
   // exposed 1.3-2.7k clocks of load latency per step on the bottleneck group: 72.3 -> 70.0 us,
-  // tools/var_specs/bstage.py r04v8)
+  // A/B r04v8, profiles/r04v)
   struct StRegs {
     uint4 nv[3];
     f32x4 nd2[ND2];
@@ -1108,8 +1105,6 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
   __syncthreads();
   // A: gather items of this lane: channels 4 cg .. 4 cg + 3 of class cells (qy, qx = slot)
   const int cg = lane & 7, slot = lane >> 3;
-  // B: this wave's tap (ty, tx) of the conv1 weight gradient
-  const int ty = wave >> 1, tx = wave & 1;
   // the groups run separate loops with the same barrier count (nF + 1), so that the compiler
   // keeps each group's loop-carried registers (A: the W2 fragments; B: the accumulators) apart
   if (is_a) {
@@ -1260,8 +1255,7 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
       // (image rows 2 kb, 2 kb + 1); lane group g holds pixels 8 g .. 8 g + 7 of it: dY1 rows
       // (clamped to the 240 that exist) and 8 consecutive image bytes (funnel-shifted by tx).
       // The 16 pixels of image row 15 (kb = 7, g >= 2) are padding: their B operand is zero.
-      // WKS: each wave takes two k-blocks of all four taps; else tap (ty, tx) = wave over all
-      // eight k-blocks. ----
+      // Each wave takes two k-blocks of all four taps. ----
       const int b = (it - 1) & 1;
       const float* dyt = dyt_buf(b);
       const uint8_t* img = img_buf(b);
@@ -1271,167 +1265,89 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
       const int g = lane >> 4, col = lane & 15;
       // the high halves of two fp32 words as a bf16 pair (x0 low, x1 high)
       auto hi2 = [](uint32_t x0, uint32_t x1) { return __builtin_amdgcn_perm(x1, x0, 0x07060302u); };
-      if constexpr (L::WKS) {
-        // k-blocks kb = 2 wave, 2 wave + 1 of all four taps: per ty, image bytes X = 8 (g & 1)
-        // .. + 8, converted once for both tx; padding pixels take zero image bytes
-        struct Raw {
-          float a[2][8];        // dY1 of oc 16 i + col, pixels 8 g .. 8 g + 7
-          uint32_t w[2][3][3];  // [ty][channel tile j] image dwords at X = 8 (g & 1) + {0, 4, 8}
-        };
-        auto load = [&](int kb, Raw& r) {
+      // k-blocks kb = 2 wave, 2 wave + 1 of all four taps: per ty, image bytes X = 8 (g & 1)
+      // .. + 8, converted once for both tx; padding pixels take zero image bytes
+      struct Raw {
+        float a[2][8];        // dY1 of oc 16 i + col, pixels 8 g .. 8 g + 7
+        uint32_t w[2][3][3];  // [ty][channel tile j] image dwords at X = 8 (g & 1) + {0, 4, 8}
+      };
+      auto load = [&](int kb, Raw& r) {
 #pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            const int pr = min(32 * kb + 8 * g + c, L::NROW - 1);
+        for (int c = 0; c < 8; ++c) {
+          const int pr = min(32 * kb + 8 * g + c, L::NROW - 1);
 #pragma unroll
-            for (int i = 0; i < 2; ++i) r.a[i][c] = dyt[pr * LDX + 16 * i + col];
-          }
-          const bool pad = kb == NKB - 1 && g >= 2;  // image row 15: zero bytes
-#pragma unroll
-          for (int ty = 0; ty < 2; ++ty) {
-            const int Y = min(2 * kb + (g >> 1) + ty, c1::GRID - 1);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-              const uint32_t* wp = reinterpret_cast<const uint32_t*>(img + (Y * c1::CH + 16 * j + col) * XP + 8 * (g & 1));
-#pragma unroll
-              for (int q = 0; q < 3; ++q) r.w[ty][j][q] = pad ? 0u : wp[q];
-            }
-          }
-        };
-        Raw rr[2];
-        load(2 * wave, rr[0]);
-        load(2 * wave + 1, rr[1]);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const Raw& r = rr[kk];  // k-block 2 wave + kk
-          // A: the three terms of the 16 dY1 values (truncation: the top 8 significand bits of x,
-          // then of the remainder, then the <= 8 bits left; each term's fp32 bits are its bf16 in
-          // the high half, every product the fp32 product)
-          VB fa[2][3];
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            uint32_t th[4], tm[4], tl[4];
-#pragma unroll
-            for (int c = 0; c < 8; c += 2) {
-              uint32_t x[2], r1[2], r2[2];
-#pragma unroll
-              for (int u = 0; u < 2; ++u) {
-                x[u] = __builtin_bit_cast(uint32_t, r.a[i][c + u]);
-                const float f1 = r.a[i][c + u] - __builtin_bit_cast(float, x[u] & 0xffff0000u);
-                r1[u] = __builtin_bit_cast(uint32_t, f1);
-                r2[u] = __builtin_bit_cast(uint32_t, f1 - __builtin_bit_cast(float, r1[u] & 0xffff0000u));
-              }
-              th[c / 2] = hi2(x[0], x[1]);
-              tm[c / 2] = hi2(r1[0], r1[1]);
-              tl[c / 2] = hi2(r2[0], r2[1]);
-            }
-            fa[i][0] = __builtin_bit_cast(VB, th);
-            fa[i][1] = __builtin_bit_cast(VB, tm);
-            fa[i][2] = __builtin_bit_cast(VB, tl);
-          }
-#pragma unroll
-          for (int ty = 0; ty < 2; ++ty) {
-            // B of taps (ty, 0) and (ty, 1), one channel tile j at a time: image bytes X = 0 .. 8
-            // (from 8 (g & 1)) -> fp32 (exact), pairs (X, X + 1) from X = tx as bf16 (the high
-            // halves; exact for bytes)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-              uint32_t f[9];
-#pragma unroll
-              for (int k = 0; k < 9; ++k)
-                f[k] = __builtin_bit_cast(uint32_t, (float)((r.w[ty][j][k >> 2] >> (8 * (k & 3))) & 255u));
-              VB fb[2];
-#pragma unroll
-              for (int tx = 0; tx < 2; ++tx) {
-                uint32_t t[4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) t[p] = hi2(f[2 * p + tx], f[2 * p + tx + 1]);
-                fb[tx] = __builtin_bit_cast(VB, t);
-              }
-#pragma unroll
-              for (int tx = 0; tx < 2; ++tx)
-#pragma unroll
-                for (int tm = 0; tm < 3; ++tm)
-#pragma unroll
-                  for (int i = 0; i < 2; ++i)
-                    acc[2 * ty + tx][i][j] = FB::mma(fa[i][tm], fb[tx], acc[2 * ty + tx][i][j]);
-            }
-          }
+          for (int i = 0; i < 2; ++i) r.a[i][c] = dyt[pr * LDX + 16 * i + col];
         }
-      } else {
-        struct Raw {
-          float a[2][8];     // dY1 of oc 16 i + col, pixels 8 g .. 8 g + 7
-          uint32_t w[3][3];  // image dwords at X = 8 (g & 1) + {0, 4, 8}, channel tile j
-        };
-        auto load = [&](int kb, Raw& r) {
-  #pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            const int pr = min(32 * kb + 8 * g + c, L::NROW - 1);
-  #pragma unroll
-            for (int i = 0; i < 2; ++i) r.a[i][c] = dyt[pr * LDX + 16 * i + col];
-          }
+        const bool pad = kb == NKB - 1 && g >= 2;  // image row 15: zero bytes
+#pragma unroll
+        for (int ty = 0; ty < 2; ++ty) {
           const int Y = min(2 * kb + (g >> 1) + ty, c1::GRID - 1);
-  #pragma unroll
+#pragma unroll
           for (int j = 0; j < 3; ++j) {
             const uint32_t* wp = reinterpret_cast<const uint32_t*>(img + (Y * c1::CH + 16 * j + col) * XP + 8 * (g & 1));
-  #pragma unroll
-            for (int q = 0; q < 3; ++q) r.w[j][q] = wp[q];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) r.w[ty][j][q] = pad ? 0u : wp[q];
           }
-        };
-        Raw rr[2];
-        load(0, rr[0]);
-  #pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-          const Raw& r = rr[kb & 1];
-          // A: the three terms of the 16 dY1 values
-          VB fa[2][3];
-  #pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            uint32_t th[4], tm[4], tl[4];
-  #pragma unroll
-            for (int c = 0; c < 8; c += 2) {
-              uint32_t x[2], r1[2], r2[2];
-  #pragma unroll
-              for (int u = 0; u < 2; ++u) {
-                x[u] = __builtin_bit_cast(uint32_t, r.a[i][c + u]);
-                const float f1 = r.a[i][c + u] - __builtin_bit_cast(float, x[u] & 0xffff0000u);
-                r1[u] = __builtin_bit_cast(uint32_t, f1);
-                r2[u] = __builtin_bit_cast(uint32_t, f1 - __builtin_bit_cast(float, r1[u] & 0xffff0000u));
-              }
-              th[c / 2] = hi2(x[0], x[1]);
-              tm[c / 2] = hi2(r1[0], r1[1]);
-              tl[c / 2] = hi2(r2[0], r2[1]);
+        }
+      };
+      Raw rr[2];
+      load(2 * wave, rr[0]);
+      load(2 * wave + 1, rr[1]);
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const Raw& r = rr[kk];  // k-block 2 wave + kk
+        // A: the three terms of the 16 dY1 values (truncation: the top 8 significand bits of x,
+        // then of the remainder, then the <= 8 bits left; each term's fp32 bits are its bf16 in
+        // the high half, every product the fp32 product)
+        VB fa[2][3];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          uint32_t th[4], tm[4], tl[4];
+#pragma unroll
+          for (int c = 0; c < 8; c += 2) {
+            uint32_t x[2], r1[2], r2[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              x[u] = __builtin_bit_cast(uint32_t, r.a[i][c + u]);
+              const float f1 = r.a[i][c + u] - __builtin_bit_cast(float, x[u] & 0xffff0000u);
+              r1[u] = __builtin_bit_cast(uint32_t, f1);
+              r2[u] = __builtin_bit_cast(uint32_t, f1 - __builtin_bit_cast(float, r1[u] & 0xffff0000u));
             }
-            fa[i][0] = __builtin_bit_cast(VB, th);
-            fa[i][1] = __builtin_bit_cast(VB, tm);
-            fa[i][2] = __builtin_bit_cast(VB, tl);
+            th[c / 2] = hi2(x[0], x[1]);
+            tm[c / 2] = hi2(r1[0], r1[1]);
+            tl[c / 2] = hi2(r2[0], r2[1]);
           }
-          // B: 8 image bytes per channel tile -> bf16 (exact), zero on the padding row
-          const bool pad = kb == NKB - 1 && g >= 2;
-          VB fb[3];
-  #pragma unroll
+          fa[i][0] = __builtin_bit_cast(VB, th);
+          fa[i][1] = __builtin_bit_cast(VB, tm);
+          fa[i][2] = __builtin_bit_cast(VB, tl);
+        }
+#pragma unroll
+        for (int ty = 0; ty < 2; ++ty) {
+          // B of taps (ty, 0) and (ty, 1), one channel tile j at a time: image bytes X = 0 .. 8
+          // (from 8 (g & 1)) -> fp32 (exact), pairs (X, X + 1) from X = tx as bf16 (the high
+          // halves; exact for bytes)
+#pragma unroll
           for (int j = 0; j < 3; ++j) {
-            const uint32_t w0 = __builtin_amdgcn_alignbyte(r.w[j][1], r.w[j][0], tx);
-            const uint32_t w1 = __builtin_amdgcn_alignbyte(r.w[j][2], r.w[j][1], tx);
-            uint32_t t[4];
-  #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              const uint32_t w = h ? w1 : w0;
-              const uint32_t f0 = __builtin_bit_cast(uint32_t, (float)(w & 255u));
-              const uint32_t f1 = __builtin_bit_cast(uint32_t, (float)((w >> 8) & 255u));
-              const uint32_t f2 = __builtin_bit_cast(uint32_t, (float)((w >> 16) & 255u));
-              const uint32_t f3 = __builtin_bit_cast(uint32_t, (float)(w >> 24));
-              t[2 * h] = pad ? 0u : hi2(f0, f1);
-              t[2 * h + 1] = pad ? 0u : hi2(f2, f3);
+            uint32_t f[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+              f[k] = __builtin_bit_cast(uint32_t, (float)((r.w[ty][j][k >> 2] >> (8 * (k & 3))) & 255u));
+            VB fb[2];
+#pragma unroll
+            for (int tx = 0; tx < 2; ++tx) {
+              uint32_t t[4];
+#pragma unroll
+              for (int p = 0; p < 4; ++p) t[p] = hi2(f[2 * p + tx], f[2 * p + tx + 1]);
+              fb[tx] = __builtin_bit_cast(VB, t);
             }
-            fb[j] = __builtin_bit_cast(VB, t);
+#pragma unroll
+            for (int tx = 0; tx < 2; ++tx)
+#pragma unroll
+              for (int tm = 0; tm < 3; ++tm)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+                  acc[2 * ty + tx][i][j] = FB::mma(fa[i][tm], fb[tx], acc[2 * ty + tx][i][j]);
           }
-          if (kb + 1 < NKB) load(kb + 1, rr[(kb + 1) & 1]);
-  #pragma unroll
-          for (int tm = 0; tm < 3; ++tm)
-  #pragma unroll
-            for (int j = 0; j < 3; ++j)
-  #pragma unroll
-              for (int i = 0; i < 2; ++i) acc[0][i][j] = FB::mma(fa[i][tm], fb[j], acc[0][i][j]);
         }
       }
       stage_st(it < nF ? f0 + it : -1, it & 1, it + 1 < nF ? f0 + it + 1 : -1, (it + 1) & 1, sr);
@@ -1441,18 +1357,16 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
   // conv1 bias: group A's 32 lanes of each channel group (8 per wave, 4 waves) in a fixed order
   float* bred = smem + L::Z0;
   if (is_a) *reinterpret_cast<f32x4*>(bred + 4 * tid) = f32x4{bsum[0], bsum[1], bsum[2], bsum[3]};
-  // WKS: group B's k-block partials of every tap -> the image / dY1 tiles' space (free now)
+  // group B's k-block partials of every tap -> the image / dY1 tiles' space (free now)
   f32x4* wpart = reinterpret_cast<f32x4*>(smem + L::IMG);
-  static_assert(!L::WKS || 4 * 4 * 6 * 64 * 4 <= L::D2S - L::IMG, "partials fit");
-  if constexpr (L::WKS) {
-    if (!is_a) {
+  static_assert(4 * 4 * 6 * 64 * 4 <= L::D2S - L::IMG, "partials fit");
+  if (!is_a) {
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
+    for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < 3; ++j) wpart[((wave * 4 + t) * 6 + 3 * i + j) * 64 + lane] = acc[t][i][j];
-    }
+        for (int j = 0; j < 3; ++j) wpart[((wave * 4 + t) * 6 + 3 * i + j) * 64 + lane] = acc[t][i][j];
   }
   __syncthreads();
   if (is_a && tid < OC1) {
@@ -1462,18 +1376,16 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
     slab_bias[(size_t)wg * OC1 + tid] = bs;
   }
   if (!is_a) {
-    // wave w writes tap w (WKS: the four waves' k-block partials of it, summed in wave order)
-    if constexpr (L::WKS) {
+    // wave w writes tap w: the four waves' k-block partials of it, summed in wave order
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          f32x4 v = wpart[((0 * 4 + wave) * 6 + 3 * i + j) * 64 + lane];
+      for (int j = 0; j < 3; ++j) {
+        f32x4 v = wpart[((0 * 4 + wave) * 6 + 3 * i + j) * 64 + lane];
 #pragma unroll
-          for (int w = 1; w < 4; ++w) v += wpart[((w * 4 + wave) * 6 + 3 * i + j) * 64 + lane];
-          acc[0][i][j] = v;
-        }
-    }
+        for (int w = 1; w < 4; ++w) v += wpart[((w * 4 + wave) * 6 + 3 * i + j) * 64 + lane];
+        acc[0][i][j] = v;
+      }
     const size_t so = (size_t)wg * OC1 * K1;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -1496,57 +1408,55 @@ DEV void conv12_bwd_body(const uint8_t* __restrict__ x, const T* __restrict__ w2
     Frag<float>::vec wb[4][OC2 / Frag<float>::KSTEP][2];
     conv12_bwd_body_f32<-1, O>(x, reinterpret_cast<const float*>(w2t), reinterpret_cast<const float*>(dy2),
                             mask1, slab, slab_bias, N, fpw, wg, lds, wb, true, rm);
-    return;
-  }
-  using F = Frag<T>;
-  typedef typename F::vec V;
-  constexpr int KPL = F::KPL, KS = F::KSTEP;
-  constexpr int LDI = c1::LB<T>::LDI;
-  constexpr int VEC = 16 / (int)sizeof(T);
-  constexpr int LDX = c1::LB<T>::LDX;                 // dY1 tile row (elements)
-  constexpr int LD2 = c1::LB<T>::LD2;                 // dY2 cell row (elements)
-  constexpr int IMGSZ = c1::GRID * c1::GRID * LDI, DYSZ = c1::NPAD * LDX;
-  constexpr int D2V = P2 * OC2 / VEC;                 // 16-byte vectors of one dY2 frame
-  constexpr int ND2 = (D2V + 255) / 256;
-  constexpr int NOK = OC2 / KS;                       // k-steps per tap
-  constexpr int G = c12_groups<T>();
-  constexpr int GSZ = IMGSZ + DYSZ + c12::NCELL * LD2;  // elements of one group's tiles
-  static_assert(GSZ == C12BLds<T>::GSZ, "LDS layout");
-  T* smem = reinterpret_cast<T*>(lds);
-  uint32_t (*msk_all)[c1::NPIX] = reinterpret_cast<uint32_t (*)[c1::NPIX]>(lds + C12BLds<T>::MSK);
-  float* bred = reinterpret_cast<float*>(lds + C12BLds<T>::BRED);
-  const int grp = threadIdx.x >> 8, tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-  T* img = smem + grp * GSZ;
-  T* dyt = img + IMGSZ;
-  T* d2s = dyt + DYSZ;
-  uint32_t* msk = msk_all[grp];
-  const int f0 = wg * fpw, f1 = min(N, f0 + fpw);
-  f32x4 acc[2][3];
+  } else {  // bf16 (the only other T that c1::LB and C12BLds have a layout for)
+    using F = Frag<T>;
+    typedef typename F::vec V;
+    constexpr int KPL = F::KPL, KS = F::KSTEP;
+    constexpr int LDI = c1::LB<T>::LDI;
+    constexpr int VEC = 16 / (int)sizeof(T);
+    constexpr int LDX = c1::LB<T>::LDX;                 // dY1 tile row (elements)
+    constexpr int LD2 = c1::LB<T>::LD2;                 // dY2 cell row (elements)
+    constexpr int IMGSZ = c1::GRID * c1::GRID * LDI, DYSZ = c1::NPAD * LDX;
+    constexpr int D2V = P2 * OC2 / VEC;                 // 16-byte vectors of one dY2 frame
+    constexpr int ND2 = (D2V + 255) / 256;
+    constexpr int NOK = OC2 / KS;                       // k-steps per tap
+    constexpr int G = C12_GROUPS;
+    constexpr int GSZ = IMGSZ + DYSZ + c12::NCELL * LD2;  // elements of one group's tiles
+    static_assert(GSZ == C12BLds<T>::GSZ, "LDS layout");
+    T* smem = reinterpret_cast<T*>(lds);
+    uint32_t (*msk_all)[c1::NPIX] = reinterpret_cast<uint32_t (*)[c1::NPIX]>(lds + C12BLds<T>::MSK);
+    float* bred = reinterpret_cast<float*>(lds + C12BLds<T>::BRED);
+    const int grp = threadIdx.x >> 8, tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
+    T* img = smem + grp * GSZ;
+    T* dyt = img + IMGSZ;
+    T* d2s = dyt + DYSZ;
+    uint32_t* msk = msk_all[grp];
+    const int f0 = wg * fpw, f1 = min(N, f0 + fpw);
+    f32x4 acc[2][3];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 3; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float bsum[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};  // conv1 bias partials
-  uint4 nv[3];
-  V nd2[ND2];
-  uint32_t nmk = 0;
-  auto fetch = [&](int f) {
-    c1_load_frame<T>(x + rm.map(f) * IMG, tid, nv);
-    const T* src = dy2 + (size_t)f * P2 * OC2;
+      for (int j = 0; j < 3; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bsum[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};  // conv1 bias partials
+    uint4 nv[3];
+    V nd2[ND2];
+    uint32_t nmk = 0;
+    auto fetch = [&](int f) {
+      c1_load_frame<T>(x + rm.map(f) * IMG, tid, nv);
+      const T* src = dy2 + (size_t)f * P2 * OC2;
 #pragma unroll
-    for (int i = 0; i < ND2; ++i) {
-      const int e = tid + i * 256;
-      nd2[i] = e < D2V ? *reinterpret_cast<const V*>(src + e * VEC) : F::zero();
-    }
-    if (tid < c1::NPIX) nmk = mask1[(size_t)f * c1::NPIX + tid];
-  };
-  if (f0 + grp < f1) fetch(f0 + grp);  // the first frame is in flight during the prologue
-  // class of this wave: output pixels iy = 2 qy + py, ix = 2 qx + px; taps kh = py + 2 j1,
-  // kw = px + 2 j2 read dY2 at (qy - j1, qx - j2)
-  const int py = wave >> 1, px = wave & 1;
-  V wa[4][2][NOK];  // [tap j1*2+j2][ci tile][k-step]: A[ci][oc] = W2[oc][kh][kw][ci]
-  if constexpr (sizeof(T) == 2) {
-    // bf16: W2 [64][512] staged through LDS with 16-byte loads (rows padded to 528 and stored
+      for (int i = 0; i < ND2; ++i) {
+        const int e = tid + i * 256;
+        nd2[i] = e < D2V ? *reinterpret_cast<const V*>(src + e * VEC) : F::zero();
+      }
+      if (tid < c1::NPIX) nmk = mask1[(size_t)f * c1::NPIX + tid];
+    };
+    if (f0 + grp < f1) fetch(f0 + grp);  // the first frame is in flight during the prologue
+    // class of this wave: output pixels iy = 2 qy + py, ix = 2 qx + px; taps kh = py + 2 j1,
+    // kw = px + 2 j2 read dY2 at (qy - j1, qx - j2)
+    const int py = wave >> 1, px = wave & 1;
+    V wa[4][2][NOK];  // [tap j1*2+j2][ci tile][k-step]: A[ci][oc] = W2[oc][kh][kw][ci]
+    // W2 [64][512] staged through LDS with 16-byte loads (rows padded to 528 and stored
     // bit-2/3 swapped, wg_row), the fragments (k = oc along the lane's 8 values) read with the
     // transposing LDS read, conflict-free
     constexpr int LDW = K2 + 2 * VEC, NWV = OC2 * K2 / VEC, NT = 256 * G, NPT = NWV / NT;
@@ -1574,129 +1484,105 @@ DEV void conv12_bwd_body(const uint8_t* __restrict__ x, const T* __restrict__ w2
           wa[t][i][ks] = lds_frag_k_sw(w2s + ks * KS * LDW + (kh * KS2 + kw) * OC1 + 16 * i, LDW, lane);
     }
     __syncthreads();  // the staging area becomes the frame tiles
-  } else {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int kh = py + 2 * (t >> 1), kw = px + 2 * (t & 1);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int ks = 0; ks < NOK; ++ks) {
-          const T* src = w2 + (size_t)(ks * KS + KPL * (lane >> 4)) * K2 + (kh * KS2 + kw) * OC1 +
-                         16 * i + (lane & 15);
-          V v;
-#pragma unroll
-          for (int j = 0; j < KPL; ++j) v[j] = src[(size_t)j * K2];
-          wa[t][i][ks] = v;
-        }
-    }
-  }
-  // zero the dY1 rows no pixel writes and the dY2 cell grid once (the border stays zero);
-  // the dY1 rows in 4-element pieces (rows of 36 elements start 8-byte aligned).  bf16: dY1
-  // rows are grid rows oy * 16 + ox (the s2d image's), so the pad rows are ox = 15 and
-  // oy = 15; fp32: rows are pixels, pad rows 225..255.
-  static_assert((c1::NPAD - c1::NPIX) * LDX % 4 == 0 && c12::NCELL * LD2 % VEC == 0 &&
-                c1::NPIX * LDX % 4 == 0 && LDX % 4 == 0, "zero fill");
-  constexpr bool GR = sizeof(T) == 2;
-  for (int e = tid; e < (c1::NPAD - c1::NPIX) * LDX / 4; e += 256) {
-    const float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (GR) {
+    // zero the dY1 rows no pixel writes and the dY2 cell grid once (the border stays zero);
+    // the dY1 rows in 4-element pieces (rows of 36 elements start 8-byte aligned).  dY1 rows
+    // are grid rows oy * 16 + ox (the s2d image's), so the pad rows are ox = 15 and oy = 15.
+    static_assert((c1::NPAD - c1::NPIX) * LDX % 4 == 0 && c12::NCELL * LD2 % VEC == 0 &&
+                  c1::NPIX * LDX % 4 == 0 && LDX % 4 == 0, "zero fill");
+    for (int e = tid; e < (c1::NPAD - c1::NPIX) * LDX / 4; e += 256) {
+      const float z[4] = {0.f, 0.f, 0.f, 0.f};
       const int rr = e / (LDX / 4), c = (e % (LDX / 4)) * 4;
       const int row = rr < H1 ? rr * c1::GRID + H1 : c1::GRID * H1 + (rr - H1);
       store4(dyt + row * LDX + c, z);
-    } else {
-      store4(dyt + c1::NPIX * LDX + e * 4, z);
     }
-  }
-  for (int e = tid; e < c12::NCELL * LD2 / VEC; e += 256)
-    *reinterpret_cast<V*>(d2s + e * VEC) = F::zero();
-  const int tapoff = ((wave >> 1) * c1::GRID + (wave & 1)) * LDI;
-  const int kl = KPL * (lane >> 4);
-  const int n_it = (f1 - f0 + G - 1) / G;
-  for (int it = 0; it < n_it; ++it) {
-    const int f = f0 + G * it + grp;
-    const bool active = f < f1;
-    __syncthreads();  // the previous frame's readers are done
-    if (active) {
-    c1_stash_frame<T, LDI>(img, tid, nv);
+    for (int e = tid; e < c12::NCELL * LD2 / VEC; e += 256)
+      *reinterpret_cast<V*>(d2s + e * VEC) = F::zero();
+    const int tapoff = ((wave >> 1) * c1::GRID + (wave & 1)) * LDI;
+    const int kl = KPL * (lane >> 4);
+    const int n_it = (f1 - f0 + G - 1) / G;
+    for (int it = 0; it < n_it; ++it) {
+      const int f = f0 + G * it + grp;
+      const bool active = f < f1;
+      __syncthreads();  // the previous frame's readers are done
+      if (active) {
+      c1_stash_frame<T, LDI>(img, tid, nv);
 #pragma unroll
-    for (int i = 0; i < ND2; ++i) {
-      const int e = tid + i * 256;
-      if (e < D2V) {
-        const int cell = (e * VEC) / OC2, oc = (e * VEC) % OC2;
-        const int oy = cell / H2, ox = cell - oy * H2;
-        *reinterpret_cast<V*>(d2s + ((oy + 1) * c12::QG + ox + 1) * LD2 + oc) = nd2[i];
-      }
-    }
-    if (tid < c1::NPIX) msk[tid] = nmk;
-    }
-    __syncthreads();
-    if (f + G < f1) fetch(f + G);
-    // ---- conv2 dgrad of class `wave` -> masked dY1 rows in LDS (+ conv1 bias partials) ----
-    // Only the tap-(0,0) B fragments are read from LDS (cells (qy, qx) of all 4 column tiles);
-    // the shifted taps are lane moves: the 16 lanes of a fragment row are cells qx = l & 7 of
-    // rows qy = 2 nt + ((l >> 3) & 1), so qx - 1 is a DPP row shift right by one (zero in at
-    // qx = 0: lane 7 -> 8 carries the always-zero column qx = 7) and qy - 1 is a shift by 8,
-    // taking the lower half from the previous tile.
-    if (active) {
-      V b0[4][NOK];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const int cell = nt * 16 + (lane & 15), qy = cell >> 3, qx = cell & 7;
-        const T* brow = d2s + ((qy + 1) * c12::QG + qx + 1) * LD2 + kl;
-#pragma unroll
-        for (int ks = 0; ks < NOK; ++ks) b0[nt][ks] = *reinterpret_cast<const V*>(brow + ks * KS);
-      }
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {  // 16-cell column tiles of the 8x8 class grid
-        f32x4 d[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int ks = 0; ks < NOK; ++ks) {
-          const V bt0 = b0[nt][ks];
-          const V bt1 = dpp_move<0x111>(bt0);                       // (qy, qx - 1)
-          V bt2 = dpp_move<0x118>(bt0);                             // (qy - 1, qx): odd rows
-          if (nt > 0) bt2 = vor(bt2, dpp_move<0x108>(b0[nt - 1][ks]));  // even rows
-          const V bt3 = dpp_move<0x111>(bt2);                       // (qy - 1, qx - 1)
-          d[0] = F::mma(wa[0][0][ks], bt0, d[0]);
-          d[1] = F::mma(wa[0][1][ks], bt0, d[1]);
-          d[0] = F::mma(wa[1][0][ks], bt1, d[0]);
-          d[1] = F::mma(wa[1][1][ks], bt1, d[1]);
-          d[0] = F::mma(wa[2][0][ks], bt2, d[0]);
-          d[1] = F::mma(wa[2][1][ks], bt2, d[1]);
-          d[0] = F::mma(wa[3][0][ks], bt3, d[0]);
-          d[1] = F::mma(wa[3][1][ks], bt3, d[1]);
+      for (int i = 0; i < ND2; ++i) {
+        const int e = tid + i * 256;
+        if (e < D2V) {
+          const int cell = (e * VEC) / OC2, oc = (e * VEC) % OC2;
+          const int oy = cell / H2, ox = cell - oy * H2;
+          *reinterpret_cast<V*>(d2s + ((oy + 1) * c12::QG + ox + 1) * LD2 + oc) = nd2[i];
         }
-        const int cell = nt * 16 + (lane & 15), qy = cell >> 3, qx = cell & 7;
-        const int iy = 2 * qy + py, ix = 2 * qx + px;
-        if (iy < H1 && ix < H1) {
-          const int p = iy * H1 + ix, drow = GR ? iy * c1::GRID + ix : p;
-          const uint32_t m = msk[p];
+      }
+      if (tid < c1::NPIX) msk[tid] = nmk;
+      }
+      __syncthreads();
+      if (f + G < f1) fetch(f + G);
+      // ---- conv2 dgrad of class `wave` -> masked dY1 rows in LDS (+ conv1 bias partials) ----
+      // Only the tap-(0,0) B fragments are read from LDS (cells (qy, qx) of all 4 column tiles);
+      // the shifted taps are lane moves: the 16 lanes of a fragment row are cells qx = l & 7 of
+      // rows qy = 2 nt + ((l >> 3) & 1), so qx - 1 is a DPP row shift right by one (zero in at
+      // qx = 0: lane 7 -> 8 carries the always-zero column qx = 7) and qy - 1 is a shift by 8,
+      // taking the lower half from the previous tile.
+      if (active) {
+        V b0[4][NOK];
 #pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const int ci = 16 * i + 4 * (lane >> 4);
-            float v[4];
+        for (int nt = 0; nt < 4; ++nt) {
+          const int cell = nt * 16 + (lane & 15), qy = cell >> 3, qx = cell & 7;
+          const T* brow = d2s + ((qy + 1) * c12::QG + qx + 1) * LD2 + kl;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              v[q] = (m >> (ci + q)) & 1u ? d[i][q] : 0.f;
-              bsum[i][q] += v[q];
+          for (int ks = 0; ks < NOK; ++ks) b0[nt][ks] = *reinterpret_cast<const V*>(brow + ks * KS);
+        }
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {  // 16-cell column tiles of the 8x8 class grid
+          f32x4 d[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+          for (int ks = 0; ks < NOK; ++ks) {
+            const V bt0 = b0[nt][ks];
+            const V bt1 = dpp_move<0x111>(bt0);                       // (qy, qx - 1)
+            V bt2 = dpp_move<0x118>(bt0);                             // (qy - 1, qx): odd rows
+            if (nt > 0) bt2 = vor(bt2, dpp_move<0x108>(b0[nt - 1][ks]));  // even rows
+            const V bt3 = dpp_move<0x111>(bt2);                       // (qy - 1, qx - 1)
+            d[0] = F::mma(wa[0][0][ks], bt0, d[0]);
+            d[1] = F::mma(wa[0][1][ks], bt0, d[1]);
+            d[0] = F::mma(wa[1][0][ks], bt1, d[0]);
+            d[1] = F::mma(wa[1][1][ks], bt1, d[1]);
+            d[0] = F::mma(wa[2][0][ks], bt2, d[0]);
+            d[1] = F::mma(wa[2][1][ks], bt2, d[1]);
+            d[0] = F::mma(wa[3][0][ks], bt3, d[0]);
+            d[1] = F::mma(wa[3][1][ks], bt3, d[1]);
+          }
+          const int cell = nt * 16 + (lane & 15), qy = cell >> 3, qx = cell & 7;
+          const int iy = 2 * qy + py, ix = 2 * qx + px;
+          if (iy < H1 && ix < H1) {
+            const int p = iy * H1 + ix, drow = iy * c1::GRID + ix;
+            const uint32_t m = msk[p];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+              const int ci = 16 * i + 4 * (lane >> 4);
+              float v[4];
+#pragma unroll
+              for (int q = 0; q < 4; ++q) {
+                v[q] = (m >> (ci + q)) & 1u ? d[i][q] : 0.f;
+                bsum[i][q] += v[q];
+              }
+              store4(dyt + drow * LDX + ci, v);
             }
-            store4(dyt + drow * LDX + ci, v);
           }
         }
       }
-    }
-    __syncthreads();  // (every group reaches it: no early exit for an idle group)
-    if (!active) continue;
-    // ---- conv1 weight gradient: reduction over the frame's (padded) 256 pixels, fragments
-    // software-pipelined one k-step ahead.  bf16: the k slots of a 32-deep step are the 32
-    // grid rows kk .. kk + 31 taken in the order that gives each 32-lane half of a
-    // transposing read 8 rows R + 4m (m = 0..7): at dY1's 18-dword and the image's 26-dword
-    // row steps those are 8 disjoint 8-dword bank ranges (tools/ldsbank.py: dY1 reads 2.0x ->
-    // 1.0x, image reads 1.88x -> 1.09x).  Rows without a pixel hold dY1 = 0; their image row
-    // is clamped to the last pixel row (238) so that the tap offsets stay inside the stashed image
-    // rows 0..255 (a 0 x NaN from an unwritten row would poison the sum). ----
-    auto frag = [&](int kk, V* a, V* b) {
-      if constexpr (sizeof(T) == 2) {
+      __syncthreads();  // (every group reaches it: no early exit for an idle group)
+      if (!active) continue;
+      // ---- conv1 weight gradient: reduction over the frame's (padded) 256 pixels, fragments
+      // software-pipelined one k-step ahead.  The k slots of a 32-deep step are the 32
+      // grid rows kk .. kk + 31 taken in the order that gives each 32-lane half of a
+      // transposing read 8 rows R + 4m (m = 0..7): at dY1's 18-dword and the image's 26-dword
+      // row steps those are 8 disjoint 8-dword bank ranges (tools/ldsbank.py: dY1 reads 2.0x ->
+      // 1.0x, image reads 1.88x -> 1.09x).  Rows without a pixel hold dY1 = 0; their image row
+      // is clamped to the last pixel row (238) so that the tap offsets stay inside the stashed image
+      // rows 0..255 (a 0 x NaN from an unwritten row would poison the sum). ----
+      auto frag = [&](int kk, V* a, V* b) {
         const int g = lane >> 4, ii = lane & 15, q = ii >> 2, pp = ii & 3;
         const int r0 = kk + 4 * (q + 4 * (g & 1)) + 2 * (g >> 1);  // rows r0 (k 0..3), r0 + 1
 #pragma unroll
@@ -1720,99 +1606,84 @@ DEV void conv12_bwd_body(const uint8_t* __restrict__ x, const T* __restrict__ w2
           v[4] = w[0]; v[5] = w[1]; v[6] = w[2]; v[7] = w[3];
           b[j] = v;
         }
-      } else {
+      };
+      constexpr int NKK = c1::NPAD / KS;
+      V fa[2][2], fb[2][3];
+      frag(0, fa[0], fb[0]);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) a[i] = lds_frag_k(dyt + kk * LDX + 16 * i, LDX, lane);
-        const int g = lane >> 4, col = lane & 15;
-        int rr[4];
+      for (int s2 = 0; s2 < NKK; ++s2) {
+        if (s2 + 1 < NKK) frag((s2 + 1) * KS, fa[(s2 + 1) & 1], fb[(s2 + 1) & 1]);
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-          rr[jj] = c1_row(min(kk + 4 * g + jj, c1::NPIX - 1), 0) * LDI + tapoff + col;
+        for (int e = 0; e < F::NE; ++e)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          V v;
+          for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int jj = 0; jj < 4; ++jj) v[jj] = (float)img[rr[jj] + 16 * j];
-          b[j] = v;
-        }
+            for (int j = 0; j < 3; ++j) acc[i][j] = F::mma_e(e, fa[s2 & 1][i], fb[s2 & 1][j], acc[i][j]);
       }
-    };
-    constexpr int NKK = c1::NPAD / KS;
-    V fa[2][2], fb[2][3];
-    frag(0, fa[0], fb[0]);
-#pragma unroll
-    for (int s2 = 0; s2 < NKK; ++s2) {
-      if (s2 + 1 < NKK) frag((s2 + 1) * KS, fa[(s2 + 1) & 1], fb[(s2 + 1) & 1]);
-#pragma unroll
-      for (int e = 0; e < F::NE; ++e)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j) acc[i][j] = F::mma_e(e, fa[s2 & 1][i], fb[s2 & 1][j], acc[i][j]);
     }
-  }
-  // conv1 bias: sum each lane's partials over the 16 lanes of its channel group (fixed
-  // butterfly order), then over the 4 class waves and the G groups in LDS, in a fixed order
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v = bsum[i][q];
-      v = row16_sum(v);
-      bsum[i][q] = v;
-    }
-  __syncthreads();  // all groups are done with their tiles
-  if ((lane & 15) == 0) {
+    // conv1 bias: sum each lane's partials over the 16 lanes of its channel group (fixed
+    // butterfly order), then over the 4 class waves and the G groups in LDS, in a fixed order
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) bred[(grp * 4 + wave) * OC1 + 16 * i + 4 * (lane >> 4) + q] = bsum[i][q];
-  }
-  // fixed-order combine of the groups' weight-gradient partials: group g > 0 -> LDS -> group 0
-  float* red = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int g = 1; g < G; ++g) {
-    __syncthreads();
-    if (grp == g) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) red[((i * 3 + j) * 4 + q) * 256 + tid] = acc[i][j][q];
-    }
-    __syncthreads();
-    if (grp == 0) {
+      for (int q = 0; q < 4; ++q) {
+        float v = bsum[i][q];
+        v = row16_sum(v);
+        bsum[i][q] = v;
+      }
+    __syncthreads();  // all groups are done with their tiles
+    if ((lane & 15) == 0) {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) acc[i][j][q] += red[((i * 3 + j) * 4 + q) * 256 + tid];
+        for (int q = 0; q < 4; ++q) bred[(grp * 4 + wave) * OC1 + 16 * i + 4 * (lane >> 4) + q] = bsum[i][q];
     }
-  }
-  __syncthreads();
-  if (grp != 0) return;
-  if (tid < OC1) {
-    float bs = 0.f;
+    // fixed-order combine of the groups' weight-gradient partials: group g > 0 -> LDS -> group 0
+    float* red = reinterpret_cast<float*>(smem);
 #pragma unroll
-    for (int g = 0; g < 4 * G; ++g) bs += bred[g * OC1 + tid];
-    slab_bias[(size_t)wg * OC1 + tid] = bs;
-  }
-  const size_t so = (size_t)wg * OC1 * K1;
+    for (int g = 1; g < G; ++g) {
+      __syncthreads();
+      if (grp == g) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int col = wave * c1::CH + 16 * j + (lane & 15);
+          for (int j = 0; j < 3; ++j)
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        slab[so + (size_t)(16 * i + 4 * (lane >> 4) + q) * K1 + col] = acc[i][j][q] * (1.f / 255.f);
+            for (int q = 0; q < 4; ++q) red[((i * 3 + j) * 4 + q) * 256 + tid] = acc[i][j][q];
+      }
+      __syncthreads();
+      if (grp == 0) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[i][j][q] += red[((i * 3 + j) * 4 + q) * 256 + tid];
+      }
     }
+    __syncthreads();
+    if (grp != 0) return;
+    if (tid < OC1) {
+      float bs = 0.f;
+#pragma unroll
+      for (int g = 0; g < 4 * G; ++g) bs += bred[g * OC1 + tid];
+      slab_bias[(size_t)wg * OC1 + tid] = bs;
+    }
+    const size_t so = (size_t)wg * OC1 * K1;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const int col = wave * c1::CH + 16 * j + (lane & 15);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          slab[so + (size_t)(16 * i + 4 * (lane >> 4) + q) * K1 + col] = acc[i][j][q] * (1.f / 255.f);
+      }
+  }
 }
 
 template <typename T>
-__global__ __launch_bounds__(256 * c12_groups<T>()) void conv12_bwd_s2d(const uint8_t* __restrict__ x,
+__global__ __launch_bounds__(256 * C12_GROUPS) void conv12_bwd_s2d(const uint8_t* __restrict__ x,
                                                       const T* __restrict__ w2,     // [64][512]
                                                       const T* __restrict__ w2t,    // [512][64] (fp32)
                                                       const T* __restrict__ dy2,    // [N][36][64]

@@ -79,17 +79,6 @@ inline double dec(float x) {
 struct Split {
   int S = 1, mps = 32;  // splits, m per split
 };
-// fp32 FC forward K loop: chunks held ahead, accumulator chains (gemm.h gemm_tile_body).
-// PF / KACC 1 / 1: 13.97 us, 2 / 1: 13.40, 1 / 2: 14.20, 2 / 2: 13.67-13.69 (r04v2,
-// tools/var_specs/fcpf.py); 2 / 1 keeps the summation order, so the output bits are unchanged
-constexpr int FCF_PF = 2, FCF_KACC = 1;
-// fp32 FC forward: FCF_BR (hidden) x FCF_BC (frames) tiles whose FCF_NW waves split each
-// chunk's k-steps (gemm_tile_body KW).  16 x 80 on 8 waves: 256 tiles at N = 1280, one per CU,
-// two waves per SIMD (the 32 x 32 tiles put two on 64 CUs, whose MFMA time bounds the kernel;
-// 32 x 48 on 4 / 8 waves: 12.3 / 11.7 us, 16 x 80 on 8: 11.4 us; profiles/r05kw)
-constexpr bool FCF_KW = true;
-constexpr int FCF_BR = 16, FCF_BC = 80;
-constexpr int FCF_NW = 8;
 Split plan_split(long M, int tiles, int target_wgs, int chunk = 64) {
   Split s;
   const long chunks = (M + chunk - 1) / chunk;
@@ -263,7 +252,7 @@ int launch_forward(impala_learner* h, const uint8_t* obs, int n, hipStream_t st,
                    bool with_heads) {
   using namespace net;
   // K chunk of the LDS-staged tile GEMM: long chunks (few, each a full memory round trip) for
-  // bf16; fp32 at most 64 (tools/var_specs/fp32a.py: 32 -> 64 cut fc_fwd 18.2 -> 14.0 us and
+  // bf16; fp32 at most 64 (round-3 A/B: 32 -> 64 cut fc_fwd 18.2 -> 14.0 us and
   // conv3_fwd 28.3 -> 27.0 us; 128 / 256 lost on conv3_fwd's LDS footprint)
 #define BK(kb) (sizeof(T) == 4 ? ((kb) < 64 ? (kb) : 64) : (kb))
   const T* sw = reinterpret_cast<const T*>(h->shadow);
@@ -314,16 +303,11 @@ int launch_forward(impala_learner* h, const uint8_t* obs, int n, hipStream_t st,
   }
   {
     FcFwd<T> op{n, sw + sh.wfc, vv + Vecs::bfc, (const T*)h->y, h->zg, (T*)h->h};
-    // 32 x 32 tiles: 320 workgroups (5.9 vs 6.7 us for 64 x 32, tools/var_specs/fcfwd.py);
-    // fp32: two K chunks in registers ahead of the MFMAs (FCF_PF / FCF_KACC)
-    constexpr int PF = sizeof(T) == 4 ? FCF_PF : 1, KA = sizeof(T) == 4 ? FCF_KACC : 1;
-    constexpr bool KW = sizeof(T) == 4 && FCF_KW;
-    constexpr int BR = KW ? FCF_BR : 32, BC = KW ? FCF_BC : 32;
-    // KW on FCF_NW waves (8: two per SIMD, K chunk 128 = one k-step per wave per chunk)
-    constexpr int NWF = KW ? FCF_NW : 4, FBK = KW && FCF_NW == 8 ? (sizeof(T) == 4 ? 128 : 256) : BK(256);
-    if (int r = klaunch(h, K_FC_FWD, "fc_fwd", gemm_tile<T, BR, BC, FBK, 2, NWF / 2, FcFwd<T>, PF, KA, KW>,
-                        dim3(persist_grid(h, (long)cdiv(n, BC) * (HID / BR))), dim3(64 * NWF), st, op,
-                        HID / BR))
+    using C = FcFwdCfg<T>;
+    if (int r = klaunch(h, K_FC_FWD, "fc_fwd",
+                        gemm_tile<T, C::BR, C::BC, C::BK, 2, C::NW / 2, FcFwd<T>, C::PF, C::KW>,
+                        dim3(persist_grid(h, (long)cdiv(n, C::BC) * (HID / C::BR))), dim3(64 * C::NW), st,
+                        op, HID / C::BR))
       return r;
   }
   if (with_heads) {  // inference; in training the fused head kernel computes the heads
@@ -385,7 +369,7 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, co
   // chunk loads in flight per CU); fp32 keeps one group for its LDS budget.  The bf16 conv
   // weight gradients run 2 groups (56 KB of LDS: two workgroups per CU) rather than 4 (112 KB:
   // one, so the merged launch's 508 workgroups ran in two rounds): 17.1 -> 14.0 us, step 0.1029
-  // -> 0.1000 ms (tools/var_specs/bfg.py, profiles/r05bg).  The bf16 FC weight gradient keeps 2
+  // -> 0.1000 ms (profiles/r05bg).  The bf16 FC weight gradient keeps 2
   // (one group: 8.2 -> 8.9 us).
   constexpr int WG4 = sizeof(T) == 2 ? 2 : 1, WG2 = sizeof(T) == 2 ? 2 : 1;
   // The two cross-stage fusions need ln_c3 and c2_c1 in one range (the data-parallel parts 0 / 1
@@ -510,7 +494,7 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, co
     }
     if (lc12) return 0;
     return klaunch(h, K_CONV12_BWD, "conv2_dgrad_conv1_wgrad", conv12_bwd_s2d<T>, dim3(h->c1_wg),
-                   dim3(256 * c12_groups<T>()), st, b->obs, sw + sh.w2, sw + sh.w2t,
+                   dim3(256 * C12_GROUPS), st, b->obs, sw + sh.w2, sw + sh.w2t,
                    (const T*)h->dact2, (const uint32_t*)h->mask1, h->s_w1, h->s_b1, N, h->c1_fpw);
   };
 

@@ -820,7 +820,7 @@ DEV void adam_elem(const AdamArgs& a, float gscale, float step_size, float bc2s,
 // Blocks [0, HID) each own one row o of the FC weight (canonical [wfc + o*FLAT, +FLAT): 64% of
 // the parameters) and re-emit its kernel-layout row (jj = p*64 + c for canonical j = c*16 + p)
 // through LDS as one 16-byte (fp32) / 8-byte (bf16) store per thread: the per-element
-// scattered stores of write_shadow cost the step ~3 us (tools/var_specs/adamko.py,
+// scattered stores of write_shadow cost the step ~3 us (knock-outs in
 // profiles/r05tail).  Blocks [HID, ..) take the other parameters, one per thread in canonical
 // order with the FC rows skipped.
 static_assert((OC1 * K1 + OC1 + OC2 * K2 + OC2 + OC3 * K3 + OC3 + 2 * FLAT) % 4 == 0,

@@ -27,10 +27,10 @@ namespace lc3 {
 constexpr int ZR = 9 * OC2 + 4;  // Z row (fp32): [tap][ci] of one output pixel, padded
 }
 
-template <typename T> constexpr int lnc3_groups() { return sizeof(T) == 2 ? 2 : 1; }
+constexpr int LNC3_GROUPS = 2;  // bf16: 4-wave groups per workgroup (lnc3_body_g)
 // threads of a launch: bf16 2 groups of 4 waves on alternating frames; fp32 8 waves on one
-// frame (lnc3_body_f32)
-template <typename T> constexpr int lnc3_threads() { return sizeof(T) == 2 ? 256 * lnc3_groups<T>() : 512; }
+// frame (lnc3_body_f32r)
+template <typename T> constexpr int lnc3_threads() { return sizeof(T) == 2 ? 256 * LNC3_GROUPS : 512; }
 
 // fp32 LDS (bytes): Z (fp32 [16 + 1][ZR], row 16 zero), the dact3 tile [16][LD3], the LN sums
 struct Lnc3F32 {
@@ -38,41 +38,40 @@ struct Lnc3F32 {
   static constexpr int D3 = (P3 + 1) * lc3::ZR * 4, RED = D3 + P3 * LD3 * 4, BYTES = RED + 4 * 2 * 4;
 };
 
-// LDS of the body (bytes): the W3 staging / per-group Z + dact3 tiles, then red and comb
-template <typename T> struct Lnc3Lds {
-  static constexpr int VEC = 16 / (int)sizeof(T), LD3 = OC3 + 2 * VEC, LW = K3 + 2 * VEC;
-  static constexpr int G = lnc3_groups<T>();
-  static constexpr int ZB = (P3 + 1) * lc3::ZR * 4, GB = ZB + P3 * LD3 * (int)sizeof(T);
-  static constexpr bool REG = sizeof(T) == 2;
-  // W3 staging (bf16; fp32 loads its fragments from the transposed copy)
-  static constexpr int STG = REG ? OC3 * LW * (int)sizeof(T) : 0;
+// LDS of lnc3_body (bytes).  bf16: the W3 staging / per-group Z + dact3 tiles, then red and
+// comb; fp32: Lnc3F32
+template <typename T> struct Lnc3Lds;
+template <> struct Lnc3Lds<__bf16> {
+  static constexpr int VEC = 16 / (int)sizeof(__bf16), LD3 = OC3 + 2 * VEC, LW = K3 + 2 * VEC;
+  static constexpr int G = LNC3_GROUPS;
+  static constexpr int ZB = (P3 + 1) * lc3::ZR * 4, GB = ZB + P3 * LD3 * (int)sizeof(__bf16);
+  static constexpr int STG = OC3 * LW * (int)sizeof(__bf16);  // W3 staging
   static constexpr int SMEM = STG > G * GB ? STG : G * GB;
   static constexpr int RED = SMEM, COMB = RED + G * 4 * 2 * 4;
-  static constexpr int BYTES = sizeof(T) == 4 ? Lnc3F32::BYTES : COMB + 2 * FLAT * 4;
+  static constexpr int BYTES = COMB + 2 * FLAT * 4;
 };
+template <> struct Lnc3Lds<float> { static constexpr int BYTES = Lnc3F32::BYTES; };
 
-// The kernel body, on workgroup `wg` (frames wg*fpw ..) with the LDS passed in
-// (Lnc3Lds<T>::BYTES), so a launch can run it ahead of another per-frame body.
-template <typename T>
-DEV void lnc3_body_g(const float* __restrict__ dy, const T* __restrict__ act3,
-                   const float* __restrict__ stats, const float* __restrict__ gam,
-                   const T* __restrict__ w3, const T* __restrict__ w3t,
-                   const T* __restrict__ act2, T* __restrict__ dact3,
-                   T* __restrict__ dact2, float* __restrict__ slab, int N, int fpw, int wg,
-                   char* __restrict__ lds) {
+// The bf16 kernel body, on workgroup `wg` (frames wg*fpw ..) with the LDS passed in
+// (Lnc3Lds<__bf16>::BYTES), so a launch can run it ahead of another per-frame body.
+DEV void lnc3_body_g(const float* __restrict__ dy, const __bf16* __restrict__ act3,
+                     const float* __restrict__ stats, const float* __restrict__ gam,
+                     const __bf16* __restrict__ w3, const __bf16* __restrict__ act2,
+                     __bf16* __restrict__ dact3, __bf16* __restrict__ dact2,
+                     float* __restrict__ slab, int N, int fpw, int wg, char* __restrict__ lds) {
+  using T = __bf16;
   using F = Frag<T>;
-  typedef typename F::vec V;
+  typedef F::vec V;
   constexpr int KPL = F::KPL, KS = F::KSTEP;
   constexpr int VEC = 16 / (int)sizeof(T);
   constexpr int LD3 = OC3 + 2 * VEC;                 // dact3 row (80 bf16: conflict-free b128 reads)
   constexpr int LW = K3 + 2 * VEC;                   // staged W3 row (bit-2/3 swapped rows)
   constexpr int NKS = K3 / KS;
   constexpr int NKO = OC3 / KS;                      // k-steps per tap (K = oc)
-  constexpr int G = lnc3_groups<T>();
+  constexpr int G = LNC3_GROUPS;
   // one group's LDS: Z (fp32 [16 + 1][ZR]: row 16 stays zero, read by the gather's
   // out-of-range taps) then the dact3 tile (T [16][LD3]), in bytes
   constexpr int ZB = Lnc3Lds<T>::ZB, GB = Lnc3Lds<T>::GB;
-  constexpr bool REG = sizeof(T) == 2;               // bf16: W3 fragments in registers
   static_assert(GB % 16 == 0 && Lnc3Lds<T>::SMEM % 16 == 0, "group alignment");
   char* smem_b = lds;
   float (*red)[4][2] = reinterpret_cast<float (*)[4][2]>(lds + Lnc3Lds<T>::RED);
@@ -106,40 +105,31 @@ DEV void lnc3_body_g(const float* __restrict__ dy, const T* __restrict__ act3,
   for (int q = 0; q < 4; ++q) gm[q] = gam[j0 + q];
 
   // ---- W3 fragments: B[k = oc][n = ci] = W3[oc][tap][ci] of every tap (k-major), held in
-  // registers for the whole frame run (bf16 72, fp32 144 VGPRs) ----
+  // registers for the whole frame run (72 VGPRs), staged through LDS (rows bit-2/3 swapped,
+  // wg_row) and read with the transposing LDS read ----
   V wa[NKS];
-  if constexpr (!REG) {
-    // fp32: 16-byte loads from the transposed copy w3t[tap*64 + ci][oc] (k = oc contiguous),
-    // all 36 in flight at once, consumed in the frame loop
+  constexpr int NV = OC3 * K3 / VEC, NT = 256 * G, NPT = (NV + NT - 1) / NT;
+  V wv[NPT];  // all loads in flight at once, then the LDS stores
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const int k = ks * KS, tap = k >> 6, oc0 = k & 63;
-      wa[ks] = F::load(w3t + (size_t)(tap * OC2 + 16 * wave + (lane & 15)) * OC3 + oc0 + kl);
-    }
-  } else {
-    constexpr int NV = OC3 * K3 / VEC, NT = 256 * G, NPT = (NV + NT - 1) / NT;
-    V wv[NPT];  // all loads in flight at once, then the LDS stores
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-      const int e = (int)threadIdx.x + i * NT;
-      if (e < NV) wv[i] = *reinterpret_cast<const V*>(w3 + (size_t)e * VEC);
-    }
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-      const int e = (int)threadIdx.x + i * NT;
-      if (e < NV) {
-        const int r = e / (K3 / VEC), c = (e % (K3 / VEC)) * VEC;
-        *reinterpret_cast<V*>(smem + wg_row(r) * LW + c) = wv[i];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const int k = ks * KS, tap = k >> 6, oc0 = k & 63;
-      wa[ks] = lds_frag_k_sw(smem + oc0 * LW + tap * OC2 + 16 * wave, LW, lane);
-    }
-    __syncthreads();  // the staging area becomes the Z / dact3 tiles
+  for (int i = 0; i < NPT; ++i) {
+    const int e = (int)threadIdx.x + i * NT;
+    if (e < NV) wv[i] = *reinterpret_cast<const V*>(w3 + (size_t)e * VEC);
   }
+#pragma unroll
+  for (int i = 0; i < NPT; ++i) {
+    const int e = (int)threadIdx.x + i * NT;
+    if (e < NV) {
+      const int r = e / (K3 / VEC), c = (e % (K3 / VEC)) * VEC;
+      *reinterpret_cast<V*>(smem + wg_row(r) * LW + c) = wv[i];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) {
+    const int k = ks * KS, tap = k >> 6, oc0 = k & 63;
+    wa[ks] = lds_frag_k_sw(smem + oc0 * LW + tap * OC2 + 16 * wave, LW, lane);
+  }
+  __syncthreads();  // the staging area becomes the Z / dact3 tiles
   // consume the prologue loads before the loop (see conv1.h: waits merged over the back-edge)
 #pragma unroll
   for (int q = 0; q < 4; ++q) asm volatile("" ::"v"(gm[q]));
@@ -442,7 +432,7 @@ DEV void lnc3_body(const float* __restrict__ dy, const T* __restrict__ act3,
     else
       lnc3_body_f32r<1>(dy, act3, stats, gam, w3t, act2, dact3, dact2, slab, N, fpw, wg, lds, [](int) {});
   } else
-    lnc3_body_g<T>(dy, act3, stats, gam, w3, w3t, act2, dact3, dact2, slab, N, fpw, wg, lds);
+    lnc3_body_g(dy, act3, stats, gam, w3, act2, dact3, dact2, slab, N, fpw, wg, lds);
 }
 
 template <typename T>
@@ -469,7 +459,7 @@ __global__ __launch_bounds__(lnc3_threads<T>()) void lnc3_conv12_bwd(
     float* __restrict__ ln_slab, const uint8_t* __restrict__ x, const T* __restrict__ w2,
     const T* __restrict__ w2t, const uint32_t* __restrict__ mask1,
     float* __restrict__ c1_slab, float* __restrict__ c1_slab_bias, int N, int fpw, const O rm) {
-  static_assert(lnc3_threads<T>() == 256 * c12_groups<T>(), "one block shape for both bodies");
+  static_assert(lnc3_threads<T>() == 256 * C12_GROUPS, "one block shape for both bodies");
   constexpr int B1 = Lnc3Lds<T>::BYTES, B2 = C12BLds<T>::BYTES;
   __shared__ __attribute__((aligned(16))) char lds[B1 > B2 ? B1 : B2];
   if constexpr (sizeof(T) == 4) {

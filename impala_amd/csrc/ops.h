@@ -297,6 +297,21 @@ template <typename T> struct Conv2Wgrad {  // m = (n, oy, ox) in N*36; c = (kh*4
   }
 };
 
+// FC forward tiles (gemm_tile<FcFwd>: BR hidden units x BC frames, K chunk BK, NW waves).
+// bf16: 32 x 32 tiles on 4 waves, 320 workgroups at N = 1280 (5.9 vs 6.7 us for 64 x 32).
+// fp32: 16 x 80 tiles whose 8 waves split each chunk's k-steps (gemm_tile_body KW; K chunk 128 =
+// one k-step per wave per chunk): 256 tiles at N = 1280, one per CU, two waves per SIMD (the
+// 32 x 32 tiles put two on 64 CUs, whose MFMA time bounds the kernel; 32 x 48 on 4 / 8 waves:
+// 12.3 / 11.7 us, 16 x 80 on 8: 11.4 us; profiles/r05kw), and two K chunks held in registers
+// ahead of the MFMAs (PF 1: 13.97 us, 2: 13.40, on the 32 x 32 tiles; a second accumulator
+// chain per fragment lost at either, 14.20 / 13.67-13.69; profiles/r04v).  PF keeps the
+// summation order, so the output bits do not depend on it.
+template <typename T> struct FcFwdCfg {
+  static constexpr bool KW = sizeof(T) == 4;
+  static constexpr int BR = KW ? 16 : 32, BC = KW ? 80 : 32, BK = KW ? 128 : 256;
+  static constexpr int NW = KW ? 8 : 4, PF = KW ? 2 : 1;
+};
+
 // FC weight gradient and FC input gradient in ONE launch.  Both read only dz (with y / Wfc), so
 // they are independent: blocks [0, gx*gy*gz) run the split weight-gradient body (gemm_wg, G
 // 4-wave groups) and the rest run the input-gradient tiles (gemm_tile with 4*G waves: 64 x 64
@@ -313,13 +328,11 @@ template <typename T> struct Conv2Wgrad {  // m = (n, oy, ox) in N*36; c = (kh*4
 // workgroups (192 at the same 6 splits), 78 KB: 512 workgroups, two per CU (8.4 -> 6.8 us)
 // With the weight-gradient loop's staging offsets advanced instead of recomputed (gemm.h):
 // fp32 17.89 -> 17.49 us, bf16 7.31 -> 7.23 (profiles/wgloop, parent -> this tree)
-constexpr int FCB_DR32 = 64, FCB_DC32 = 80, FCB_DWR32 = 4, FCB_DWC32 = 1;
-constexpr int FCB_WBC32 = 128;
 template <typename T, int G> struct FcBwdCfg {
-  static constexpr int DR = G == 2 ? 64 : FCB_DR32, DWR = G == 2 ? 2 : FCB_DWR32;
-  static constexpr int DC = G == 2 ? 64 : FCB_DC32, DWC = G == 2 ? 4 : FCB_DWC32;
+  static constexpr int DR = 64, DWR = G == 2 ? 2 : 4;
+  static constexpr int DC = G == 2 ? 64 : 80, DWC = G == 2 ? 4 : 1;
   static constexpr int DBK = sizeof(T) == 2 ? 128 : 64;
-  static constexpr int WBC = G == 2 ? 128 : FCB_WBC32;
+  static constexpr int WBC = 128;
   static constexpr int SW = gemm_wg_smem<T, 64, WBC, 32, G>();
   static constexpr int SD = gemm_tile_smem<T, DR, DC, DBK, DWR, DWC, FcDgrad<T>>();
   static constexpr int SMEM = SW > SD ? SW : SD;

@@ -1,5 +1,5 @@
 // Probe: the fp32 FC forward (Linear 1024 -> 256 + GELU at N = 1280) in the library's KW tile
-// GEMM (gemm_tile<float, BR, BC, 128, 2, 4, FcFwd<float>, PF 2, KACC 1, KW>: 8 waves split each
+// GEMM (gemm_tile<float, BR, BC, 128, 2, 4, FcFwd<float>, PF 2, KW>: 8 waves split each
 // K chunk's k-steps) over several BR x BC tile shapes, 300 launches each, outputs compared
 // bitwise with the library's 16 x 80 shape (the KW sum order does not depend on the tile).
 //   hipcc -O3 --offload-arch=gfx950 -std=c++17 -I impala_amd/csrc tools/probe/fc_tiles.hip -o tools/probe/fc_tiles
@@ -14,7 +14,7 @@
 
 template <int BR, int BC>
 static void run(const FcFwd<float>& op, int N, int reps, float* dh, std::vector<float>& ref, bool first) {
-  auto k = gemm_tile<float, BR, BC, 128, 2, 4, FcFwd<float>, 2, 1, true>;
+  auto k = gemm_tile<float, BR, BC, 128, 2, 4, FcFwd<float>, 2, true>;
   const long tiles = (long)((N + BC - 1) / BC) * (HID / BR);
   const int grid = (int)(tiles < 768 ? tiles : 768);
   for (int i = 0; i < 20; ++i) k<<<grid, 512>>>(op, HID / BR);

@@ -1,5 +1,5 @@
 # s_memtime stamps of the two-group fp32 conv12 backward body after the k-split weight gradient
-# (C12B32::WKS), workgroup 0: group A wave 0 (thread 0) per frame: top / before the barrier;
+# (conv12_bwd_body_f32 group B), workgroup 0: group A wave 0 (thread 0) per frame: top / before the barrier;
 # group B wave 4 (thread 256) per step: top / weight gradient done (before its LDS staging
 # stores).  One "PP" line: clocks from the body's start.
 C = "conv1.h"
