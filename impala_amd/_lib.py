@@ -73,6 +73,18 @@ SAC_EXPORTS = (
     "sac_timer_start", "sac_timer_read", "sac_sample",
 )
 SAC_NUM_METRICS = 12
+# every symbol declared in include/dqn_hip.h
+DQN_EXPORTS = (
+    "dqn_abi_version", "dqn_last_error", "dqn_config_default", "dqn_param_count", "dqn_create",
+    "dqn_destroy", "dqn_bind_state", "dqn_bind_target", "dqn_sync_target", "dqn_refresh_weights",
+    "dqn_set_step", "dqn_set_metrics", "dqn_set_metrics_host", "dqn_forward", "dqn_act",
+    "dqn_train_step", "dqn_loss_head",
+)
+DQN_ABI_VERSION = 1
+DQN_NUM_METRICS = 9
+# ApexLearner metric keys (agents/dqn/learning.py:185-190) -> metrics slot (DQN_M_*)
+DQN_METRIC_SLOTS = (("train_step/q", 0), ("train_step/target", 1), ("train_step/priorities", 2),
+                    ("train_step/loss", 3), ("train_step/grad_norm", 6))
 # SACLearner metric keys (agents/sac/learning.py:206,220,243-265) -> metrics slot
 SAC_CRITIC_METRICS = (("train/qf1_loss", 0), ("train/qf2_loss", 1), ("train/qf1", 2),
                       ("train/qf2", 3), ("train/qf_loss", 4), ("train/critic_grad_norm", 5))
@@ -123,6 +135,18 @@ class SacBatch(C.Structure):
     _fields_ = [("s", C.c_void_p), ("a", C.c_void_p), ("r", C.c_void_p), ("s1", C.c_void_p),
                 ("done", C.c_void_p), ("probabilities", C.c_void_p), ("noise", C.c_void_p),
                 ("priorities", C.c_void_p)]
+
+
+class DqnConfig(C.Structure):
+    _fields_ = [("batch_size", C.c_int), ("num_actions", C.c_int), ("dtype", C.c_int),
+                ("lr", C.c_float), ("adam_beta1", C.c_float), ("adam_beta2", C.c_float),
+                ("adam_eps", C.c_float), ("max_grad_norm", C.c_float),
+                ("importance_sampling_exponent", C.c_float)]
+
+
+class DqnBatch(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("targets", C.c_void_p),
+                ("probabilities", C.c_void_p), ("priorities", C.c_void_p)]
 
 
 class SacState(C.Structure):
@@ -214,6 +238,26 @@ def _declare(lib):
     lib.sac_timer_read.argtypes = [_P, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     lib.sac_sample.argtypes = [C.c_uint64, C.c_uint64, C.c_int64, C.c_int, _P, _P,
                                C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t), C.c_int, _P]
+    lib.dqn_config_default.argtypes = [C.POINTER(DqnConfig)]
+    lib.dqn_param_count.argtypes = [C.c_int]
+    lib.dqn_create.argtypes = [C.POINTER(DqnConfig), C.c_int, C.POINTER(_P)]
+    lib.dqn_destroy.argtypes = [_P]
+    lib.dqn_bind_state.argtypes = [_P, _P, _P, _P, _P, _P, _P]
+    lib.dqn_bind_target.argtypes = [_P, _P, _P]
+    lib.dqn_sync_target.argtypes = [_P, _P]
+    lib.dqn_refresh_weights.argtypes = [_P, _P]
+    lib.dqn_set_step.argtypes = [_P, C.c_int64, _P]
+    lib.dqn_set_metrics.argtypes = [_P, _P]
+    lib.dqn_set_metrics_host.argtypes = [_P, _P]
+    lib.dqn_forward.argtypes = [_P, _P, C.c_int, C.c_int, _P, _P]
+    lib.dqn_act.argtypes = [_P, _P, C.c_int, _P, C.c_float, C.c_uint64, C.c_uint64, _P, _P, _P,
+                            _P, _P]
+    lib.dqn_train_step.argtypes = [_P, C.POINTER(DqnBatch), _P]
+    lib.dqn_loss_head.argtypes = [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P,
+                                  _P]
+    for name in DQN_EXPORTS:
+        getattr(lib, name).restype = (C.c_char_p if name == "dqn_last_error" else
+                                      C.c_size_t if name == "dqn_param_count" else C.c_int)
     for name in SAC_EXPORTS:
         if name in ("sac_actor_param_count", "sac_critic_param_count"):
             getattr(lib, name).restype = C.c_size_t

@@ -22,8 +22,8 @@ def sources():
 
 
 def hip_units():
-    """The translation units linked into the one library (impala.hip: IMPALA / PPO learner,
-    sac.hip: SAC learner)."""
+    """The translation units linked into the one library (impala.hip: IMPALA / PPO learner and,
+    through csrc/dqn.h on the same launchers, the Ape-X DQN learner; sac.hip: SAC learner)."""
     return [os.path.join(SRC_DIR, f) for f in ("impala.hip", "sac.hip")]
 
 

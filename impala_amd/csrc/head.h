@@ -2,7 +2,7 @@
 // (agents/impala/learning.py:144-170), the heads' input gradient through GELU (dz) and the
 // heads' weight-gradient partial -- one workgroup per group of whole trajectories.
 //
-//   phase 1  stage h[F][256] of the group's F frames in LDS; heads = Wh . h + bh (MFMA)
+//   phase 1  stage h[F][HID] of the group's F frames in LDS; heads = Wh . h + bh (MFMA)
 //   phase 2a all four waves, a quad of threads per frame, four actions per thread: log-softmax
 //            of the policy and behaviour logits, entropy, KL, log pi(a), rho (quad DPP sums)
 //   phase 2b wave 0, one lane per (trajectory, t) = one frame: the V-trace in the reference's
@@ -32,10 +32,10 @@ DEV float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994
 
 struct HeadArgs {
   // phase 1 inputs
-  const void* h;      // T [N][256]
-  const float* zg;    // [N][256] gelu'(pre-GELU), from the FC forward
-  const void* wh;     // T [16][256]
-  const void* wht;    // T [256][32]
+  const void* h;      // T [N][HID]
+  const float* zg;    // [N][HID] gelu'(pre-GELU), from the FC forward
+  const void* wh;     // T [16][HID]
+  const void* wht;    // T [HID][32]
   const float* bh;    // [16]
   // batch
   const int64_t* act; const float* rew; const float* disc; const float* mu;
@@ -44,9 +44,9 @@ struct HeadArgs {
   float lam, crho, cpg, ent_coef;
   float clip_lo, clip_hi;  // PPO: ratio clamp bounds (1 -+ clip_coeff)
   // outputs
-  void* dz;             // T [N][256]
+  void* dz;             // T [N][HID]
   float* partials;      // [gridDim.x][8] loss partial sums
-  float* slab_h;        // [gridDim.x][16][256]
+  float* slab_h;        // [gridDim.x][16][HID]
   float* slab_bh;       // [gridDim.x][16]
   float* heads_out;     // optional [N][16] (logits + value), nullptr = skip
   float* vt_dbg;        // optional debug export (IMPALA only): adv, err, q [3][B][T-1] then
@@ -64,7 +64,9 @@ template <typename T> constexpr int head_split() { return sizeof(T) == 4 ? 8 : 4
 // L2 hit and the loss is one wavefront), then each takes a 64-column slice of dz / dWh.
 // PPO = true: the PPO clipped-surrogate loss (kernels.h::ppo_frame) on flat transitions (T = 1,
 // one lane per transition, targets in `rew`, `disc` unused) instead of V-trace.
-template <typename T, bool PPO = false, class O = ObsDirect>
+// HID: the projection width (the actor-critic's 256: the phase 3 / 4 wave map below covers 32-
+// and 64-column slices; the 512-wide dueling head has its own kernel, dqn_head.h).
+template <typename T, bool PPO = false, class O = ObsDirect, int HID = HID_AC>
 __global__ __launch_bounds__(256) void head_step_kernel(const HeadArgs a, const O fm) {
   constexpr int HEAD_JC = HID / head_split<T>();  // hidden columns per workgroup in phases 3/4
   static_assert(HEAD_JC == 64 || HEAD_JC == 32, "phase 3 / 4 wave map");
@@ -79,7 +81,7 @@ __global__ __launch_bounds__(256) void head_step_kernel(const HeadArgs a, const 
   __shared__ float lg_s[64][HEADS + 1];
   __shared__ __attribute__((aligned(16))) float zs[64 * (HEAD_JC + 4)];  // z slice (phase 3)
   __shared__ float bred[4][HEADS];
-  // the heads weights [16][256 + VEC], staged once per workgroup (each wave used to load all 16
+  // the heads weights [16][HID + VEC], staged once per workgroup (each wave used to load all 16
   // KB of fragments itself: 64 KB of the ~155 KB a workgroup loaded, headstamps4 r04c)
   __shared__ __attribute__((aligned(16))) T whs[HEADS * LDH];
   __shared__ f32x4 fst[64];    // per frame: H, KL, log pi(a), rho (phase 2a -> 2b)
@@ -329,7 +331,7 @@ __global__ __launch_bounds__(256) void head_step_kernel(const HeadArgs a, const 
     }
   }
   __syncthreads();
-  // ---- phase 3: dz = gelu'(z) * (dH . Wh)   rows j (256: wave w -> 4 row tiles), cols f ----
+  // ---- phase 3: dz = gelu'(z) * (dH . Wh)   rows j (HID: wave w -> 4 row tiles), cols f ----
   {
     T* dz = reinterpret_cast<T*>(a.dz);
     {

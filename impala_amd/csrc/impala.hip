@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/impala_hip.h"
+#include "dqn_head.h"
 #include "head.h"
 #include "hostpool.h"
 #include "kernels.h"
@@ -44,7 +45,11 @@ int fail(int code, const std::string& msg) {
 // shared with the SAC translation unit (sac.hip): one last-error slot per thread for the library
 namespace impala_internal {
 int set_error(int code, const std::string& msg) { return fail(code, msg); }
+// cfg->algo of the handle behind a dqn_learner (never accepted by impala_create)
+constexpr int ALGO_DQN = 2;
+int create_learner(const impala_config* cfg, int device, int hid, impala_learner** out);
 }  // namespace impala_internal
+using impala_internal::ALGO_DQN;
 
 namespace {
 
@@ -112,6 +117,7 @@ struct impala_learner {
   int N = 0;  // frames per step = B * T
   int A = 15;
   bool bf16 = false;
+  int hid = net::HID_AC;  // projection width: the launchers' HID instantiation (BY_NET)
   net::Canon cn;
   net::Shadow sh;
   // caller-owned (bound)
@@ -147,6 +153,9 @@ struct impala_learner {
   int c1_fpw = 1, c1_wg = 1;  // conv1 wgrad: frames per workgroup, workgroups (= splits)
   int c12f_fpw = 0;           // conv1+conv2 forward frames per workgroup (0: N / CUs)
   float* vt_dbg = nullptr;    // impala_set_debug_vtrace: the step's V-trace outputs
+  // DQN handles (dqn.h): the step's priorities output and the importance-sampling exponent
+  float* dqn_prio = nullptr;
+  float dqn_beta = 0.4f;
   // live launch timer (impala_timer_*): per kernel id, event pairs handed to
   // hipExtLaunchKernel, which stamps the kernel's own start / end (as rocprofv3 does)
   struct KTimer {
@@ -247,10 +256,18 @@ unsigned long long* step_stamp(impala_learner* h) {
   return h->clock_buf && h->clock_i < h->clock_n ? h->clock_buf + h->clock_i++ : nullptr;
 }
 
-template <typename T>
+// The launchers are instantiated per compute type and projection width; BY_NET picks the
+// handle's instantiation.
+#define BY_NET(h, fn, ...)                                                                   \
+  ((h)->hid == net::HID_DQN                                                                  \
+       ? ((h)->bf16 ? fn<__bf16, net::HID_DQN>(__VA_ARGS__) : fn<float, net::HID_DQN>(__VA_ARGS__)) \
+       : ((h)->bf16 ? fn<__bf16, net::HID_AC>(__VA_ARGS__) : fn<float, net::HID_AC>(__VA_ARGS__)))
+
+template <typename T, int HID>
 int launch_forward(impala_learner* h, const uint8_t* obs, int n, hipStream_t st,
                    bool with_heads) {
   using namespace net;
+  using Vecs = VecsT<HID>;
   // K chunk of the LDS-staged tile GEMM: long chunks (few, each a full memory round trip) for
   // bf16; fp32 at most 64 (round-3 A/B: 32 -> 64 cut fc_fwd 18.2 -> 14.0 us and
   // conv3_fwd 28.3 -> 27.0 us; 128 / 256 lost on conv3_fwd's LDS footprint)
@@ -302,17 +319,17 @@ int launch_forward(impala_learner* h, const uint8_t* obs, int n, hipStream_t st,
       return r;
   }
   {
-    FcFwd<T> op{n, sw + sh.wfc, vv + Vecs::bfc, (const T*)h->y, h->zg, (T*)h->h};
+    FcFwd<T, HID> op{n, sw + sh.wfc, vv + Vecs::bfc, (const T*)h->y, h->zg, (T*)h->h};
     using C = FcFwdCfg<T>;
     if (int r = klaunch(h, K_FC_FWD, "fc_fwd",
-                        gemm_tile<T, C::BR, C::BC, C::BK, 2, C::NW / 2, FcFwd<T>, C::PF, C::KW>,
+                        gemm_tile<T, C::BR, C::BC, C::BK, 2, C::NW / 2, FcFwd<T, HID>, C::PF, C::KW>,
                         dim3(persist_grid(h, (long)cdiv(n, C::BC) * (HID / C::BR))), dim3(64 * C::NW), st,
                         op, HID / C::BR))
       return r;
   }
   if (with_heads) {  // inference; in training the fused head kernel computes the heads
-    HeadsFwd<T> op{n, sw + sh.wh, vv + Vecs::bh, (const T*)h->h, h->heads};
-    if (int r = klaunch(h, K_HEADS_FWD, "heads_fwd", gemm_rc<T, 1, 1, HeadsFwd<T>>,
+    HeadsFwd<T, HID> op{n, sw + sh.wh, vv + Vecs::bh, (const T*)h->h, h->heads};
+    if (int r = klaunch(h, K_HEADS_FWD, "heads_fwd", gemm_rc<T, 1, 1, HeadsFwd<T, HID>>,
                         dim3(cdiv(n, 64), 1), dim3(256), st, op))
       return r;
   }
@@ -322,9 +339,10 @@ int launch_forward(impala_learner* h, const uint8_t* obs, int n, hipStream_t st,
 // slab-reduction segment groups (indices into RedArgs::seg, in the order create() adds them)
 enum { RS_CONV1 = 0, RS_CONV2 = 2, RS_CONV3 = 4, RS_LN = 6, RS_FC = 7, RS_END = 11 };
 
+template <int HID>
 int reduce_segments(impala_learner* h, int s_lo, int s_hi, hipStream_t st, int fin) {
   const int n = h->red.wg_start[s_hi] - h->red.wg_start[s_lo];
-  return klaunch(h, K_REDUCE, "reduce_grads", reduce_grads_kernel, dim3(n), dim3(256), st, h->red,
+  return klaunch(h, K_REDUCE, "reduce_grads", reduce_grads_kernel<HID>, dim3(n), dim3(256), st, h->red,
                  s_lo, fin);
 }
 
@@ -360,8 +378,12 @@ const BwdPart* bwd_part(int part) {
 }
 
 template <typename T>
+int launch_dqn_head(impala_learner* h, const impala_batch* b, hipStream_t st);
+
+template <typename T, int HID>
 int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, const BwdPart* bp) {
   using namespace net;
+  using Vecs = VecsT<HID>;
   const int N = h->N, B = h->cfg.batch_size, Tl = h->cfg.rollout_length;
   const T* sw = reinterpret_cast<const T*>(h->shadow);
   const Shadow& sh = h->sh;
@@ -397,7 +419,9 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, co
     ha.clip_lo = (float)(1.0 - (double)h->cfg.ppo_clip);
     ha.clip_hi = (float)(1.0 + (double)h->cfg.ppo_clip);
     const dim3 hg(h->n_loss_wg, head_split<T>());
-    if (int r = h->cfg.algo == IMPALA_ALGO_PPO
+    if constexpr (HID == HID_DQN) {  // the dueling head in head_step's slot (dqn_head.h)
+      if (int r = launch_dqn_head<T>(h, b, st)) return r;
+    } else if (int r = h->cfg.algo == IMPALA_ALGO_PPO
                     ? klaunch(h, K_HEAD_STEP, "head_step", head_step_kernel<T, true>, hg, dim3(256), st, ha,
                               ObsDirect{})
                     : h->rows_on
@@ -406,22 +430,22 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, co
                     : klaunch(h, K_HEAD_STEP, "head_step", head_step_kernel<T, false>, hg, dim3(256), st, ha,
                               ObsDirect{}))
       return r;
-    FcWgrad<T> ow{};
+    FcWgrad<T, HID> ow{};
     ow.M = N; ow.x = (const T*)h->dz; ow.y = (const T*)h->y;
-    FcDgrad<T> od{N, sw + sh.wfc, (const T*)h->dz, h->dy};
+    FcDgrad<T, HID> od{N, sw + sh.wfc, (const T*)h->dz, h->dy};
     if (h->fc_merged) {  // both in one launch
-      using C = FcBwdCfg<T, WG2>;
+      using C = FcBwdCfg<T, WG2, HID>;
       const int gx = FLAT / C::WBC, gy = HID / 64, gz = h->spfc.S;
       const int n_rt = FLAT / C::DR, n_dt = n_rt * cdiv(N, C::DC);
-      return klaunch(h, K_FC_BWD, "fc_wgrad_fc_dgrad", fc_bwd_kernel<T, WG2>,
+      return klaunch(h, K_FC_BWD, "fc_wgrad_fc_dgrad", fc_bwd_kernel<T, WG2, HID>,
                      dim3(gx * gy * gz + n_dt), dim3(256 * WG2), st, ow, h->s_fc, h->s_bfc,
                      h->spfc.mps, gx, gy, gz, od, n_rt);
     }
-    if (int r = klaunch(h, K_FC_WGRAD, "fc_wgrad", gemm_wg<T, 64, 256, 1, 4, 32, WG2, FcWgrad<T>>,
+    if (int r = klaunch(h, K_FC_WGRAD, "fc_wgrad", gemm_wg<T, 64, 256, 1, 4, 32, WG2, FcWgrad<T, HID>>,
                         dim3(FLAT / 256, HID / 64, h->spfc.S), dim3(256 * WG2), st, ow, h->s_fc,
                         h->s_bfc, h->spfc.mps))
       return r;
-    return klaunch(h, K_FC_DGRAD, "fc_dgrad", gemm_tile<T, 64, 64, BK(128), 2, 2, FcDgrad<T>>,
+    return klaunch(h, K_FC_DGRAD, "fc_dgrad", gemm_tile<T, 64, 64, BK(128), 2, 2, FcDgrad<T, HID>>,
                    dim3(persist_grid(h, (long)cdiv(N, 64) * (FLAT / 64))), dim3(256), st, od,
                    FLAT / 64);
   };
@@ -507,10 +531,10 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, co
     }
     if (r) return r;
   }
-  return reduce_segments(h, bp->red_lo, bp->red_hi, st, bp->fin);
+  return reduce_segments<HID>(h, bp->red_lo, bp->red_hi, st, bp->fin);
 }
 
-template <typename T>
+template <typename T, int HID>
 int launch_adam(impala_learner* h, hipStream_t st) {
   AdamArgs aa{};
   aa.params = h->params; aa.grads = h->grads; aa.m = h->exp_avg; aa.v = h->exp_avg_sq;
@@ -524,13 +548,13 @@ int launch_adam(impala_learner* h, hipStream_t st) {
   aa.cn = h->cn; aa.sh = h->sh;
   // HID blocks for the FC weight rows, then the other parameters (adam_kernel)
   const long rest = (long)h->cn.total - (long)(h->cn.bfc - h->cn.wfc);
-  return klaunch(h, K_ADAM, "adam", adam_kernel<T>, dim3(net::HID + cdiv(rest, 256)),
+  return klaunch(h, K_ADAM, "adam", adam_kernel<T, HID>, dim3(HID + cdiv(rest, 256)),
                  dim3(256), st, aa);
 }
 
-template <typename T>
+template <typename T, int HID>
 int launch_pack(impala_learner* h, hipStream_t st) {
-  pack_params_kernel<T><<<cdiv((long)h->cn.total, 256), 256, 0, st>>>(h->params, ShadowPtrs{h->shadow, h->vecs, h->A},
+  pack_params_kernel<T, HID><<<cdiv((long)h->cn.total, 256), 256, 0, st>>>(h->params, ShadowPtrs{h->shadow, h->vecs, h->A},
                                                      h->cn, h->sh);
   CK_LAUNCH("pack_params");
   return 0;
@@ -679,6 +703,18 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
   if (cfg->dtype != IMPALA_DTYPE_F32 && cfg->dtype != IMPALA_DTYPE_BF16)
     return fail(IMPALA_E_INVALID, "unknown dtype");
   if (cfg->world_size < 1) return fail(IMPALA_E_INVALID, "world_size must be >= 1");
+  return impala_internal::create_learner(cfg, device, net::HID_AC, out);
+}
+
+extern "C++" {
+// The handle behind impala_create, and behind dqn_create (dqn.h) with the 512-wide projection and
+// cfg->algo = ALGO_DQN (flat transitions, rollout_length 1).  The configuration is the caller's
+// to validate.
+int impala_internal::create_learner(const impala_config* cfg, int device, int hid,
+                                    impala_learner** out) {
+  using namespace net;
+  const int HID = hid;
+  const bool dqn = cfg->algo == ALGO_DQN;
   CK(hipSetDevice(device));
   impala_learner* h = new (std::nothrow) impala_learner();
   if (!h) return fail(IMPALA_E_INVALID, "out of host memory");
@@ -693,12 +729,14 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
         cu > 0)
       h->n_cu = cu;
   }
-  h->cn = canon(h->A);
-  h->sh = shadow();
+  h->hid = hid;
+  h->cn = hid == HID_DQN ? canon_dqn(h->A) : canon(h->A);
+  h->sh = hid == HID_DQN ? shadow_dqn() : shadow();
   const int N = h->N;
   const size_t es = h->bf16 ? 2 : 4;
   h->S_seg = next_pow2(cfg->rollout_length);
   h->n_loss_wg = cdiv(cfg->batch_size, 64 / h->S_seg);  // fused head: 64/S trajectories per WG
+  if (dqn) h->n_loss_wg = cdiv(N, DQN_F);               // dueling head: DQN_F transitions per WG
   if (const char* lf = std::getenv("IMPALA_LNC3_FUSED")) h->lnc3_fused = lf[0] != '0';
   if (h->lnc3_fused) {  // frames per workgroup of the fused kernel (one slab each)
     h->ln_fpw = std::max(1, cdiv(N, h->n_cu));
@@ -738,7 +776,7 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
     return o;
   };
   const size_t o_shadow = take(h->sh.total * es);
-  const size_t o_vecs = take(Vecs::total * 4);
+  const size_t o_vecs = take((hid == HID_DQN ? VecsDqn::total : Vecs::total) * 4);
   const size_t o_act1 = take((size_t)N * P1 * OC1 * es);
   const size_t o_act2 = take((size_t)N * P2 * OC2 * es);
   const size_t o_act3 = take((size_t)N * FLAT * es);
@@ -857,6 +895,7 @@ int impala_create(const impala_config* cfg, int device, impala_learner** out) {
   *out = h;
   return 0;
 }
+}  // extern "C++"
 
 extern "C++" {
 namespace {
@@ -985,7 +1024,7 @@ int impala_refresh_weights(impala_learner* h, void* stream) {
   if (int r = check_bound(h, false)) return r;
   CK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  return h->bf16 ? launch_pack<__bf16>(h, st) : launch_pack<float>(h, st);
+  return BY_NET(h, launch_pack, h, st);
 }
 
 int impala_set_step(impala_learner* h, int64_t step, void* stream) {
@@ -1007,8 +1046,7 @@ int impala_forward(impala_learner* h, const uint8_t* obs, int n, float* logits, 
   if (((uintptr_t)obs & 15) != 0) return fail(IMPALA_E_INVALID, "obs must be 16-byte aligned");
   CK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  int r = h->bf16 ? launch_forward<__bf16>(h, obs, n, st, true)
-                  : launch_forward<float>(h, obs, n, st, true);
+  int r = BY_NET(h, launch_forward, h, obs, n, st, true);
   if (r) return r;
   split_heads_kernel<<<cdiv((long)n * net::HEADS, 256), 256, 0, st>>>(h->heads, n, h->A, logits,
                                                                        values);
@@ -1025,8 +1063,7 @@ int impala_act(impala_learner* h, const uint8_t* obs, int n, const uint8_t* dete
   if (((uintptr_t)obs & 15) != 0) return fail(IMPALA_E_INVALID, "obs must be 16-byte aligned");
   CK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  int r = h->bf16 ? launch_forward<__bf16>(h, obs, n, st, true)
-                  : launch_forward<float>(h, obs, n, st, true);
+  int r = BY_NET(h, launch_forward, h, obs, n, st, true);
   if (r) return r;
   act_heads_kernel<<<cdiv(n, 256), 256, 0, st>>>(h->heads, n, h->A, deterministic,
                                                  deterministic_all, seed, counter, actions,
@@ -1041,11 +1078,10 @@ int enqueue_grads(impala_learner* h, const impala_batch* b, hipStream_t st, int 
   const BwdPart* bp = bwd_part(part);
   if (!bp) return fail(IMPALA_E_INVALID, "unknown backward part");
   if (bp->first == BS_HEAD_FC) {  // (the other parts continue a backward)
-    int r = h->bf16 ? launch_forward<__bf16>(h, b->obs, h->N, st, false)
-                    : launch_forward<float>(h, b->obs, h->N, st, false);
+    int r = BY_NET(h, launch_forward, h, b->obs, h->N, st, false);
     if (r) return r;
   }
-  return h->bf16 ? launch_backward<__bf16>(h, b, st, bp) : launch_backward<float>(h, b, st, bp);
+  return BY_NET(h, launch_backward, h, b, st, bp);
 }
 
 int enqueue_update(impala_learner* h, hipStream_t st) {
@@ -1054,7 +1090,7 @@ int enqueue_update(impala_learner* h, hipStream_t st) {
                         (const float*)h->grads, (size_t)h->cn.total, h->sumsq_part))
       return r;
   }
-  return h->bf16 ? launch_adam<__bf16>(h, st) : launch_adam<float>(h, st);
+  return BY_NET(h, launch_adam, h, st);
 }
 
 bool same_batch(const impala_batch& a, const impala_batch& b) {
@@ -1960,3 +1996,6 @@ int impala_ppo_loss_head(const float* logits, const float* values, const int64_t
 }
 
 }  // extern "C"
+
+// the Ape-X DQN entry points (include/dqn_hip.h) on the launchers above
+#include "dqn.h"

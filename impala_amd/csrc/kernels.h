@@ -358,6 +358,21 @@ DEV void finalize_ppo_metrics(const float* part, int nparts, int N, float ent_co
   metrics[8] = s[5] * c;
 }
 
+// metrics from the DQN head's (dqn_head.h) partial sums (q[a], target, |err|, err^2 w): the reference's
+// train_step/{q, target, priorities, loss}; the slots Adam does not write are zeroed.
+// (called by a whole wavefront; lane 0 writes)
+DEV void finalize_dqn_metrics(const float* part, int nparts, int N, float* metrics, int lane,
+                              bool step_vector = true) {
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  sum_partials<4>(part, nparts, lane, s);
+  if (lane != 0) return;
+  const float c = 1.f / (float)N;
+  metrics[0] = s[0] * c;
+  metrics[1] = s[1] * c;
+  metrics[2] = s[2] * c;
+  metrics[3] = 0.5f * (s[3] * c);
+  if (step_vector) metrics[4] = metrics[5] = metrics[8] = 0.f;
+}
 // Standalone PPO loss head on given outputs, one lane per transition (test / reuse entry).
 __global__ __launch_bounds__(256) void ppo_loss_head_kernel(
     const float* __restrict__ logits, const float* __restrict__ values,
@@ -522,8 +537,9 @@ struct ShadowPtrs {
   int A;
 };
 
-template <typename T>
+template <typename T, int HID>
 DEV void write_shadow(const ShadowPtrs& sp, const Canon& cn, const Shadow& sh, size_t i, float p) {
+  using Vecs = VecsT<HID>;
   T* w = reinterpret_cast<T*>(sp.base);
   float* vv = sp.vecs;
   const T pt = (T)p;
@@ -558,7 +574,7 @@ DEV void write_shadow(const ShadowPtrs& sp, const Canon& cn, const Shadow& sh, s
   } else if (i < cn.wa) {
     vv[Vecs::bfc + (i - cn.bfc)] = p;
   } else if (i < cn.ba) {
-    const int k = (int)(i - cn.wa), ar = k >> 8, j = k & 255;
+    const int k = (int)(i - cn.wa), ar = k >> hid_log2<HID>(), j = k & (HID - 1);
     w[sh.wh + ar * HID + j] = pt;
     w[sh.wht + j * HPAD + ar] = pt;
   } else if (i < cn.wc) {
@@ -572,11 +588,11 @@ DEV void write_shadow(const ShadowPtrs& sp, const Canon& cn, const Shadow& sh, s
   }
 }
 
-template <typename T>
+template <typename T, int HID>
 __global__ __launch_bounds__(256) void pack_params_kernel(const float* __restrict__ params,
                                                           ShadowPtrs sp, Canon cn, Shadow sh) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < cn.total) write_shadow<T>(sp, cn, sh, i, params[i]);
+  if (i < cn.total) write_shadow<T, HID>(sp, cn, sh, i, params[i]);
 }
 
 // =========================================================================================
@@ -610,7 +626,7 @@ struct RedArgs {
   float* adam_sc;     // [2]: lr / (1 - b1^t), sqrt(1 - b2^t)
 };
 
-DEV long long canon_index(const RedArgs& a, const RedSeg& sg, int k) {
+template <int HID> DEV long long canon_index(const RedArgs& a, const RedSeg& sg, int k) {
   switch (sg.kind) {
     case RK_CONV1: {  // k = oc*192 + k' (s2d order)  ->  oc*192 + ci*64 + kh*8 + kw
       const int oc = k / K1;
@@ -632,8 +648,8 @@ DEV long long canon_index(const RedArgs& a, const RedSeg& sg, int k) {
       const int o = k >> 10, j = k & 1023, p = j >> 6, c = j & 63;
       return sg.canon + (long long)o * FLAT + c * 16 + p;
     }
-    case RK_HEADS_W: {  // k = row*256 + j; rows 0..A-1 actor, row 15 critic, else padding
-      const int row = k >> 8, j = k & 255;
+    case RK_HEADS_W: {  // k = row*HID + j; rows 0..A-1 actor, row 15 critic, else padding
+      const int row = k >> hid_log2<HID>(), j = k & (HID - 1);
       if (row < a.A) return (long long)a.cn.wa + row * HID + j;
       if (row == VCOL) return (long long)a.cn.wc + j;
       return -1;
@@ -709,6 +725,7 @@ DEV f32x4 reduce_unit_sum(const RedArgs& a, const RedUnit& r) {
   }
   return acc;
 }
+template <int HID>
 DEV float reduce_unit_finish(const RedArgs& a, const RedUnit& r, const f32x4* part, f32x4& acc,
                              long long (&ci)[4]) {
   float sq = 0.f;
@@ -719,18 +736,19 @@ DEV float reduce_unit_finish(const RedArgs& a, const RedUnit& r, const f32x4* pa
     const int k = r.v4 * 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      ci[i] = canon_index(a, a.seg[r.s], k + i);
+      ci[i] = canon_index<HID>(a, a.seg[r.s], k + i);
       if (ci[i] >= 0) sq += acc[i] * acc[i];
     }
   }
   return sq;
 }
+template <int HID>
 DEV float reduce_unit(const RedArgs& a, int wg, f32x4* part, f32x4& acc, long long (&ci)[4]) {
   const RedUnit r = reduce_unit_at(a, wg, (int)threadIdx.x);
   acc = reduce_unit_sum(a, r);
   part[threadIdx.x] = acc;
   __syncthreads();
-  return reduce_unit_finish(a, r, part, acc, ci);
+  return reduce_unit_finish<HID>(a, r, part, acc, ci);
 }
 
 // Each segment is processed by workgroups of 256 threads = (256/SG) float4 columns x SG
@@ -740,13 +758,14 @@ DEV float reduce_unit(const RedArgs& a, int wg, f32x4* part, f32x4& acc, long lo
 // each weight-gradient branch can be reduced as soon as its slab is complete; the workgroup's
 // global index (wg_start[s_lo] + blockIdx.x) names its sum-of-squares partial, so the partial
 // order -- and the norm -- does not depend on how the segments were grouped into launches.
+template <int HID>
 __global__ __launch_bounds__(256) void reduce_grads_kernel(const RedArgs a, int s_lo, int fin) {
   __shared__ f32x4 part[256];
   __shared__ float red[4];
   const int wg = a.wg_start[s_lo] + (int)blockIdx.x;
   f32x4 acc;
   long long ci[4];
-  float sq = reduce_unit(a, wg, part, acc, ci);
+  float sq = reduce_unit<HID>(a, wg, part, acc, ci);
 #pragma unroll
   for (int i = 0; i < 4; ++i)
     if (ci[i] >= 0) a.grads[ci[i]] = acc[i];
@@ -755,7 +774,9 @@ __global__ __launch_bounds__(256) void reduce_grads_kernel(const RedArgs a, int 
   __syncthreads();
   if (threadIdx.x == 0) a.sumsq_part[wg] = red[0] + red[1] + red[2] + red[3];
   if (fin && blockIdx.x == 0 && (threadIdx.x >> 6) == 1) {  // wave 1
-    if (a.algo == 1)
+    if constexpr (HID == HID_DQN)  // (the 512-wide instantiation serves the DQN handle alone)
+      finalize_dqn_metrics(a.loss_part, a.n_loss_part, a.B * a.T, a.metrics, threadIdx.x & 63);
+    else if (a.algo == 1)
       finalize_ppo_metrics(a.loss_part, a.n_loss_part, a.B * a.T, a.ent_coef, a.metrics, threadIdx.x & 63);
     else
       finalize_loss_metrics(a.loss_part, a.n_loss_part, a.B, a.T, a.ent_coef, a.metrics, threadIdx.x & 63);
@@ -825,7 +846,7 @@ DEV void adam_elem(const AdamArgs& a, float gscale, float step_size, float bc2s,
 // order with the FC rows skipped.
 static_assert((OC1 * K1 + OC1 + OC2 * K2 + OC2 + OC3 * K3 + OC3 + 2 * FLAT) % 4 == 0,
               "adam_kernel: the FC weight rows start float4-aligned in the canonical buffer");
-template <typename T>
+template <typename T, int HID>
 __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
   __shared__ float red[4];
   __shared__ __attribute__((aligned(16))) T fcrow[FLAT];
@@ -923,7 +944,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
     else
       *reinterpret_cast<uint2*>(w) = *reinterpret_cast<const uint2*>(fcrow + 4 * threadIdx.x);
   } else {
-    for (int k = 0; k < n; ++k) write_shadow<T>(a.sp, a.cn, a.sh, i0 + k, p[k]);
+    for (int k = 0; k < n; ++k) write_shadow<T, HID>(a.sp, a.cn, a.sh, i0 + k, p[k]);
   }
 }
 

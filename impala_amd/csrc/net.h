@@ -8,13 +8,18 @@
 //   w1  [32][192]        k' = tap*48 + ci*16 + (kh%4)*4 + kw%4, tap = (kh/4)*2 + kw/4 (s2d)
 //   w2  [64][512]        k = (kh*4+kw)*32 + ci                       (conv2, channels-last)
 //   w3  [64][576]        k = (kh*3+kw)*64 + ci                       (conv3)
-//   wfc [256][1024]      k = p*64 + c   (canonical column j = c*16 + p, NCHW flatten)
-//   wh  [16][256]        rows 0..A-1 actor, row 15 critic, rest 0
+//   wfc [HID][1024]      k = p*64 + c   (canonical column j = c*16 + p, NCHW flatten)
+//   wh  [16][HID]        rows 0..A-1 actor, row 15 critic, rest 0
 // (the dgrads read w2 / w3 / wfc k-major through LDS: no transposed copies)
-//   wht [256][32]        [j][o'], o' >= 16 zero
+//   wht [HID][32]        [j][o'], o' >= 16 zero
 //   w2t [512][64]        [(kh*4+kw)*32 + ci][oc]   (fp32 only: the dgrads' B fragments as one
 //   w3t [576][64]        [(kh*3+kw)*64 + ci][oc]    16-byte load, k = oc contiguous)
-//   f32: b1[32] b2[64] b3[64] lng[1024] lnb[1024] (p*64+c order) bfc[256] bh[16]
+//   f32: b1[32] b2[64] b3[64] lng[1024] lnb[1024] (p*64+c order) bfc[HID] bh[16]
+//
+// HID, the width of the projection after the LayerNorm, is a template parameter of everything
+// from the FC layer on: 256 for the actor-critic (IMPALA / PPO), 512 for the dueling DQN
+// (agents/dqn, DuellingAtariNetwork), whose advantage rows take the actor's place and whose
+// state value takes the critic's.  The conv trunk and the LayerNorm do not depend on it.
 #pragma once
 #include <stddef.h>
 
@@ -25,7 +30,12 @@ constexpr int OC2 = 64, KS2 = 4, ST2 = 2, H2 = 6, K2 = OC1 * KS2 * KS2;    // 51
 constexpr int OC3 = 64, KS3 = 3, ST3 = 1, H3 = 4, K3 = OC2 * KS3 * KS3;    // 576
 constexpr int P1 = H1 * H1, P2 = H2 * H2, P3 = H3 * H3;                   // 225, 36, 16
 constexpr int FLAT = OC3 * P3;                                             // 1024
-constexpr int HID = 256;
+constexpr int HID_AC = 256;   // actor-critic projection width (IMPALA, PPO)
+constexpr int HID_DQN = 512;  // dueling DQN projection width
+template <int HID> constexpr int hid_log2() {
+  static_assert(HID == 256 || HID == 512, "projection widths in use");
+  return HID == 256 ? 8 : 9;
+}
 // row stride (elements) of the LayerNorm output y [N][YLD], the FC layer's input: a padded
 // stride moves the rows of one 16-row fragment load off a common 4 KB alignment
 constexpr int YLD = FLAT;
@@ -39,7 +49,7 @@ constexpr float LN_EPS = 1e-5f;
 struct Canon {
   size_t w1, b1, w2, b2, w3, b3, lng, lnb, wfc, bfc, wa, ba, wc, bc, total;
 };
-inline Canon canon(int A) {
+template <int HID> inline Canon canon_t(int A) {
   Canon c;
   size_t o = 0;
   c.w1 = o; o += (size_t)OC1 * K1;
@@ -59,13 +69,15 @@ inline Canon canon(int A) {
   c.total = o;
   return c;
 }
+inline Canon canon(int A) { return canon_t<HID_AC>(A); }
+inline Canon canon_dqn(int A) { return canon_t<HID_DQN>(A); }  // wa / wc: advantage rows / value
 
 // shadow-weight element offsets (elements of the compute type T), 64-element aligned
 struct Shadow {
   size_t w1, w2, w3, wfc, wh, wht, w2t, w3t, total;
 };
 constexpr size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
-inline Shadow shadow() {
+template <int HID> inline Shadow shadow_t() {
   Shadow s;
   size_t o = 0;
   s.w1 = o; o = al64(o + (size_t)OC1 * K1);
@@ -79,9 +91,13 @@ inline Shadow shadow() {
   s.total = o;
   return s;
 }
+inline Shadow shadow() { return shadow_t<HID_AC>(); }
+inline Shadow shadow_dqn() { return shadow_t<HID_DQN>(); }
 // fp32 side vector (biases, LayerNorm affine) offsets
-struct Vecs {
+template <int HID> struct VecsT {
   static constexpr size_t b1 = 0, b2 = 64, b3 = 128, lng = 192, lnb = 192 + 1024,
-                          bfc = 192 + 2048, bh = 192 + 2048 + 256, total = 192 + 2048 + 256 + 64;
+                          bfc = 192 + 2048, bh = 192 + 2048 + HID, total = 192 + 2048 + HID + 64;
 };
+using Vecs = VecsT<HID_AC>;
+using VecsDqn = VecsT<HID_DQN>;
 }  // namespace net

@@ -73,9 +73,9 @@ template <typename T> struct Conv3Fwd {
   }
 };
 
-// projection Linear(1024 -> 256) + exact GELU (models/models.py:67-68).
-// rows o (256), cols frame n, k = p*64 + c over the LayerNorm output y.
-template <typename T> struct FcFwd {
+// projection Linear(1024 -> HID) + exact GELU (models/models.py:67-68).
+// rows o (HID), cols frame n, k = p*64 + c over the LayerNorm output y.
+template <typename T, int HID> struct FcFwd {
   static constexpr bool A_KMAJOR = false;
   static constexpr bool TILE_EPI = false;
   static constexpr int K = FLAT;
@@ -101,7 +101,7 @@ template <typename T> struct FcFwd {
 };
 
 // actor ‖ critic heads fused into one 16-row GEMM (models/models.py:69-70, 76).
-template <typename T> struct HeadsFwd {
+template <typename T, int HID> struct HeadsFwd {
   static constexpr bool A_KMAJOR = false;
   static constexpr bool TILE_EPI = false;
   static constexpr int K = HID;
@@ -145,12 +145,12 @@ template <typename T> struct Conv3LnFwd : Conv3Fwd<T> {
 
 // dy = dz . Wfc  (rows j in p*64+c order, cols frame), fp32 out for the LayerNorm backward.
 // A[j][o] = wfc[o][j]: read k-major from the forward weight (no transposed copy).
-template <typename T> struct FcDgrad {
+template <typename T, int HID> struct FcDgrad {
   static constexpr bool A_KMAJOR = true;
   static constexpr bool TILE_EPI = false;
   static constexpr int K = HID;
   int C;
-  const T* w;   // wfc [256][1024]
+  const T* w;   // wfc [HID][1024]
   const T* dz;
   float* dy;
   struct ColCtx { const T* p; };
@@ -205,7 +205,7 @@ template <typename T> struct Conv3Dgrad {
   }
 };
 
-template <typename T> struct FcWgrad {  // dWfc[o][j] = sum_n dz[n][o] y[n][j]
+template <typename T, int HID> struct FcWgrad {  // dWfc[o][j] = sum_n dz[n][o] y[n][j]
   static constexpr int R = HID, C = FLAT;
   int M;
   float out_scale = 1.f;
@@ -328,28 +328,28 @@ template <typename T> struct FcFwdCfg {
 // workgroups (192 at the same 6 splits), 78 KB: 512 workgroups, two per CU (8.4 -> 6.8 us)
 // With the weight-gradient loop's staging offsets advanced instead of recomputed (gemm.h):
 // fp32 17.89 -> 17.49 us, bf16 7.31 -> 7.23 (profiles/wgloop, parent -> this tree)
-template <typename T, int G> struct FcBwdCfg {
+template <typename T, int G, int HID> struct FcBwdCfg {
   static constexpr int DR = 64, DWR = G == 2 ? 2 : 4;
   static constexpr int DC = G == 2 ? 64 : 80, DWC = G == 2 ? 4 : 1;
   static constexpr int DBK = sizeof(T) == 2 ? 128 : 64;
   static constexpr int WBC = 128;
   static constexpr int SW = gemm_wg_smem<T, 64, WBC, 32, G>();
-  static constexpr int SD = gemm_tile_smem<T, DR, DC, DBK, DWR, DWC, FcDgrad<T>>();
+  static constexpr int SD = gemm_tile_smem<T, DR, DC, DBK, DWR, DWC, FcDgrad<T, HID>>();
   static constexpr int SMEM = SW > SD ? SW : SD;
 };
-template <typename T, int G>
-__global__ __launch_bounds__(256 * G) void fc_bwd_kernel(const FcWgrad<T> ow, float* __restrict__ slab,
+template <typename T, int G, int HID>
+__global__ __launch_bounds__(256 * G) void fc_bwd_kernel(const FcWgrad<T, HID> ow, float* __restrict__ slab,
                                                          float* __restrict__ slab_bias, int mps,
                                                          int gx, int gy, int gz,
-                                                         const FcDgrad<T> od, int n_rtiles) {
-  using C = FcBwdCfg<T, G>;
+                                                         const FcDgrad<T, HID> od, int n_rtiles) {
+  using C = FcBwdCfg<T, G, HID>;
   __shared__ __attribute__((aligned(16))) T smem[C::SMEM];
   const int nw = gx * gy * gz;
   if ((int)blockIdx.x < nw)
-    gemm_wg_body<T, 64, C::WBC, 1, 4, 32, G, FcWgrad<T>>(ow, slab, slab_bias, mps, (int)blockIdx.x,
+    gemm_wg_body<T, 64, C::WBC, 1, 4, 32, G, FcWgrad<T, HID>>(ow, slab, slab_bias, mps, (int)blockIdx.x,
                                                          gx, gy, gz, smem);
   else
-    gemm_tile_body<T, C::DR, C::DC, C::DBK, C::DWR, C::DWC, FcDgrad<T>>(od, n_rtiles, (int)blockIdx.x - nw,
+    gemm_tile_body<T, C::DR, C::DC, C::DBK, C::DWR, C::DWC, FcDgrad<T, HID>>(od, n_rtiles, (int)blockIdx.x - nw,
                                                                 (int)gridDim.x - nw, smem);
 }
 

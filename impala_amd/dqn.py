@@ -1,0 +1,601 @@
+"""Ape-X DQN on the HIP learner: ``AtariDQNModel``
+(models/distributed_models.py:72-104), ``ApexLearner`` (agents/dqn/learning.py:97-191),
+``PrioritizedReplay`` (rlmeta ReplayBuffer + PrioritizedSampler as agents/dqn/builder.py:82-89
+builds them) and ``ApexDQNBuilder`` (agents/dqn/builder.py:76-120).
+
+The network is IMPALA's trunk with a 512-wide projection and a dueling head; the step is one
+``dqn_train_step`` call (include/dqn_hip.h).  The compute path is the HIP library only.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import time
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from impala_amd import _lib
+from impala_amd.core import Builder, Learner
+from impala_amd.learner import ImpalaAdam
+from impala_amd.model import (OBS_SHAPE, _Node, layer_init_truncated, picklable_state,
+                              rebind_views)
+
+HIDDEN = 512
+
+
+def net_specs(num_actions: int = 15) -> List[Tuple[str, Tuple[int, ...]]]:
+    """state_dict keys / shapes of one DuellingAtariNetwork (models/models.py:44-87)."""
+    return [
+        ("body.body.0.weight", (32, 3, 8, 8)), ("body.body.0.bias", (32,)),
+        ("body.body.2.weight", (64, 32, 4, 4)), ("body.body.2.bias", (64,)),
+        ("body.body.4.weight", (64, 64, 3, 3)), ("body.body.4.bias", (64,)),
+        ("q.body.0.weight", (1024,)), ("q.body.0.bias", (1024,)),
+        ("q.body.1.weight", (HIDDEN, 1024)), ("q.body.1.bias", (HIDDEN,)),
+        ("q.q.weight", (num_actions, HIDDEN)), ("q.q.bias", (num_actions,)),
+        ("q.v.weight", (1, HIDDEN)), ("q.v.bias", (1,)),
+    ]
+
+
+def param_specs(num_actions: int = 15):
+    """AtariDQNModel.state_dict(): the online net, then the target net."""
+    s = net_specs(num_actions)
+    return [("online_net." + k, v) for k, v in s] + [("target_net." + k, v) for k, v in s]
+
+
+def param_count(num_actions: int = 15) -> int:
+    """Parameters of one net (the online net alone): dqn_param_count."""
+    return sum(int(np.prod(s)) for _, s in net_specs(num_actions))
+
+
+def _check(status: int, what: str) -> None:
+    if status != 0:
+        msg = _lib.lib().dqn_last_error().decode(errors="replace")
+        cls = _lib.Unsupported if status == _lib.IMPALA_E_UNSUPPORTED else RuntimeError
+        raise cls(f"{what} failed (status {status}): {msg}")
+
+
+def default_config() -> _lib.DqnConfig:
+    cfg = _lib.DqnConfig()
+    _check(_lib.lib().dqn_config_default(C.byref(cfg)), "dqn_config_default")
+    return cfg
+
+
+def dqn_loss_head(adv, v, actions, targets, probabilities=None,
+                  importance_sampling_exponent: float = 0.4) -> Dict[str, torch.Tensor]:
+    """The DQN loss alone on given heads (``dqn_loss_head``): adv [N,A], v [N] fp32 on the GPU."""
+    adv = adv.contiguous().float()
+    N, A = adv.shape
+    dev = adv.device
+    out = dict(dadv=torch.empty_like(adv), dv=torch.empty(N, device=dev),
+               priorities=torch.empty(N, device=dev), metrics=torch.empty(4, device=dev))
+    v, targets = v.reshape(-1).contiguous().float(), targets.reshape(-1).contiguous().float()
+    actions = actions.reshape(-1).contiguous().to(torch.int64)
+    if probabilities is not None:
+        probabilities = probabilities.reshape(-1).contiguous().float()
+    _check(_lib.lib().dqn_loss_head(_lib.ptr(adv), _lib.ptr(v), _lib.ptr(actions), _lib.ptr(targets),
+                                    _lib.ptr(probabilities), N, A, importance_sampling_exponent,
+                                    _lib.ptr(out["dadv"]), _lib.ptr(out["dv"]),
+                                    _lib.ptr(out["priorities"]), _lib.ptr(out["metrics"]),
+                                    _lib.stream_ptr(None)), "dqn_loss_head")
+    return out
+
+
+class DqnEngine:
+    """One ``dqn_learner`` handle bound to an ``AtariDQNModel``'s flat buffers."""
+
+    def __init__(self, model: "AtariDQNModel", batch_size: int = 512, dtype: Optional[str] = None,
+                 lr: float = 6.25e-5, eps: float = 1e-4, betas=(0.9, 0.999),
+                 max_grad_norm: float = 40.0, importance_sampling_exponent: float = 0.4,
+                 inference_only: bool = False):
+        self.model = model
+        self.device = model.flat.device
+        if self.device.type != "cuda":
+            raise RuntimeError("the DQN engine runs on the HIP path only (cuda device)")
+        self.N, self.A = int(batch_size), model.action_dim
+        cfg = default_config()
+        cfg.batch_size, cfg.num_actions = self.N, self.A
+        cfg.dtype = _lib.IMPALA_DTYPE_BF16 if (dtype or model.compute_dtype) == "bf16" \
+            else _lib.IMPALA_DTYPE_F32
+        cfg.lr, cfg.adam_eps = lr, eps
+        cfg.adam_beta1, cfg.adam_beta2 = betas
+        cfg.max_grad_norm = max_grad_norm
+        cfg.importance_sampling_exponent = importance_sampling_exponent
+        self._h = _lib._P()
+        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        _check(_lib.lib().dqn_create(C.byref(cfg), idx, C.byref(self._h)), "dqn_create")
+        n = model.flat.numel()
+        self.inference_only = inference_only
+        self.exp_avg = None if inference_only else torch.zeros(n, device=self.device)
+        self.exp_avg_sq = None if inference_only else torch.zeros(n, device=self.device)
+        self.metrics = torch.zeros(_lib.DQN_NUM_METRICS, device=self.device)
+        sp = _lib.stream_ptr(None)
+        _check(_lib.lib().dqn_bind_state(self._h, _lib.ptr(model.flat),
+                                         0 if inference_only else _lib.ptr(model.flat_grad),
+                                         _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
+                                         _lib.ptr(self.metrics), sp), "dqn_bind_state")
+        _check(_lib.lib().dqn_bind_target(self._h, _lib.ptr(model.target_flat), sp), "dqn_bind_target")
+        self._version = model._version
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            _lib.lib().dqn_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _fresh(self):
+        if self._version != self.model._version:  # the flat buffers were written from outside
+            _check(_lib.lib().dqn_refresh_weights(self._h, _lib.stream_ptr(None)), "dqn_refresh_weights")
+            self._version = self.model._version
+
+    def bind_metrics(self, m: torch.Tensor) -> None:
+        self.metrics = m
+        _check(_lib.lib().dqn_set_metrics(self._h, _lib.ptr(m)), "dqn_set_metrics")
+
+    def set_step(self, step: int) -> None:
+        _check(_lib.lib().dqn_set_step(self._h, int(step), _lib.stream_ptr(None)), "dqn_set_step")
+
+    def forward(self, obs: torch.Tensor, target: bool = False) -> torch.Tensor:
+        self._fresh()
+        obs = obs.contiguous()
+        n = obs.shape[0]
+        q = torch.empty(n, self.A, device=self.device)
+        _check(_lib.lib().dqn_forward(self._h, _lib.ptr(obs), n, 1 if target else 0, _lib.ptr(q),
+                                      _lib.stream_ptr(None)), "dqn_forward")
+        return q
+
+    def act(self, obs: torch.Tensor, eps, seed: int, counter: int):
+        """-> (action [n] i64, q_pi [n], q_star [n], greedy [n] i64) on the device."""
+        self._fresh()
+        obs = obs.contiguous()
+        n = obs.shape[0]
+        eps_t, eps_all = None, 0.0
+        if isinstance(eps, torch.Tensor) and eps.numel() > 1:
+            eps_t = eps.reshape(-1).to(self.device, torch.float32).contiguous()
+            if eps_t.numel() != n:
+                raise ValueError("eps: one value, or one per frame")
+        else:
+            eps_all = float(eps.reshape(-1)[0]) if isinstance(eps, torch.Tensor) else float(eps)
+        a = torch.empty(n, dtype=torch.int64, device=self.device)
+        g = torch.empty(n, dtype=torch.int64, device=self.device)
+        q_pi, q_star = torch.empty(n, device=self.device), torch.empty(n, device=self.device)
+        _check(_lib.lib().dqn_act(self._h, _lib.ptr(obs), n, _lib.ptr(eps_t), eps_all, int(seed),
+                                  int(counter), _lib.ptr(a), _lib.ptr(q_pi), _lib.ptr(q_star),
+                                  _lib.ptr(g), _lib.stream_ptr(None)), "dqn_act")
+        return a, q_pi, q_star, g
+
+    def sync_target(self) -> None:
+        self._fresh()
+        _check(_lib.lib().dqn_sync_target(self._h, _lib.stream_ptr(None)), "dqn_sync_target")
+
+    def train_step(self, obs, actions, targets, probabilities=None) -> torch.Tensor:
+        """One learner step; returns the new priorities |err| [N] (device)."""
+        self._fresh()
+        if obs.shape[0] != self.N:
+            raise ValueError(f"batch of {obs.shape[0]} transitions on a handle of {self.N}")
+        prio = torch.empty(self.N, device=self.device)
+        keep = [obs.contiguous(), actions.reshape(-1).contiguous().to(torch.int64),
+                targets.reshape(-1).contiguous().float(),
+                None if probabilities is None else probabilities.reshape(-1).contiguous().to(
+                    self.device, torch.float32)]
+        b = _lib.DqnBatch(_lib.ptr(keep[0]), _lib.ptr(keep[1]), _lib.ptr(keep[2]), _lib.ptr(keep[3]),
+                          _lib.ptr(prio))
+        _check(_lib.lib().dqn_train_step(self._h, C.byref(b), _lib.stream_ptr(None)), "dqn_train_step")
+        return prio
+
+
+class AtariDQNModel(nn.Module):
+    """Drop-in for ``models.distributed_models.AtariDQNModel`` on an MI355X: the online and the
+    target net are one flat fp32 buffer each, exposed as ``nn.Parameter`` views under the
+    reference's ``state_dict`` names (``target_net.*`` with ``requires_grad=False``)."""
+
+    def __init__(self, observation_space: Tuple[int, ...] = OBS_SHAPE, action_dim: int = 15,
+                 device="cuda", seed: Optional[int] = None, dtype: str = "fp32"):
+        super().__init__()
+        if tuple(observation_space) != OBS_SHAPE:
+            raise ValueError(f"AtariBody requires observations of shape {OBS_SHAPE}")
+        if not 1 <= action_dim <= 15:
+            raise ValueError("action_dim must be in [1, 15]")
+        self.action_dim = action_dim
+        self.compute_dtype = dtype
+        device = torch.device(device)
+        n = param_count(action_dim)
+        self.flat = torch.zeros(n, dtype=torch.float32, device=device)
+        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=device)
+        self.target_flat = torch.zeros(n, dtype=torch.float32, device=device)
+        self._specs = net_specs(action_dim)
+        self._version = 0
+        self._train_engine = None
+        self._infer_engine = None
+        self._act_seed = int.from_bytes(os.urandom(8), "little") >> 2
+        self._act_calls = 0
+        self.add_module("online_net", _Node())
+        self.add_module("target_net", _Node())
+        self._register(self.online_net, self.flat, self.flat_grad, True)
+        self._register(self.target_net, self.target_flat, None, False)
+        self.reset_parameters(seed)
+        self.downstream = None
+
+    def _register(self, root, flat, grad, requires_grad):
+        off = 0
+        for name, shape in self._specs:
+            cnt = int(np.prod(shape))
+            parts = name.split(".")
+            mod = root
+            for p in parts[:-1]:
+                if not hasattr(mod, p):
+                    mod.add_module(p, _Node())
+                mod = getattr(mod, p)
+            param = nn.Parameter(flat[off:off + cnt].view(shape), requires_grad=requires_grad)
+            if grad is not None:
+                param.grad = grad[off:off + cnt].view(shape)
+            mod.register_parameter(parts[-1], param)
+            off += cnt
+        assert off == flat.numel()
+
+    # ---------------------------------------------------------------- parameters
+    def reset_parameters(self, seed: Optional[int] = None) -> None:
+        """Reference init: layers built in the reference's order on the CPU, ``layer_init_truncated``
+        on the 3 convs and 3 Linears (models/common.py:151-158), LayerNorm (1, 0); the target net
+        is a copy of the online net (distributed_models.py:77)."""
+        if seed is not None:
+            torch.manual_seed(int(seed))
+        trunc = layer_init_truncated
+        layers = [trunc(nn.Conv2d(3, 32, 8, stride=4), 3 * 64),
+                  trunc(nn.Conv2d(32, 64, 4, stride=2), 32 * 16),
+                  trunc(nn.Conv2d(64, 64, 3, stride=1), 64 * 9)]
+        layers += [nn.LayerNorm(1024), trunc(nn.Linear(1024, HIDDEN), 1024),
+                   trunc(nn.Linear(HIDDEN, self.action_dim), HIDDEN), trunc(nn.Linear(HIDDEN, 1), HIDDEN)]
+        flat = torch.cat([t.detach().reshape(-1) for l in layers for t in (l.weight, l.bias)])
+        with torch.no_grad():
+            self.flat.copy_(flat.to(self.flat.device))
+            self.target_flat.copy_(self.flat)
+        self.params_changed()
+
+    def load_flat(self, flat, target=None) -> None:
+        with torch.no_grad():
+            self.flat.copy_(torch.as_tensor(np.asarray(flat, dtype=np.float32)).to(self.flat.device))
+            if target is not None:
+                self.target_flat.copy_(torch.as_tensor(np.asarray(target, dtype=np.float32)).to(
+                    self.flat.device))
+        self.params_changed()
+
+    def params_changed(self) -> None:
+        self._version = getattr(self, "_version", 0) + 1
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        res = super().load_state_dict(state_dict, strict=strict, assign=False)
+        self.params_changed()
+        return res
+
+    def __getstate__(self):
+        return picklable_state(self)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        rebind_views(self.online_net, self._specs, self.flat, self.flat_grad)
+        rebind_views(self.target_net, self._specs, self.target_flat, None)
+        self.params_changed()
+
+    # ---------------------------------------------------------------- compute
+    def _engine(self) -> DqnEngine:
+        if self._train_engine is not None:
+            return self._train_engine
+        if self._infer_engine is None:
+            # the reference serves act() in batches of <= 128 (distributed_models.py:84)
+            self._infer_engine = DqnEngine(self, batch_size=128, inference_only=True)
+        return self._infer_engine
+
+    def forward(self, obs: torch.Tensor) -> torch.Tensor:
+        """distributed_models.py:81-82 -> q [N, A] of the online net."""
+        if obs.device.type != "cuda" or self.flat.device.type != "cuda":
+            raise RuntimeError("AtariDQNModel.forward runs on the HIP path only (cuda device)")
+        return self._engine().forward(obs)
+
+    @torch.no_grad()
+    def act(self, obs: torch.Tensor, eps: torch.Tensor):
+        """distributed_models.py:84-101 -> (action [N,1], q_pi [N,1], q_star [N,1]) on the CPU."""
+        if self.flat.device.type != "cuda":
+            raise RuntimeError("AtariDQNModel.act runs on the HIP path only (cuda device)")
+        x = obs.to(self.flat.device)
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        self._act_calls += 1
+        a, q_pi, q_star, _ = self._engine().act(x, eps, seed=self._act_seed, counter=self._act_calls)
+        return a.unsqueeze(-1).cpu(), q_pi.unsqueeze(-1).cpu(), q_star.unsqueeze(-1).cpu()
+
+    def sync_target_net(self) -> None:  # distributed_models.py:103-104
+        if self.flat.device.type == "cuda":
+            self._engine().sync_target()
+        else:
+            with torch.no_grad():
+                self.target_flat.copy_(self.flat)
+
+    def push(self) -> None:
+        if self.downstream is not None:
+            self.downstream.load_flat_from(self)
+
+    def load_flat_from(self, other: "AtariDQNModel") -> None:
+        with torch.no_grad():
+            self.flat.copy_(other.flat.to(self.flat.device, non_blocking=True))
+            self.target_flat.copy_(other.target_flat.to(self.flat.device, non_blocking=True))
+        self.params_changed()
+
+    def clone_to(self, device) -> "AtariDQNModel":
+        m = AtariDQNModel(OBS_SHAPE, self.action_dim, device=device, dtype=self.compute_dtype)
+        m.load_flat_from(self)
+        for p in m.parameters():
+            p.requires_grad_(False)
+        return m
+
+
+class PrioritizedReplay:
+    """A ring of flat transitions ``(s u8 [3,64,64], a i64, target f32)`` with a priority vector,
+    on one device: ``P(i) ∝ priority_i ** priority_exponent`` (rlmeta's PrioritizedSampler as
+    agents/dqn/builder.py:82-89 configures it).  ``sample`` is cumsum + searchsorted in torch.
+
+    The returned ``probabilities`` are normalised (``p^α / Σ p^α``); whether rlmeta returns these
+    or the raw ``p^α`` is not pinned, and the learner's weights ``w / max w`` do not depend on
+    that scale.
+    """
+
+    def __init__(self, capacity: int, priority_exponent: float = 0.6, device="cuda",
+                 seed: Optional[int] = None, obs_shape=OBS_SHAPE):
+        self.capacity = int(capacity)
+        self.alpha = float(priority_exponent)
+        self.device = torch.device(device)
+        self.s = torch.zeros((self.capacity,) + tuple(obs_shape), dtype=torch.uint8, device=self.device)
+        self.a = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
+        self.target = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+        self.priorities = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+        self._size = 0
+        self._cursor = 0
+        self._max_priority = torch.ones((), dtype=torch.float32, device=self.device)
+        self._gen = torch.Generator(device=self.device)
+        self.reset(seed)
+
+    def reset(self, seed: Optional[int] = None) -> None:
+        self._gen.manual_seed(0 if seed is None else int(seed))
+
+    def __len__(self) -> int:
+        return self._size
+
+    @property
+    def size(self) -> int:
+        return self._size
+
+    def extend(self, items, priorities=None) -> torch.Tensor:
+        """items: ``(s [n,3,64,64], a [n], target [n])`` or a list of per-transition triples (each
+        with or without a leading dim).  Items without a priority get the current maximum.
+        Returns the ring keys written."""
+        if isinstance(items, (list,)) and items and isinstance(items[0], (tuple, list)):
+            cols = list(zip(*items))
+            s = torch.cat([x if x.dim() == 4 else x.unsqueeze(0) for x in cols[0]])
+            a = torch.cat([x.reshape(-1) for x in cols[1]])
+            t = torch.cat([x.reshape(-1) for x in cols[2]])
+        else:
+            s, a, t = items
+        n = s.shape[0]
+        if n > self.capacity:
+            raise ValueError("more items than the ring holds")
+        keys = (torch.arange(n, device=self.device) + self._cursor) % self.capacity
+        self.s[keys] = s.to(self.device)
+        self.a[keys] = a.reshape(-1).to(self.device, torch.int64)
+        self.target[keys] = t.reshape(-1).to(self.device, torch.float32)
+        if priorities is None:
+            self.priorities[keys] = self._max_priority
+        else:
+            p = torch.as_tensor(priorities, dtype=torch.float32).reshape(-1).to(self.device)
+            self.priorities[keys] = p
+            self._max_priority = torch.maximum(self._max_priority, p.max())
+        self._cursor = (self._cursor + n) % self.capacity
+        self._size = min(self.capacity, self._size + n)
+        return keys
+
+    async def async_extend(self, items, priorities=None):
+        return self.extend(items, priorities)
+
+    def probabilities(self) -> torch.Tensor:
+        w = self.priorities[:self._size].double().pow(self.alpha)
+        return (w / w.sum()).float()
+
+    def sample(self, n: int):
+        """-> (keys [n] i64, (s, a, target), probabilities [n]), drawn with replacement."""
+        if self._size == 0:
+            raise RuntimeError("sample from an empty replay")
+        w = self.priorities[:self._size].double().pow(self.alpha)
+        cdf = torch.cumsum(w, 0)
+        u = torch.rand(n, generator=self._gen, device=self.device, dtype=torch.float64) * cdf[-1]
+        keys = torch.searchsorted(cdf, u, right=True).clamp_(max=self._size - 1)
+        probs = (w[keys] / cdf[-1]).float()
+        return keys, (self.s[keys], self.a[keys], self.target[keys]), probs
+
+    def update(self, keys, priorities) -> None:
+        p = torch.as_tensor(priorities, dtype=torch.float32).reshape(-1).to(self.device)
+        self.priorities[torch.as_tensor(keys).to(self.device)] = p
+        # (a device-side running maximum: no host synchronisation in the step)
+        self._max_priority = torch.maximum(self._max_priority, p.max())
+
+    def async_update(self, keys, priorities):
+        self.update(keys, priorities)
+        return None
+
+    def warm_up(self, learning_starts: Optional[int] = None, timeout: float = 240.0) -> None:
+        """Block until ``learning_starts`` transitions are stored (rlmeta ReplayBuffer.warm_up);
+        another thread's ``extend`` fills the ring meanwhile."""
+        if not learning_starts:
+            return
+        need = min(int(learning_starts), self.capacity)
+        deadline = time.monotonic() + timeout
+        while self._size < need:
+            if time.monotonic() > deadline:
+                raise TimeoutError(f"replay warm_up: {self._size}/{need} after {timeout}s")
+            time.sleep(0.01)
+
+
+class ApexLearner(Learner):
+    """agents/dqn/learning.py:97-191 with ``_train_step`` as one ``dqn_train_step`` call."""
+
+    def __init__(self, model, replay_buffer, optimizer=None, batch_size: int = 512,
+                 max_grad_norm: float = 40.0, importance_sampling_exponent: float = 0.4,
+                 target_sync_period: int = 2500, learning_starts: Optional[int] = None,
+                 model_push_period: int = 10, dtype: Optional[str] = None) -> None:
+        self._model = model
+        self._replay_buffer = replay_buffer
+        if optimizer is None:
+            optimizer = ImpalaAdam(lr=6.25e-5, eps=1e-4)
+        elif isinstance(optimizer, torch.optim.Optimizer):
+            optimizer = ImpalaAdam.from_torch(optimizer)
+        self._optimizer = optimizer
+        self._batch_size = batch_size
+        self._max_grad_norm = max_grad_norm
+        self._importance_sampling_exponent = importance_sampling_exponent
+        self._target_sync_period = target_sync_period
+        self._learning_starts = learning_starts
+        self._model_push_period = model_push_period
+        self._step_counter = 0
+        self._update_priorities_future = None
+        self._device = model.flat.device
+        self.can_train = False
+        self._engine = DqnEngine(model, batch_size=batch_size, dtype=dtype, lr=optimizer.lr,
+                                 eps=optimizer.eps, betas=optimizer.betas,
+                                 max_grad_norm=max_grad_norm,
+                                 importance_sampling_exponent=importance_sampling_exponent)
+        model._train_engine = self._engine
+
+    @property
+    def engine(self) -> DqnEngine:
+        return self._engine
+
+    @property
+    def samples_per_step(self) -> int:
+        return self._batch_size
+
+    def prepare(self):  # learning.py:154-157
+        if not self.can_train:
+            self._replay_buffer.warm_up(self._learning_starts)
+        self.can_train = True
+
+    def train_step(self):
+        """Sample, one device step, then the periodic target sync and weight push.  The ``debug/*``
+        keys are the reference learner's; the times are host wall-clock milliseconds and the two
+        rates are transitions per second."""
+        clock = time.perf_counter
+        begin = clock()
+        keys, batch, probabilities = self._replay_buffer.sample(self._batch_size)
+        batch = tuple(x.to(self._device) for x in batch)
+        sampled = clock()
+        metrics = self._train_step(keys, batch, probabilities)
+        stepped = clock()
+        self._step_counter += 1
+
+        def every(period, action):  # -> ms spent in `action` when this step is a multiple of period
+            if self._step_counter % period:
+                return 0.0
+            t = clock()
+            action()
+            return (clock() - t) * 1e3
+
+        sync_ms = every(self._target_sync_period, self._model.sync_target_net)
+        push_ms = every(self._model_push_period, self._model.push)
+        metrics.update({
+            "debug/replay_sample_per_second": self._batch_size / max(sampled - begin, 1e-9),
+            "debug/gradient_per_second": self._batch_size / max(stepped - begin, 1e-9),
+            "debug/forward_dt": (stepped - sampled) * 1e3,
+            "debug/target_sync_time": sync_ms,
+            "debug/update_time": push_ms,
+            "debug/total_time": (clock() - begin) * 1e3,
+        })
+        return metrics
+
+    def _train_step(self, keys, batch, probabilities) -> Dict[str, torch.Tensor]:  # :159-191
+        e = self._engine
+        m = torch.empty(_lib.DQN_NUM_METRICS, dtype=torch.float32, device=e.device)
+        e.bind_metrics(m)
+        obs, action, target = batch
+        priorities = e.train_step(obs, action, target, probabilities)
+        priority_update_time = 0
+        if isinstance(self._replay_buffer, PrioritizedReplay):
+            self._replay_buffer.update(keys, priorities)  # stays on the device
+        else:
+            if self._update_priorities_future is not None:
+                t0 = time.perf_counter()
+                self._update_priorities_future.wait()
+                priority_update_time = (time.perf_counter() - t0) * 1000
+            self._update_priorities_future = self._replay_buffer.async_update(keys, priorities.cpu())
+        v = m.unbind(0)  # device scalars; float(v) synchronises lazily
+        out = {name: v[i] for name, i in _lib.DQN_METRIC_SLOTS}
+        out["debug/priority_update_time"] = priority_update_time
+        return out
+
+
+class ConstantEpsFunc:
+    """Actor index -> the same exploration rate for every actor (the evaluation actors)."""
+
+    def __init__(self, eps: float) -> None:
+        self.eps = float(eps)
+
+    def __call__(self, index: int) -> float:
+        return self.eps
+
+
+class FlexibleEpsFunc:
+    """Actor index -> Ape-X's per-actor exploration rate: ``eps ** (1 + alpha * i / (num - 1))`` for
+    actor i of ``num``, so actor 0 explores at ``eps`` and the last at ``eps ** (1 + alpha)``; one
+    actor alone gets ``eps``.  Signature as the reference's helper of the same name."""
+
+    def __init__(self, eps: float, num: int, alpha: float = 7.0) -> None:
+        self.eps, self.num, self.alpha = float(eps), int(num), float(alpha)
+
+    def __call__(self, index: int) -> float:
+        frac = index / (self.num - 1) if self.num > 1 else 0.0
+        return self.eps ** (1.0 + self.alpha * frac)
+
+
+class ApexDQNBuilder(Builder):
+    """agents/dqn/builder.py:76-120 on the HIP learner."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self._learner_model = None
+        self._actor_model = None
+
+    def make_replay(self):  # builder.py:82-89
+        return PrioritizedReplay(self.cfg.agent.replay_buffer_size,
+                                 priority_exponent=float(self.cfg.agent.priority_exponent),
+                                 device=self.cfg.distributed.train_device,
+                                 seed=self.cfg.training.seed)
+
+    def make_actor(self, model, rb=None, deterministic: bool = False):  # builder.py:91-97
+        # ApexActor's targets need rlego.n_step_bootstrapped_returns, which is absent; the actor
+        # side is out of scope here
+        raise NotImplementedError("Ape-X actors are not part of the MI355X learner path")
+
+    def learner_kwargs(self) -> dict:
+        """make_learner's constructor arguments (builder.py:99-110): Adam from
+        cfg.agent.optimizer and learning_starts; every other argument keeps its default."""
+        return dict(optimizer=ImpalaAdam(lr=float(self.cfg.agent.optimizer.lr),
+                                         eps=float(self.cfg.agent.optimizer.eps)),
+                    learning_starts=self.cfg.agent.learning_starts)
+
+    def make_learner(self, model, rb):
+        return ApexLearner(self._learner_model if model is None else model, replay_buffer=rb,
+                           **self.learner_kwargs())
+
+    def make_network(self, env_spec=None):  # builder.py:112-120
+        obs_shape, n_act = OBS_SHAPE, 15
+        if env_spec is not None:
+            obs_shape = tuple(env_spec.observation_space.shape)
+            n_act = int(env_spec.action_space.n)
+        model = AtariDQNModel(obs_shape, n_act, device=self.cfg.distributed.train_device)
+        self._learner_model = model
+        self._actor_model = model.clone_to(self.cfg.distributed.infer_device)
+        model.downstream = self._actor_model
+        return model

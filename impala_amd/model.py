@@ -65,6 +65,18 @@ def rebind_views(root: nn.Module, specs, flat: torch.Tensor, grad: Optional[torc
     assert off == flat.numel()
 
 
+def layer_init_truncated(layer: nn.Module, fan_in: int) -> nn.Module:
+    """The reference's ``layer_init_truncated`` (models/common.py:151-158) restated, shared by the
+    actor-critic and the DQN model: trunc_normal weights of std sqrt(1 / fan_in) / 0.8796...,
+    zero bias."""
+    std_div = np.asarray(.87962566103423978, dtype=np.float32)
+    with torch.no_grad():
+        std = np.sqrt(1.0 / max(1, fan_in)) / std_div
+        torch.nn.init.trunc_normal_(layer.weight, std=std)
+        torch.nn.init.constant_(layer.bias, 0.)
+    return layer
+
+
 # attributes holding native handles (ctypes pointers): never pickled, recreated lazily
 ENGINE_ATTRS = ("_train_engine", "_infer_engine", "_engine")
 
@@ -132,15 +144,7 @@ class AtariPPOModel(nn.Module):
         global torch RNG first, as main.py:57-58 does before ``make_network``."""
         if seed is not None:
             torch.manual_seed(int(seed))
-        std_div = np.asarray(.87962566103423978, dtype=np.float32)
-
-        def trunc(layer, fan_in):
-            with torch.no_grad():
-                std = np.sqrt(1.0 / max(1, fan_in)) / std_div
-                torch.nn.init.trunc_normal_(layer.weight, std=std)
-                torch.nn.init.constant_(layer.bias, 0.)
-            return layer
-
+        trunc = layer_init_truncated
         layers = [trunc(nn.Conv2d(3, 32, 8, stride=4), 3 * 64),
                   trunc(nn.Conv2d(32, 64, 4, stride=2), 32 * 16),
                   trunc(nn.Conv2d(64, 64, 3, stride=1), 64 * 9)]
