@@ -144,25 +144,34 @@ DEV float xor32_sum(float v) {
 // Four values reduced over the four rows at once (3 swaps, 3 adds, instead of 4 x 2 of each):
 // row r of the result holds ((x[row 0] + x[row 1]) + (x[row 2] + x[row 3])) of x = a, b, c, d for
 // r = 0, 1, 2, 3 -- the value and the order of xor32_sum(xor16_sum(x)).
+// WAIT = false: for a call that follows, in program order, a WAIT call on other registers of the
+// same MFMAs' results (volatile asm blocks keep their order): those MFMAs have retired, and the
+// 20 wait states need not be paid again.
+template <bool WAIT = true>
 DEV float rows_sum4(float a, float b, float c, float d) {
   // one asm block: its inputs come straight from MFMAs, whose results a following VALU /
   // permlane may only read after the XDL write latency (the leading 20 wait states; the
   // compiler does not insert them for inline asm), and the adds -> permlane32 read hazard
   // (s_nop 1).  Rows after the swaps: a = [a0 b0 a2 b2], b = [a1 b1 a3 b3]; after the adds and
   // the xor-32 swap, a = [a01 b01 c01 d01], c = [a23 b23 c23 d23].
-  asm volatile(
-      "s_nop 7\n\ts_nop 7\n\ts_nop 3\n\t"
-      "v_permlane16_swap_b32 %0, %1\n\t"
-      "v_permlane16_swap_b32 %2, %3\n\t"
-      "s_nop 1\n\t"
-      "v_add_f32 %0, %0, %1\n\t"
-      "v_add_f32 %2, %2, %3\n\t"
-      "s_nop 1\n\t"
-      "v_permlane32_swap_b32 %0, %2\n\t"
-      "s_nop 1\n\t"
-      "v_add_f32 %0, %0, %2\n\t"
-      "s_nop 1"
-      : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+  // (WAIT = false keeps s_nop 1: a register copy the compiler may place before the block is a
+  // VALU write that the first permlane reads)
+#define ROWS_SUM4_BODY                      \
+  "v_permlane16_swap_b32 %0, %1\n\t"        \
+  "v_permlane16_swap_b32 %2, %3\n\t"        \
+  "s_nop 1\n\t"                             \
+  "v_add_f32 %0, %0, %1\n\t"                \
+  "v_add_f32 %2, %2, %3\n\t"                \
+  "s_nop 1\n\t"                             \
+  "v_permlane32_swap_b32 %0, %2\n\t"        \
+  "s_nop 1\n\t"                             \
+  "v_add_f32 %0, %0, %2\n\t"                \
+  "s_nop 1"
+  if constexpr (WAIT)
+    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3\n\t" ROWS_SUM4_BODY : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+  else
+    asm volatile("s_nop 1\n\t" ROWS_SUM4_BODY : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+#undef ROWS_SUM4_BODY
   return a;
 }
 DEV uint32_t xor16_or(uint32_t v) {

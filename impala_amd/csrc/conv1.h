@@ -359,7 +359,10 @@ DEV void conv12_fwd_body(const uint8_t* __restrict__ x, const T* __restrict__ w1
   T* a2s = smem + G * GSZ;
   const bool tail = c3.act3 != nullptr;
   constexpr int WPG = c12f_wpg<T>(), NTG = 64 * WPG;
-  const int grp = (int)threadIdx.x / NTG, tid = (int)threadIdx.x % NTG, lane = tid & 63, wave = tid >> 6;
+  // group and wave are wave-uniform; readfirstlane says so to the compiler, which then tests the
+  // roles (conv2 waves, stash waves, the tail) with scalar branches instead of exec masks
+  const int grp = __builtin_amdgcn_readfirstlane((int)threadIdx.x / NTG);
+  const int tid = (int)threadIdx.x % NTG, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wq = wave & 3, wh = WPG == 8 ? wave >> 2 : 0;
   constexpr int NI = WPG == 8 ? 1 : 2;  // conv1 output-channel tiles per wave
   // the image loads / stash run on 256 threads: fp32 on waves 4..7, during waves 0..3's conv2
@@ -769,11 +772,16 @@ DEV void conv12_fwd_body(const uint8_t* __restrict__ x, const T* __restrict__ w1
         // every frame slot runs (a slot past the run re-reads the last frame; its result is
         // dropped), so the FMAX accumulators interleave (F::mma_e); the act2 window reads run one
         // k-step ahead (k = ks*16 + kl: tap = k / 64, ci = k % 64)
+        // one base per frame slot, computed once: the k-step's part of every address is an
+        // instruction offset
+        const T* a2fr[FMAX];
+#pragma unroll
+        for (int fr = 0; fr < FMAX; ++fr) a2fr[fr] = a2f + min(fr, nF - 1) * (A2F * LDA2);
         auto bload = [&](int ks, V* b) {
           const int k = ks * KS, tap = k >> 6, kh = tap / 3, kw = tap - kh * 3;
 #pragma unroll
           for (int fr = 0; fr < FMAX; ++fr)
-            b[fr] = *reinterpret_cast<const V*>(a2f + (min(fr, nF - 1) * A2F + kh * A2W + kw) * LDA2 + (k & 63));
+            b[fr] = *reinterpret_cast<const V*>(a2fr[fr] + (kh * A2W + kw) * LDA2 + (k & 63));
         };
         V b[2][FMAX];
         bload(0, b[0]);
@@ -879,7 +887,8 @@ constexpr int C12_GROUPS = 2;
 // two groups overlap: the frame's s2d image as BYTES (the raw 0..255 values, converted when
 // read) in [Y][channel][X] rows of XP bytes (4 consecutive X in one 32-bit word) x 2, dY1 in
 // pixel rows iy * 16 + ix (240: the conv1 weight gradient's 15 k-steps = the 15 pixel rows,
-// ix = 15 a zero pad) x 2, dY2 rows (36) x 2, one half-Z tile per stride-parity class (2 taps x 32 channels; row 36
+// ix = 15 a zero pad; then 16 zero rows, the pad pixels 240..255 of the weight gradient's last
+// k-block, so that its loop reads them like any other row) x 2, dY2 rows (36) x 2, one half-Z tile per stride-parity class (2 taps x 32 channels; row 36
 // stays zero: the gather's out-of-range taps read it), the mask words x 2.
 // The Z rows are 64 floats = 16 chunks of 16 B, unpadded; chunk c of row r is stored at chunk
 // c ^ zswz(r).  The Z stores write 8 consecutive rows at one chunk per ds_write_b128 lane
@@ -891,13 +900,15 @@ constexpr int C12_GROUPS = 2;
 // 3 chunks (39 % of the backward's LDS cycles were conflict cycles, profiles/r04pmc).
 struct C12B32 {
   static constexpr int XP = 20, LDX = 36;  // image row bytes (X 0..16), dY1 row
-  static constexpr int NROW = 240, LDD = OC2 + 4, DROWS = P2, LDZ = 2 * OC1, ZROWS = P2 + 1;
+  static constexpr int NROW = 240, NROWP = c1::NPAD;  // dY1 pixel rows, and with the zero pad rows
+  static constexpr int LDD = OC2 + 4, DROWS = P2, LDZ = 2 * OC1, ZROWS = P2 + 1;
   static_assert(2 * OC1 == 64, "Z rows of 16 chunks");
   __device__ static constexpr int zswz(int r) { return ((r & 1) * 12) | ((r >> 1) & 3); }
-  static constexpr int IMGW = c1::GRID * c1::CH * XP / 4, DYW = NROW * LDX, D2W = DROWS * LDD;
+  static constexpr int IMGW = c1::GRID * c1::CH * XP / 4, DYW = NROWP * LDX, D2W = DROWS * LDD;
   static constexpr int IMG = 0, DYT = IMG + 2 * IMGW, D2S = DYT + 2 * DYW;
   static constexpr int Z0 = D2S + 2 * D2W, ZSZ = ZROWS * LDZ, MSK = Z0 + 4 * ZSZ;
   static constexpr int BYTES = (MSK + 2 * c1::NPIX) * 4;
+  static_assert(BYTES <= 160 * 1024, "one workgroup's LDS");
 };
 
 // LDS of conv12_bwd_body (bytes).  bf16: per-group image / dY1 / dY2 tiles, the ReLU mask words,
@@ -1055,6 +1066,16 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
     f32x4 nd2[ND2];
     uint32_t nmk;
   };
+  // No lane-divergent test in either half: the ragged last pass of the dY2 vectors is whole
+  // waves (a scalar branch on the wave index), the mask word of a thread past the 225 pixels is
+  // a second load of the last pixel's, stored into a dY2 row's unread pitch columns (row
+  // tid - 225, floats 64..67) -- the padding has a place, the loop has no exec-masked block.
+  static_assert(D2V % 64 == 0 && 256 - c1::NPIX <= P2 && LDD > OC2, "whole waves; a pad slot per thread");
+  const int wu = __builtin_amdgcn_readfirstlane(wave);
+  const int tidm = min(tid, c1::NPIX - 1);
+  // the mask word's LDS slot (in words) in buffer 0, and its step to buffer 1
+  const int mword = tid < c1::NPIX ? L::MSK + tid : L::D2S + (tid - c1::NPIX) * LDD + OC2;
+  const int mstep = tid < c1::NPIX ? c1::NPIX : L::D2W;
   auto stage_ld = [&](int fi, int fd, StRegs& r) {
     r.nmk = 0;
     if (fi >= 0) c1_load_frame<float>(x + rm.map(fi) * IMG, tid, r.nv);
@@ -1063,9 +1084,9 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
 #pragma unroll
       for (int i = 0; i < ND2; ++i) {
         const int e = tid + i * 256;
-        r.nd2[i] = e < D2V ? *reinterpret_cast<const f32x4*>(src + e * 4) : F::zero();
+        if ((i + 1) * 256 <= D2V || wu < (D2V - i * 256) / 64) r.nd2[i] = *reinterpret_cast<const f32x4*>(src + e * 4);
       }
-      if (tid < c1::NPIX) r.nmk = mask1[(size_t)fd * c1::NPIX + tid];
+      r.nmk = mask1[(size_t)fd * c1::NPIX + tidm];
     }
   };
   auto stage_st = [&](int fi, int bi, int fd, int bd, const StRegs& r) {
@@ -1074,9 +1095,10 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
 #pragma unroll
       for (int i = 0; i < ND2; ++i) {
         const int e = tid + i * 256;
-        if (e < D2V) *reinterpret_cast<f32x4*>(d2s + ((e * 4) / OC2) * LDD + (e * 4) % OC2) = r.nd2[i];
+        if ((i + 1) * 256 <= D2V || wu < (D2V - i * 256) / 64)
+          *reinterpret_cast<f32x4*>(d2s + ((e * 4) / OC2) * LDD + (e * 4) % OC2) = r.nd2[i];
       }
-      if (tid < c1::NPIX) msk_buf(bd)[tid] = r.nmk;
+      reinterpret_cast<uint32_t*>(smem)[mword + bd * mstep] = r.nmk;
     }
     if (fi < 0) return;
     uint8_t* img = img_buf(bi);
@@ -1101,6 +1123,10 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
     const int b = e / (H1 * (LDX / 4)), r = e % (H1 * (LDX / 4));
     *reinterpret_cast<f32x4*>(dyt_buf(b) + ((r / (LDX / 4)) * 16 + 15) * LDX + 4 * (r % (LDX / 4))) = F::zero();
   }
+  // and the pad pixel rows 240..255 of both buffers (group B's last k-block reads them)
+  constexpr int NPV = (L::NROWP - L::NROW) * (LDX / 4);
+  for (int e = (int)threadIdx.x; e < 2 * NPV; e += 512)
+    *reinterpret_cast<f32x4*>(dyt_buf(e / NPV) + L::NROW * LDX + 4 * (e % NPV)) = F::zero();
   if (!is_a && nF > 0) stage(-1, 0, f0, 0);
   __syncthreads();
   // A: gather items of this lane: channels 4 cg .. 4 cg + 3 of class cells (qy, qx = slot)
@@ -1169,9 +1195,11 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
         {
           // the k-phase sums of the four cc at once: row cc of t holds cc's (rows_sum4), lane
           // 16 cc + 4 og + j stores ci 16 (cc & 1) + 4 og .. + 3 of op 32 + j
+          // (registers 1..3 come from the MFMAs that register 0's call has waited for)
           f32x4 t;
+          t[0] = rows_sum4(z4[0][0], z4[1][0], z4[2][0], z4[3][0]);
 #pragma unroll
-          for (int q = 0; q < 4; ++q) t[q] = rows_sum4(z4[0][q], z4[1][q], z4[2][q], z4[3][q]);
+          for (int q = 1; q < 4; ++q) t[q] = rows_sum4<false>(z4[0][q], z4[1][q], z4[2][q], z4[3][q]);
           const int cc = lane >> 4;
           *reinterpret_cast<f32x4*>(zw + (32 + (lane & 3)) * LDZ +
                                     4 * ((8 * (cc >> 1) + 4 * (cc & 1) + ((lane >> 2) & 3)) ^
@@ -1253,8 +1281,8 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
       // channel n (exact in bf16).  Every product is the fp32 product; 16x16x32 bf16 MFMAs take
       // half the cycles of 16x16x4 f32 for 8x the K.  k-block kb = pixel rows 32 kb .. 32 kb + 31
       // (image rows 2 kb, 2 kb + 1); lane group g holds pixels 8 g .. 8 g + 7 of it: dY1 rows
-      // (clamped to the 240 that exist) and 8 consecutive image bytes (funnel-shifted by tx).
-      // The 16 pixels of image row 15 (kb = 7, g >= 2) are padding: their B operand is zero.
+      // and 8 consecutive image bytes (funnel-shifted by tx).
+      // The 16 pixels of image row 15 (kb = 7, g >= 2) are padding: their A operand is zero.
       // Each wave takes two k-blocks of all four taps. ----
       const int b = (it - 1) & 1;
       const float* dyt = dyt_buf(b);
@@ -1266,33 +1294,37 @@ DEV void conv12_bwd_body_f32(const uint8_t* __restrict__ x, const float* __restr
       // the high halves of two fp32 words as a bf16 pair (x0 low, x1 high)
       auto hi2 = [](uint32_t x0, uint32_t x1) { return __builtin_amdgcn_perm(x1, x0, 0x07060302u); };
       // k-blocks kb = 2 wave, 2 wave + 1 of all four taps: per ty, image bytes X = 8 (g & 1)
-      // .. + 8, converted once for both tx; padding pixels take zero image bytes
+      // .. + 8, converted once for both tx
       struct Raw {
         float a[2][8];        // dY1 of oc 16 i + col, pixels 8 g .. 8 g + 7
         uint32_t w[2][3][3];  // [ty][channel tile j] image dwords at X = 8 (g & 1) + {0, 4, 8}
       };
+      // The padding is data, not a test: pixels 240..255 (k-block 7, g >= 2) read the dY1 tile's
+      // zero rows, and their image row (Y = 15 and, under ty = 1, the 20-byte rows past the
+      // image) whatever bytes lie there -- any byte is a finite non-negative float, and +0 times
+      // it is the +0 that the zero byte gave.  Lane offsets once, the k-block's a scalar, the
+      // rest in the instructions' offset fields.
+      static_assert(NKB * 32 == L::NROWP && 4 * (L::IMG + L::IMGW) + (2 * NKB + 2) * c1::CH * XP <= L::BYTES,
+                    "the pad pixels' rows exist");
+      const float* dyl = dyt + 8 * g * LDX + col;
+      const uint8_t* imgl = img + ((g >> 1) * c1::CH + col) * XP + 8 * (g & 1);
       auto load = [&](int kb, Raw& r) {
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const int pr = min(32 * kb + 8 * g + c, L::NROW - 1);
+        for (int c = 0; c < 8; ++c)
 #pragma unroll
-          for (int i = 0; i < 2; ++i) r.a[i][c] = dyt[pr * LDX + 16 * i + col];
-        }
-        const bool pad = kb == NKB - 1 && g >= 2;  // image row 15: zero bytes
+          for (int i = 0; i < 2; ++i) r.a[i][c] = dyl[(32 * kb + c) * LDX + 16 * i];
 #pragma unroll
-        for (int ty = 0; ty < 2; ++ty) {
-          const int Y = min(2 * kb + (g >> 1) + ty, c1::GRID - 1);
+        for (int ty = 0; ty < 2; ++ty)
 #pragma unroll
           for (int j = 0; j < 3; ++j) {
-            const uint32_t* wp = reinterpret_cast<const uint32_t*>(img + (Y * c1::CH + 16 * j + col) * XP + 8 * (g & 1));
+            const uint32_t* wp = reinterpret_cast<const uint32_t*>(imgl + ((2 * kb + ty) * c1::CH + 16 * j) * XP);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) r.w[ty][j][q] = pad ? 0u : wp[q];
+            for (int q = 0; q < 3; ++q) r.w[ty][j][q] = wp[q];
           }
-        }
       };
       Raw rr[2];
-      load(2 * wave, rr[0]);
-      load(2 * wave + 1, rr[1]);
+      load(2 * wu, rr[0]);
+      load(2 * wu + 1, rr[1]);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
         const Raw& r = rr[kk];  // k-block 2 wave + kk

@@ -317,10 +317,14 @@ DEV void gemm_tile_body(const Op& op, int n_rtiles, int vbid, int vgrid, T* __re
         for (int kk = 0; kk < BK; kk += F::KSTEP) {
           V a[TRW], b[TCW];
           frags(kk, a, b);
+          // MFMA e of every accumulator before e + 1 of any (F::mma_e): no fp32 MFMA issues
+          // straight after the one that wrote its accumulator
 #pragma unroll
-          for (int i = 0; i < TRW; ++i)
+          for (int e = 0; e < F::NE; ++e)
 #pragma unroll
-            for (int j = 0; j < TCW; ++j) acc[i][j] = F::mma(a[i], b[j], acc[i][j]);
+            for (int i = 0; i < TRW; ++i)
+#pragma unroll
+              for (int j = 0; j < TCW; ++j) acc[i][j] = F::mma_e(e, a[i], b[j], acc[i][j]);
         }
       }
     }

@@ -279,6 +279,8 @@ DEV void lnc3_body_f32r(const float* __restrict__ dy, const float* __restrict__ 
   float* d3s = reinterpret_cast<float*>(lds + Lnc3F32::D3);
   float (*red)[2] = reinterpret_cast<float (*)[2]>(lds + Lnc3F32::RED);
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wu = __builtin_amdgcn_readfirstlane(wave);  // the wave index as a scalar
+  static_assert(P2 * 16 % 64 == 0, "gather items in whole waves");
   const int f0 = wg * fpw, f1 = min(N, f0 + fpw);
   const int kl = 4 * (lane >> 4);
   const int j0 = 256 * (wave & 3) + 4 * lane, p0 = j0 >> 6, c0 = j0 & 63;
@@ -387,7 +389,8 @@ DEV void lnc3_body_f32r(const float* __restrict__ dy, const float* __restrict__ 
 #pragma unroll
     for (int r = 0; r < NGI; ++r) {
       const int e = t + 512 * r;
-      if (e < P2 * 16) {
+      // (the ragged last pass is whole waves: a scalar branch, no exec mask)
+      if ((r + 1) * 512 <= P2 * 16 || wu < (P2 * 16 - 512 * r) / 64) {
         const int px = e >> 4, ci = 4 * (e & 15), iy = px / H2, ix = px - iy * H2;
         f32x4 zt[9];
 #pragma unroll
