@@ -926,27 +926,31 @@ template <> struct C12BLds<__bf16> {
 template <> struct C12BLds<float> { static constexpr int BYTES = C12B32::BYTES; };
 
 // The W2 fragments of stride-parity class `cls` (conv12_bwd_body_f32's group A wave):
-// B[k = oc][n = ci] = W2[oc][kh][kw][ci] for the class's 4 taps, 16-byte loads from the
-// transposed copy w2t[(kh*4+kw)*32 + ci][oc] (k = oc contiguous)
+// B[k = oc][n = ci] = W2[oc][kh][kw][ci] for the class's 4 taps: wb[t][ks][ct] of lane l holds
+// oc = 16 ks + 4 (l >> 4) .. + 3, ci = 16 ct + (l & 15) of tap t.  16-byte loads from the
+// fragment-major copy w2t (net.h w2t_index): instruction (t * 4 + ks) * 2 + ct of wave cls is
+// 1 KB contiguous, lane l at byte 16 l; a tap is 8 KB, the wave's 32 instructions 32 KB
 DEV void c12_load_w2(const float* __restrict__ w2t, Frag<float>::vec (&wb)[4][OC2 / Frag<float>::KSTEP][2],
                      int cls, int lane, int t0 = 0, int t1 = 4) {  // taps [t0, t1)
   using F = Frag<float>;
   constexpr int KS = F::KSTEP, NKO = OC2 / KS;
-  // 32-bit element offsets from the (uniform) base, from a lane value the compiler cannot hoist:
-  // a caller inside a frame loop would otherwise keep 32 64-bit addresses live across it
+  // the lane's address from a lane value the compiler cannot hoist (a caller inside a frame loop
+  // would otherwise keep the addresses live across it); the instruction's part is a constant,
+  // four loads per 64-bit base with the rest in the immediate offset
   int ln = lane;
   asm volatile("" : "+v"(ln));
-  const int py = cls >> 1, px = cls & 1;
-  const uint32_t o0 = (uint32_t)((ln & 15) * OC2 + 4 * (ln >> 4));
+  static_assert(w2t_index(KS * 2 + 4 * 1 + 3, 1 + 2 * 1, 0 + 2 * 0, 16 * 1 + 5) ==
+                    (((2 * 4 + 2) * NKO + 2) * 2 + 1) * WFRAG + 4 * (16 * 1 + 5) + 3,
+                "w2t: [class][tap of the class][ks][ci tile][lane][q]");
+  const float* wp = w2t + (uint32_t)(cls * 4 * NKO * 2 * WFRAG + 4 * ln);  // the rest are constants
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     if (t < t0 || t >= t1) continue;
-    const int kh = py + 2 * (t >> 1), kw = px + 2 * (t & 1);
 #pragma unroll
     for (int ks = 0; ks < NKO; ++ks)
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct)
-        wb[t][ks][ct] = F::load(w2t + (o0 + (uint32_t)(((kh * KS2 + kw) * OC1 + 16 * ct) * OC2 + ks * KS)));
+        wb[t][ks][ct] = F::load(wp + ((t * NKO + ks) * 2 + ct) * WFRAG);
   }
 }
 
@@ -1717,7 +1721,7 @@ DEV void conv12_bwd_body(const uint8_t* __restrict__ x, const T* __restrict__ w2
 template <typename T>
 __global__ __launch_bounds__(256 * C12_GROUPS) void conv12_bwd_s2d(const uint8_t* __restrict__ x,
                                                       const T* __restrict__ w2,     // [64][512]
-                                                      const T* __restrict__ w2t,    // [512][64] (fp32)
+                                                      const T* __restrict__ w2t,    // fragment-major (fp32, net.h)
                                                       const T* __restrict__ dy2,    // [N][36][64]
                                                       const uint32_t* __restrict__ mask1,  // [N][225]
                                                       float* __restrict__ slab,

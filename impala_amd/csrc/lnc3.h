@@ -260,7 +260,8 @@ DEV void lnc3_body_g(const float* __restrict__ dy, const __bf16* __restrict__ ac
 //           which `pre(k)` loads during the frames, one tap (32 KB per workgroup) in frame
 //           1 + k after that frame's prefetch, so the W3 burst is not delayed and no frame's
 //           loads queue behind all 128 KB (one 128 KB burst in frame 1 made the LayerNorm part
-//           8.4k clocks longer: the CU's load path, not the latency, bounds it);
+//           8.4k clocks longer, measured when a load touched 16 cache lines; a tap's 8 loads per wave
+//           are now 1 KB contiguous each, 1.1k clocks instead of 2.6k, profiles/wfrag);
 //   role 1: the W3 fragments of all nine taps (ci tile = wave & 3), the scatter GEMM, the other
 //           half of the gather.
 // Same sums in the same order as the one-group form.
@@ -302,7 +303,10 @@ DEV void lnc3_body_f32r(const float* __restrict__ dy, const float* __restrict__ 
   };
   if (f0 < f1) fetch(f0);
   float gm[4], dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
-  // W3 fragments of the nine taps (role 1), from the transposed copy w3t[tap*64 + ci][oc]
+  // W3 fragments of the nine taps (role 1): wa[tap][ko] = W3[oc = 16 ko + kl .. + 3][tap]
+  // [ci = 16 ct + (lane & 15)], from the fragment-major copy w3t (net.h w3t_index): instruction
+  // tap * 4 + ko of wave ct is 1 KB contiguous, this lane's 16 bytes at 16 lane, the wave's 36
+  // instructions one after the other (36 KB)
   V wa[LN ? 1 : 9][NKO];
   if constexpr (LN) {
 #pragma unroll
@@ -310,11 +314,15 @@ DEV void lnc3_body_f32r(const float* __restrict__ dy, const float* __restrict__ 
 #pragma unroll
     for (int q = 0; q < 4; ++q) asm volatile("" ::"v"(gm[q]));
   } else {
+    static_assert(w3t_index(KS * 1 + 4 * 2 + 3, 5, 16 * 3 + 7) == ((3 * 9 + 5) * NKO + 1) * WFRAG + 4 * (16 * 2 + 7) + 3,
+                  "w3t: [ci tile][tap][ko][lane][q]");
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const float* wp = w3t + (uint32_t)(ct * 9 * NKO * WFRAG + 4 * ln);  // the rest are constants
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
-      for (int ko = 0; ko < NKO; ++ko)
-        wa[tap][ko] = F::load(w3t + (size_t)(tap * OC2 + 16 * ct + (lane & 15)) * OC3 + ko * KS + kl);
+      for (int ko = 0; ko < NKO; ++ko) wa[tap][ko] = F::load(wp + (tap * NKO + ko) * WFRAG);
   }
   for (int e = t; e < lc3::ZR / 4; e += 512)  // the Z tile's zero row
     *reinterpret_cast<f32x4*>(zs + P3 * lc3::ZR + 4 * e) = f32x4{0.f, 0.f, 0.f, 0.f};

@@ -12,8 +12,10 @@
 //   wh  [16][HID]        rows 0..A-1 actor, row 15 critic, rest 0
 // (the dgrads read w2 / w3 / wfc k-major through LDS: no transposed copies)
 //   wht [HID][32]        [j][o'], o' >= 16 zero
-//   w2t [512][64]        [(kh*4+kw)*32 + ci][oc]   (fp32 only: the dgrads' B fragments as one
-//   w3t [576][64]        [(kh*3+kw)*64 + ci][oc]    16-byte load, k = oc contiguous)
+//   w2t [4][16][64][4]   fp32 only: the dgrads' B fragments (k = oc) in the order the waves load
+//   w3t [4][36][64][4]   them, [wave][instruction][lane][q]: one wave instruction reads 1 KB
+//                        contiguous, lane l its 16 bytes at 16 l, and a wave's instructions follow
+//                        each other (w2t_index / w3t_index below; loaders c12_load_w2, lnc3.h)
 //   f32: b1[32] b2[64] b3[64] lng[1024] lnb[1024] (p*64+c order) bfc[HID] bh[16]
 //
 // HID, the width of the projection after the LayerNorm, is a template parameter of everything
@@ -93,6 +95,28 @@ template <int HID> inline Shadow shadow_t() {
 }
 inline Shadow shadow() { return shadow_t<HID_AC>(); }
 inline Shadow shadow_dqn() { return shadow_t<HID_DQN>(); }
+// Fragment-major element positions in w2t / w3t.  A lane of a 16x16x4 fp32 B fragment holds, for
+// k-step ks over oc, the 4 values oc = 16 ks + 4 (lane >> 4) + q of input channel
+// ci = 16 ct + (lane & 15); position = (instruction * 64 + lane) * 4 + q.
+//   w2t: wave cls = (kh & 1) * 2 + (kw & 1) (stride-parity class), instruction
+//        ((t * 4 + ks) * 2 + ct), t = (kh >> 1) * 2 + (kw >> 1): a tap is 8 KB contiguous
+//   w3t: wave ct (ci tile), instruction tap * 4 + ks, tap = kh * 3 + kw
+constexpr int WFRAG = 256;  // elements of one wave instruction (64 lanes x 16 bytes)
+#if defined(__HIPCC__)
+#define NET_HD __host__ __device__
+#else
+#define NET_HD  // a host compiler (tests/wfrag_check.cpp)
+#endif
+NET_HD constexpr int wfrag_lane(int oc, int ci) {
+  return ((((oc >> 2) & 3) * 16 + (ci & 15)) << 2) + (oc & 3);
+}
+NET_HD constexpr int w2t_index(int oc, int kh, int kw, int ci) {
+  return ((((((kh & 1) * 2 + (kw & 1)) * 4 + (kh >> 1) * 2 + (kw >> 1)) * 4 + (oc >> 4)) * 2 + (ci >> 4)) *
+          WFRAG) + wfrag_lane(oc, ci);
+}
+NET_HD constexpr int w3t_index(int oc, int tap, int ci) {
+  return (((ci >> 4) * 9 + tap) * 4 + (oc >> 4)) * WFRAG + wfrag_lane(oc, ci);
+}
 // fp32 side vector (biases, LayerNorm affine) offsets
 template <int HID> struct VecsT {
   static constexpr size_t b1 = 0, b2 = 64, b3 = 128, lng = 192, lnb = 192 + 1024,
