@@ -1,13 +1,16 @@
 // hostpool.h — a small host thread pool for the staging ring's host-side collate
 // (impala_stage_rows): B trajectories scattered in host memory are copied into the slot's
 // page-locked block by several threads at once, since one thread's memcpy moves the 15.7 MB of
-// a C2 batch in ~1 ms (below PCIe's 0.3 ms for the same bytes).  Host code only.
+// a C2 batch in ~1 ms (below PCIe's 0.3 ms for the same bytes).  Also the staged batch's byte
+// layout (StageLayout) and the collate itself (collate_rows).  Host code only: no HIP includes,
+// so tests/hostpool_check.cpp checks all of it without a GPU.
 #pragma once
 
 #include <pthread.h>
 #include <sched.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -54,7 +57,7 @@ inline void copy_stream(char* dst, const char* src, size_t n) {
 }
 
 // The CPUs of a NUMA node, within the process's affinity set (empty when the topology cannot be
-// read): where the staging threads run (impala_stage_rows_async; impala.hip stage_cpus).
+// read): where the staging threads run (impala_stage_rows_async; stage.h stage_cpus).
 // node < 0: the node of the CPU the calling thread runs on
 inline std::vector<int> local_node_cpus(int node = -1) {
   std::vector<int> out;
@@ -176,6 +179,57 @@ class HostPool {
   uint64_t gen_ = 0;
   bool stop_ = false;
 };
+
+// The byte layout of a staged batch of B trajectories of T frames: obs | actions | rewards |
+// discounts | behaviour logits in one block, each field at a 256-byte aligned offset.  A device
+// slot, a slot's page-locked host block and the priming scratch batch are all laid out by it.
+struct StageLayout {
+  enum { OBS = 0, ACTIONS, REWARDS, DISCOUNTS, LOGITS, kFields };
+  size_t row[kFields] = {};      // bytes of one trajectory's field
+  size_t bytes[kFields] = {};    // bytes of the batch's field (B rows)
+  size_t off[kFields + 1] = {};  // the field's offset in the block; off[kFields] = block size
+  StageLayout() = default;
+  StageLayout(size_t B, size_t T, size_t A) {
+    const size_t frame[kFields] = {3 * 64 * 64, 8, 4, 4, A * 4};
+    for (int f = 0; f < kFields; ++f) {
+      row[f] = T * frame[f];
+      bytes[f] = B * row[f];
+      off[f + 1] = off[f] + ((bytes[f] + 255) & ~(size_t)255);
+    }
+  }
+};
+
+// The host collate of impala_stage_rows: rows[f][b] is trajectory b's field f (n trajectories),
+// copied to dst + L.off[f] + b * L.row[f].  Obs rows go in 64 KB pieces through copy_stream,
+// each small field is one task; rows[DISCOUNTS] may be null (PPO handles), and that region of
+// dst is then left alone.  The tasks run on `pool` and the calling thread, or serially when
+// pool is null.
+inline void collate_rows(const StageLayout& L, const void* const* const rows[StageLayout::kFields],
+                         int n, char* dst, HostPool* pool) {
+  constexpr size_t kPiece = 65536;
+  const size_t orow = L.row[StageLayout::OBS];
+  const int per_row = (int)((orow + kPiece - 1) / kPiece);
+  const int n_obs_tasks = per_row * n;
+  const std::function<void(int)> task = [&](int i) {
+    if (i < n_obs_tasks) {
+      const int b = i / per_row;
+      const size_t o = (size_t)(i - b * per_row) * kPiece, len = std::min(kPiece, orow - o);
+      copy_stream(dst + L.off[StageLayout::OBS] + (size_t)b * orow + o,
+                  (const char*)rows[StageLayout::OBS][b] + o, len);
+      return;
+    }
+    const int f = 1 + (i - n_obs_tasks);
+    if (!rows[f]) return;
+    for (int b = 0; b < n; ++b)
+      std::memcpy(dst + L.off[f] + (size_t)b * L.row[f], rows[f][b], L.row[f]);
+  };
+  const int ntasks = n_obs_tasks + (StageLayout::kFields - 1);
+  if (pool) {
+    pool->run(ntasks, task);
+  } else {
+    for (int i = 0; i < ntasks; ++i) task(i);
+  }
+}
 
 // One background thread that runs staging jobs in order (impala_stage_rows_async): the caller
 // hands over a job and returns at once; `pending(slot)` jobs per slot are waited for by the

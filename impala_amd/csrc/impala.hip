@@ -98,6 +98,8 @@ Split plan_split(long M, int tiles, int target_wgs, int chunk = 64) {
 
 }  // namespace
 
+#include "stage.h"
+
 // kernel ids for the live launch timer (impala_timer_*)
 enum KernelId {
   K_CONV1_FWD = 0, K_CONV2_FWD, K_CONV12_FWD, K_CONV3_FWD, K_FC_FWD, K_HEADS_FWD, K_HEAD_STEP, K_FC_DGRAD,
@@ -181,36 +183,7 @@ struct impala_learner {
   hipStream_t cap = nullptr;
   bool use_graph = false;
   uint64_t graph_tick = 0;
-  // host staging ring (impala_stage*): device batch slots filled by H2D copies on `h2d`;
-  // `ready` = the slot's copies are done, `done` = the steps that read it are done
-  struct StageSlot {
-    char* mem = nullptr;
-    impala_batch dev{};
-    hipEvent_t ready = nullptr, done = nullptr;
-    // impala_stage_rows: the slot's page-locked host block (obs, then the four small fields,
-    // impala_stage's layout), allocated at the first row-staging into the slot
-    char* host_blk = nullptr;
-  };
-  static constexpr int kMaxStageSlots = 8;
-  StageSlot ring[kMaxStageSlots];
-  int n_slots = 0;
-  // copy streams: IMPALA_H2D_STREAMS > 1 splits the obs block over several streams (stream 0
-  // joins the others and signals `ready`); see impala_stage_init for the measured defaults
-  static constexpr int kMaxH2D = 8;
-  hipStream_t h2d_s[kMaxH2D] = {};
-  hipEvent_t h2d_join[kMaxH2D] = {};
-  int n_h2d = 0;
-  int h2d_pull_wg = 0;        // > 0: copy everything with h2d_pull_kernel on that many workgroups
-  int h2d_pull_threads = 256; // threads per pull workgroup (IMPALA_H2D_THREADS)
-  bool h2d_small_pull = true; // SDMA obs: the four small fields in one 1-workgroup pull launch
-  hipStream_t h2d = nullptr;  // = h2d_s[0]
-  // impala_stage_rows: 0 = collate the rows into the slot's host block with the thread pool,
-  // then impala_stage's copies; 1 = one SDMA copy per obs row straight from its memory
-  // (IMPALA_STAGE_ROWS=collate|rows; IMPALA_STAGE_THREADS = pool threads).  (The batched copy
-  // API, hipMemcpyBatchAsync, is newer than the HIP runtime torch loads.)
-  int stage_rows_mode = 0;
-  impala_host::HostPool* pool = nullptr;
-  impala_host::Stager* stager = nullptr;  // impala_stage_rows_async's thread (lazily started)
+  StageRing stage;  // host staging ring (impala_stage*, impala_slot_*): csrc/stage.h
   // native data-parallel step (impala_dp_*): the library's own RCCL communicator, so the
   // gradient all-reduces are enqueued with no host round trip and no c10d bookkeeping; the FC +
   // heads bucket is all-reduced on dp_stream while the per-frame backward runs
@@ -567,75 +540,6 @@ void drop_graphs(impala_learner* h) {
   }
 }
 
-// The staging rings' copy streams, shared by every handle on a device that asks for the same
-// number: a process's streams share GPU_MAX_HW_QUEUES (4) hardware queues, and each handle's own
-// pair of copy streams took a share of them (a second handle's staging ran at 0.42 instead of
-// 0.30 ms per step beside the first's, profiles/r06w).  Reference-counted; the last handle's
-// release destroys them.
-struct SharedH2D {
-  int device = -1, n = 0, refs = 0;
-  hipStream_t s[impala_learner::kMaxH2D] = {};
-};
-std::mutex g_h2d_mu;
-SharedH2D g_h2d[16];
-
-int acquire_h2d(impala_learner* h, int n) {
-  std::lock_guard<std::mutex> lk(g_h2d_mu);
-  SharedH2D* e = nullptr;
-  for (auto& x : g_h2d)
-    if (x.refs > 0 && x.device == h->device && x.n == n) e = &x;
-  if (!e) {
-    for (auto& x : g_h2d)
-      if (x.refs == 0) {
-        e = &x;
-        break;
-      }
-    if (!e) return fail(IMPALA_E_STATE, "impala_stage_init: too many staging stream sets");
-    e->device = h->device;
-    e->n = 0;
-    for (int i = 0; i < n; ++i) {
-      if (hipStreamCreateWithFlags(&e->s[i], hipStreamNonBlocking) != hipSuccess) {
-        for (int j = 0; j < i; ++j) (void)hipStreamDestroy(e->s[j]);
-        return fail(IMPALA_E_STATE, "impala_stage_init: hipStreamCreate failed");
-      }
-    }
-    e->n = n;
-  }
-  ++e->refs;
-  for (int i = 0; i < n; ++i) h->h2d_s[i] = e->s[i];
-  return 0;
-}
-
-void release_h2d(impala_learner* h) {
-  if (!h->n_h2d) return;
-  std::lock_guard<std::mutex> lk(g_h2d_mu);
-  for (auto& x : g_h2d)
-    if (x.refs > 0 && x.device == h->device && x.n == h->n_h2d && x.s[0] == h->h2d_s[0]) {
-      if (--x.refs == 0) {
-        for (int i = 0; i < x.n; ++i) (void)hipStreamDestroy(x.s[i]);
-        x = SharedH2D{};
-      }
-      break;
-    }
-}
-
-void free_ring(impala_learner* h) {
-  if (h->stager) {  // no staging job may still be writing into the ring
-    std::string m;
-    (void)h->stager->wait(-1, m);
-  }
-  for (int i = 0; i < h->n_h2d; ++i) (void)hipStreamSynchronize(h->h2d_s[i]);
-  for (auto& s : h->ring) {
-    if (s.done) (void)hipEventSynchronize(s.done);
-    if (s.ready) (void)hipEventDestroy(s.ready);
-    if (s.done) (void)hipEventDestroy(s.done);
-    if (s.mem) (void)hipFree(s.mem);
-    if (s.host_blk) (void)hipHostFree(s.host_blk);
-    s = impala_learner::StageSlot{};
-  }
-  h->n_slots = 0;
-}
-
 int check_bound(impala_learner* h, bool train = true) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
   if (!h->params) return fail(IMPALA_E_STATE, "impala_bind_state() not called");
@@ -956,18 +860,13 @@ int impala_destroy(impala_learner* h) {
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();  // replays may still be in flight on the caller's streams
   drop_graphs(h);
-  free_ring(h);
-  release_h2d(h);  // (the shared copy streams; the join events are the handle's)
-  for (int i = 0; i < h->n_h2d; ++i)
-    if (h->h2d_join[i]) (void)hipEventDestroy(h->h2d_join[i]);
+  stage_destroy(h->stage);
   for (auto& t : h->timers) {
     for (int i = 0; i < 2 * t.cap; ++i) (void)hipEventDestroy(t.ev[i]);
     delete[] t.ev;
   }
   if (h->cap) (void)hipStreamDestroy(h->cap);
   dp_release(h);
-  delete h->stager;  // (free_ring above already waited for its jobs)
-  delete h->pool;
   if (h->ws) (void)hipFree(h->ws);
   delete h;
   return 0;
@@ -1367,292 +1266,25 @@ int impala_gather_rows_hidx(const void* const* src, void* const* dst, const size
   return 0;
 }
 
-// Prime the copy path at init: the learner's staging loop (ImpalaLearner._stage_host) for
-// IMPALA_STAGE_PRIME rounds (default 24, 0 = off) in each of two shapes on a page-locked scratch batch, with a
-// 250 us spin kernel on a private stream standing in for each step.  An H2D hipMemcpyAsync is
-// given an SDMA engine by the runtime at issue time (hsa_amd_memory_get_preferred_copy_engine /
-// copy_engine_status, then hsa_amd_memory_async_copy_on_engine), and the first copy given an
-// engine creates that engine's queue inside the call: a 6-9 ms host stall before the copy is
-// submitted (HIP + HSA API traces, profiles/r05d; hsa_queue_create alone takes 6-6.5 ms here).
-// Which engines a loop gets depends on what is in flight and waiting when it issues (copies
-// queued behind the previous step's events), so rounds of copies with nothing to wait for did
-// not reach them (r05c, r05e); in the driver's 20-step host-staged pass one such stall landed
-// in the timed steps (0.67 ms per step against a 0.30 ms median, profiles/r05a).
-int prime_copy_path(impala_learner* h) {
-  int rounds = 24;
-  if (const char* e = std::getenv("IMPALA_STAGE_PRIME")) rounds = std::max(0, std::atoi(e));
-  if (rounds == 0 || h->n_slots < 2) return 0;
-  const size_t N = (size_t)h->N;
-  const size_t sz[5] = {N * 3 * 64 * 64, N * 8, N * 4, N * 4, N * (size_t)h->A * 4};
-  size_t total = 0;
-  for (size_t b : sz) total += (b + 255) & ~(size_t)255;
-  char* scratch = nullptr;
-  CK(hipHostMalloc((void**)&scratch, total, hipHostMallocDefault));
-  std::memset(scratch, 0, total);
-  impala_batch hb{};
-  {
-    size_t o = 0;
-    const void* p[5];
-    for (int f = 0; f < 5; ++f) {
-      p[f] = scratch + o;
-      o += (sz[f] + 255) & ~(size_t)255;
-    }
-    hb = impala_batch{(const uint8_t*)p[0], (const int64_t*)p[1], (const float*)p[2],
-                      (const float*)p[3], (const float*)p[4]};
-  }
-  hipStream_t cs = nullptr;
-  hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
-  int r = e == hipSuccess ? impala_stage(h, &hb, 0) : (int)e;
-  for (int k = 0; k < rounds && r == 0 && e == hipSuccess; ++k) {
-    const int s = k & 1;
-    e = hipEventSynchronize(h->ring[1 - s].ready);             // stage_wait(1 - s)
-    if (e == hipSuccess) r = impala_stage(h, &hb, 1 - s);      // stage(1 - s)
-    if (r == 0 && e == hipSuccess) e = hipStreamWaitEvent(cs, h->ring[s].ready, 0);  // slot_batch(s)
-    if (r == 0 && e == hipSuccess) {
-      stage_prime_spin_kernel<<<1, 64, 0, cs>>>(25000);      // the "step" (250 us)
-      e = hipGetLastError();
-    }
-    if (r == 0 && e == hipSuccess) e = hipEventRecord(h->ring[s].done, cs);  // slot_release(s)
-  }
-  // ... then the same rounds over every slot with the host running ahead, as a loop that reads
-  // its metrics only every k steps does (DistributedAgent sync_every > 1): the host waits only
-  // for a slot's previous copy (the collate's wait before it rewrites the slot's host block), so
-  // every copy is queued behind the event of a step still two slots back.  Without this phase
-  // that loop met one 7 ms queue-creation stall in its first dozen steps (profiles/r06y).
-  for (int k = 0; k < rounds && r == 0 && e == hipSuccess; ++k) {
-    const int s = k % h->n_slots;
-    e = hipEventSynchronize(h->ring[s].ready);
-    if (e == hipSuccess) r = impala_stage(h, &hb, s);
-    if (r == 0 && e == hipSuccess) e = hipStreamWaitEvent(cs, h->ring[s].ready, 0);
-    if (r == 0 && e == hipSuccess) {
-      stage_prime_spin_kernel<<<1, 64, 0, cs>>>(25000);
-      e = hipGetLastError();
-    }
-    if (r == 0 && e == hipSuccess) e = hipEventRecord(h->ring[s].done, cs);
-  }
-  if (cs) {
-    const hipError_t es = hipStreamSynchronize(cs);
-    if (e == hipSuccess) e = es;
-  }
-  for (int i = 0; i < h->n_h2d; ++i) {
-    const hipError_t es = hipStreamSynchronize(h->h2d_s[i]);
-    if (e == hipSuccess) e = es;
-  }
-  // leave the ring as stage_init's allocation loop does: both events recorded (complete) on
-  // h2d, none referring to work of the private stream about to be destroyed
-  for (int i = 0; i < h->n_slots && e == hipSuccess; ++i) {
-    e = hipEventRecord(h->ring[i].ready, h->h2d);
-    if (e == hipSuccess) e = hipEventRecord(h->ring[i].done, h->h2d);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(h->h2d);
-  if (cs) (void)hipStreamDestroy(cs);
-  (void)hipHostFree(scratch);
-  if (r) return r;
-  if (e != hipSuccess)
-    return fail((int)e, std::string("impala_stage_init (copy-path priming): ") + hipGetErrorString(e));
-  return 0;
-}
-
 int impala_stage_init(impala_learner* h, int nslots) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
-  if (nslots < 1 || nslots > impala_learner::kMaxStageSlots)
+  if (nslots < 1 || nslots > StageRing::kMaxSlots)
     return fail(IMPALA_E_INVALID, "nslots must be in [1, 8]");
-  CK(hipSetDevice(h->device));
-  free_ring(h);
-  if (!h->n_h2d) {
-    // Default: hipMemcpyAsync (SDMA) of obs split over 2 streams, the four small fields in one
-    // small pull launch.  Beside the fp32 step (profiles/r04hs: H2D bandwidth A/B) SDMA on
-    // 1 / 2 / 4 streams kept 41-43 / 46.4 / 43.9 GB/s, while the pull kernel (8 x 256 threads,
-    // 45-48 GB/s alone and the round-1 default) fell to 36 GB/s and slowed the trunk forward it
-    // shares CUs with from 63 to 190-210 us (rocprofv3 kernel trace, r04hs).
-    // IMPALA_H2D_KERNEL=<workgroups> copies everything with the pull kernel instead.
-    // Data-parallel handles (world_size > 1) never use the pull kernel unless asked: whether
-    // every device of a node maps a rank's page-locked buffers is not something this library
-    // checks.
-    h->h2d_pull_wg = 0;
-    if (const char* e = std::getenv("IMPALA_H2D_KERNEL")) h->h2d_pull_wg = std::max(0, std::atoi(e));
-    if (const char* e = std::getenv("IMPALA_H2D_THREADS"))
-      h->h2d_pull_threads = std::max(64, std::min(1024, std::atoi(e) / 64 * 64));
-    h->h2d_small_pull = h->cfg.world_size == 1;
-    if (const char* e = std::getenv("IMPALA_H2D_SMALL_PULL")) h->h2d_small_pull = e[0] == '1';
-    if (const char* e = std::getenv("IMPALA_STAGE_ROWS"))
-      h->stage_rows_mode = std::strcmp(e, "rows") == 0 ? 1 : 0;
-    int n = h->h2d_pull_wg > 0 ? 1 : 2;
-    if (const char* e = std::getenv("IMPALA_H2D_STREAMS")) n = std::atoi(e);
-    n = std::max(1, std::min(n, (int)impala_learner::kMaxH2D));
-    if (int r = acquire_h2d(h, n)) return r;
-    h->n_h2d = n;
-    for (int i = 0; i < n; ++i) CK(hipEventCreateWithFlags(&h->h2d_join[i], hipEventDisableTiming));
-    h->h2d = h->h2d_s[0];
-  }
-  const size_t N = (size_t)h->N;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_obs = take(N * 3 * 64 * 64), o_act = take(N * 8), o_rew = take(N * 4),
-               o_disc = take(N * 4), o_mu = take(N * (size_t)h->A * 4);
-  for (int i = 0; i < nslots; ++i) {
-    auto& s = h->ring[i];
-    hipError_t e = hipMalloc(&s.mem, off);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ready, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
-    // both events start recorded (complete), so the first stage / slot_batch never waits
-    if (e == hipSuccess) e = hipEventRecord(s.ready, h->h2d);
-    if (e == hipSuccess) e = hipEventRecord(s.done, h->h2d);
-    if (e != hipSuccess) {
-      free_ring(h);
-      return fail((int)e, std::string("impala_stage_init: ") + hipGetErrorString(e));
-    }
-    s.dev = impala_batch{(const uint8_t*)(s.mem + o_obs), (const int64_t*)(s.mem + o_act),
-                         (const float*)(s.mem + o_rew), (const float*)(s.mem + o_disc),
-                         (const float*)(s.mem + o_mu)};
-  }
-  h->n_slots = nslots;
-  if (h->h2d_pull_wg == 0) {
-    if (int r = prime_copy_path(h)) {
-      free_ring(h);
-      return r;
-    }
-  }
-  return 0;
+  return stage_init(h->stage, h->device, h->cfg, nslots);
 }
-
-namespace {
-// Where the staging threads run (IMPALA_STAGE_PIN): "gpu" (default) the CPUs of the NUMA node
-// the device's PCIe link hangs off, so the page-locked blocks they first touch and fill sit
-// next to the DMA engines that read them; "caller" the calling thread's node; "0" anywhere.
-std::vector<int> stage_cpus(const impala_learner* h) {
-  const char* pin = std::getenv("IMPALA_STAGE_PIN");
-  if (pin && pin[0] == '0') return {};
-  if (pin && std::strcmp(pin, "caller") == 0) return impala_host::local_node_cpus();
-  char bus[64] = {};
-  int node = -1;
-  if (hipDeviceGetPCIBusId(bus, sizeof(bus), h->device) == hipSuccess) {
-    for (char* c = bus; *c; ++c) *c = (char)std::tolower((unsigned char)*c);
-    const std::string path = std::string("/sys/bus/pci/devices/") + bus + "/numa_node";
-    if (FILE* f = std::fopen(path.c_str(), "r")) {
-      if (std::fscanf(f, "%d", &node) != 1) node = -1;
-      std::fclose(f);
-    }
-  } else {
-    (void)hipGetLastError();
-  }
-  return impala_host::local_node_cpus(node);  // (node -1: the caller's)
-}
-
-// the staging jobs of `slot` (every slot when < 0) queued by impala_stage_rows_async have run;
-// a failed one's status is returned here
-int wait_staged(impala_learner* h, int slot) {
-  if (!h->stager) return 0;
-  std::string m;
-  if (int r = h->stager->wait(slot, m)) return fail(r, "impala_stage_rows_async: " + m);
-  return 0;
-}
-}  // namespace
-
-namespace {
-int stage_now(impala_learner* h, const impala_batch* b, int slot);
-}  // namespace
 
 int impala_stage(impala_learner* h, const impala_batch* b, int slot) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
-  if (slot < 0 || slot >= h->n_slots)
+  if (slot < 0 || slot >= h->stage.n_slots)
     return fail(IMPALA_E_INVALID, "slot out of range (impala_stage_init not called?)");
-  if (int r = wait_staged(h, -1)) return r;  // one staging at a time per handle
-  return stage_now(h, b, slot);
+  if (int r = wait_staged(h->stage, -1)) return r;  // one staging at a time per handle
+  return stage_now(h->stage, b, slot);
 }
 
-namespace {
-// impala_stage's copies (also run by the staging thread's jobs, which must not wait on
-// themselves)
-int stage_now(impala_learner* h, const impala_batch* b, int slot) {
-  const bool ppo = h->cfg.algo == IMPALA_ALGO_PPO;
-  if (!b || !b->obs || !b->actions || !b->rewards || (!ppo && !b->discounts) ||
-      !b->behaviour_logits)
-    return fail(IMPALA_E_INVALID, "null batch pointer");
-  CK(hipSetDevice(h->device));
-  auto& s = h->ring[slot];
-  const size_t N = (size_t)h->N;
-  const int ns = h->n_h2d;
-  for (int i = 0; i < ns; ++i)  // the steps that read the slot have run
-    CK(hipStreamWaitEvent(h->h2d_s[i], s.done, 0));
-  // the pull kernel reads page-locked, device-mapped host fields (hipHostGetDevicePointer);
-  // anything else takes hipMemcpyAsync
-  const void* hsrc[5] = {b->obs, b->actions, b->rewards, b->discounts, b->behaviour_logits};
-  const void* msrc[5] = {};
-  bool mapped = h->h2d_pull_wg > 0 || h->h2d_small_pull;
-  for (int f = 0; f < 5 && mapped; ++f) {
-    if (!hsrc[f]) continue;
-    void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, const_cast<void*>(hsrc[f]), 0) != hipSuccess || !dp ||
-        (((uintptr_t)dp) & 15) != 0) {
-      (void)hipGetLastError();
-      mapped = false;
-    }
-    msrc[f] = dp;
-  }
-  void* dst[5] = {(void*)s.dev.obs, (void*)s.dev.actions, (void*)s.dev.rewards,
-                  (void*)s.dev.discounts, (void*)s.dev.behaviour_logits};
-  const size_t bytes[5] = {N * 3 * 64 * 64, N * 8, N * 4, N * 4, N * (size_t)h->A * 4};
-  auto pull = [&](int f_lo, int wgs, int threads) -> int {
-    PullArgs pa{};
-    for (int f = f_lo; f < 5; ++f) {
-      if (!msrc[f]) continue;
-      pa.src[pa.nf] = (const char*)msrc[f];
-      pa.dst[pa.nf] = (char*)dst[f];
-      pa.bytes[pa.nf] = (long long)bytes[f];
-      ++pa.nf;
-    }
-    h2d_pull_kernel<<<wgs, threads, 0, h->h2d>>>(pa);
-    CK_LAUNCH("h2d_pull");
-    return 0;
-  };
-  if (mapped && h->h2d_pull_wg > 0) {
-    if (int r = pull(0, h->h2d_pull_wg, h->h2d_pull_threads)) return r;
-  } else {
-    // the small fields first on stream 0 (one pull launch, or four copies), then obs in ns
-    // contiguous chunks, one per copy stream
-    if (mapped && h->h2d_small_pull) {
-      // 8 workgroups, one per XCD: ~100 KB at PCIe latency (one workgroup took 37-42 us,
-      // delaying the obs chunk behind it on the stream; rocprofv3 trace, r04hs3)
-      if (int r = pull(1, 8, 256)) return r;
-    } else {
-      CK(hipMemcpyAsync(dst[1], b->actions, bytes[1], hipMemcpyDefault, h->h2d));
-      CK(hipMemcpyAsync(dst[2], b->rewards, bytes[2], hipMemcpyDefault, h->h2d));
-      if (b->discounts) CK(hipMemcpyAsync(dst[3], b->discounts, bytes[3], hipMemcpyDefault, h->h2d));
-      CK(hipMemcpyAsync(dst[4], b->behaviour_logits, bytes[4], hipMemcpyDefault, h->h2d));
-    }
-    const size_t ob = bytes[0], chunk = (ob / ns + 4095) & ~(size_t)4095;
-    for (int i = 0; i < ns; ++i) {
-      const size_t o0 = std::min(ob, (size_t)i * chunk), o1 = std::min(ob, o0 + chunk);
-      if (o1 > o0)
-        CK(hipMemcpyAsync((char*)s.dev.obs + o0, b->obs + o0, o1 - o0, hipMemcpyDefault, h->h2d_s[i]));
-    }
-  }
-  for (int i = 1; i < ns; ++i) {
-    CK(hipEventRecord(h->h2d_join[i], h->h2d_s[i]));
-    CK(hipStreamWaitEvent(h->h2d, h->h2d_join[i], 0));
-  }
-  CK(hipEventRecord(s.ready, h->h2d));
-  return 0;
-}
-}  // namespace
-
-// Row staging (impala_stage_rows): the batch is B trajectories scattered in host memory (the
-// replay's rows), not one collated host batch.  Default (collate): the host's thread pool
-// copies the rows into the slot's page-locked block -- obs, then the four small fields, in
-// impala_stage's layout -- and impala_stage's copies follow (obs over the SDMA streams, the
-// small fields in one pull launch).  One thread's memcpy moves the 15.7 MB of a C2 batch in
-// ~1 ms, over three times the PCIe copy it feeds; the pool's threads share it.  The rows modes
-// instead copy each obs row by SDMA straight from its own memory (runs of adjacent rows merged)
-// and collate only the small fields.
 namespace {
 int check_rows(impala_learner* h, const impala_rows* rows, int n, int slot) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
-  if (slot < 0 || slot >= h->n_slots)
+  if (slot < 0 || slot >= h->stage.n_slots)
     return fail(IMPALA_E_INVALID, "slot out of range (impala_stage_init not called?)");
   const bool ppo = h->cfg.algo == IMPALA_ALGO_PPO;
   if (!rows || n != h->cfg.batch_size)
@@ -1666,21 +1298,21 @@ int check_rows(impala_learner* h, const impala_rows* rows, int n, int slot) {
       return fail(IMPALA_E_INVALID, "impala_stage_rows: null row pointer");
   return 0;
 }
-int stage_rows_now(impala_learner* h, const impala_rows* rows, int n, int slot);
 }  // namespace
 
 int impala_stage_rows(impala_learner* h, const impala_rows* rows, int n, int slot) {
   if (int r = check_rows(h, rows, n, slot)) return r;
-  if (int r = wait_staged(h, -1)) return r;  // one staging at a time per handle
-  return stage_rows_now(h, rows, n, slot);
+  if (int r = wait_staged(h->stage, -1)) return r;  // one staging at a time per handle
+  return stage_rows_now(h->stage, rows, n, slot);
 }
 
 int impala_stage_rows_async(impala_learner* h, const impala_rows* rows, int n, int slot) {
   if (int r = check_rows(h, rows, n, slot)) return r;
-  if (int r = wait_staged(h, slot)) return r;  // the slot's previous job
-  if (!h->stager) {
-    h->stager = new (std::nothrow) impala_host::Stager(stage_cpus(h));
-    if (!h->stager) return fail(IMPALA_E_STATE, "impala_stage_rows_async: staging thread");
+  StageRing* ring = &h->stage;
+  if (int r = wait_staged(*ring, slot)) return r;  // the slot's previous job
+  if (!ring->stager) {
+    ring->stager = new (std::nothrow) impala_host::Stager(stage_cpus(ring->device));
+    if (!ring->stager) return fail(IMPALA_E_STATE, "impala_stage_rows_async: staging thread");
   }
   // the job owns copies of the five pointer arrays; the rows themselves stay the caller's
   auto p = std::make_shared<std::vector<const void*>>();
@@ -1689,145 +1321,39 @@ int impala_stage_rows_async(impala_learner* h, const impala_rows* rows, int n, i
                              rows->behaviour_logits};
   for (int k = 0; k < 5; ++k)
     for (int b = 0; b < n; ++b) p->push_back(f[k] ? f[k][b] : nullptr);
-  h->stager->submit(slot, [h, p, n, slot](std::string& msg) {
+  ring->stager->submit(slot, [ring, p, n, slot](std::string& msg) {
     const void* const* d = p->data();
     const impala_rows r{d, d + n, d + 2 * n, d[3 * n] ? d + 3 * n : nullptr, d + 4 * n};
-    const int st = stage_rows_now(h, &r, n, slot);
+    const int st = stage_rows_now(*ring, &r, n, slot);
     if (st) msg = impala_last_error();
     return st;
   });
   return 0;
 }
 
-namespace {
-int stage_rows_now(impala_learner* h, const impala_rows* rows, int n, int slot) {
-  const bool ppo = h->cfg.algo == IMPALA_ALGO_PPO;
-  CK(hipSetDevice(h->device));
-  auto& s = h->ring[slot];
-  const size_t T = (size_t)h->cfg.rollout_length, N = (size_t)h->N, A = (size_t)h->A;
-  const size_t rb[5] = {T * 3 * 64 * 64, T * 8, T * 4, T * 4, T * A * 4};
-  // host block layout: obs | actions | rewards | discounts | behaviour logits (256-B aligned)
-  size_t off[6];
-  off[0] = 0;
-  for (int f = 0; f < 5; ++f) off[f + 1] = off[f] + ((N * rb[f] / T + 255) & ~(size_t)255);
-  if (!s.host_blk) {
-    void* p = nullptr;
-    // IMPALA_STAGE_HOSTMEM=1: mapped + portable (the round-6 first form); default flags
-    // otherwise (as torch's page-locked tensors, which impala_stage copies from)
-    const char* hm = std::getenv("IMPALA_STAGE_HOSTMEM");
-    const unsigned flags = hm && hm[0] == '1' ? (hipHostMallocMapped | hipHostMallocPortable)
-                                              : hipHostMallocDefault;
-    CK(hipHostMalloc(&p, off[5], flags));
-    s.host_blk = (char*)p;
-  }
-  // the slot's previous copies (out of its host block too) have finished before it is rewritten
-  CK(hipEventSynchronize(s.ready));
-  const void* const* src[5] = {rows->obs, rows->actions, rows->rewards, rows->discounts,
-                               rows->behaviour_logits};
-  char* hb = s.host_blk;
-  const bool collate = h->stage_rows_mode == 0;
-  // host copies: obs rows in 64 KB pieces (collate mode), each small field as one task
-  constexpr size_t kPiece = 65536;
-  const int per_row = collate ? (int)((rb[0] + kPiece - 1) / kPiece) : 0;
-  const int n_obs_tasks = per_row * n;
-  auto task = [&](int i) {
-    if (i < n_obs_tasks) {
-      const int b = i / per_row;
-      const size_t o = (size_t)(i - b * per_row) * kPiece, len = std::min(kPiece, rb[0] - o);
-      impala_host::copy_stream(hb + (size_t)b * rb[0] + o, (const char*)src[0][b] + o, len);
-      return;
-    }
-    const int f = 1 + (i - n_obs_tasks);
-    if (f == 3 && ppo) return;
-    for (int b = 0; b < n; ++b) std::memcpy(hb + off[f] + (size_t)b * rb[f], src[f][b], rb[f]);
-  };
-  const int ntasks = n_obs_tasks + 4;
-  if (collate && !h->pool) {
-    int nt = 7;
-    if (const char* e = std::getenv("IMPALA_STAGE_THREADS")) nt = std::max(0, std::atoi(e) - 1);
-    h->pool = new (std::nothrow) impala_host::HostPool(nt, stage_cpus(h));
-    if (!h->pool) return fail(IMPALA_E_STATE, "impala_stage_rows: thread pool");
-  }
-  if (h->pool && collate) {
-    h->pool->run(ntasks, task);
-  } else {
-    for (int i = 0; i < ntasks; ++i) task(i);
-  }
-  if (collate) {
-    const impala_batch hbat{(const uint8_t*)(hb + off[0]), (const int64_t*)(hb + off[1]),
-                            (const float*)(hb + off[2]),
-                            ppo ? nullptr : (const float*)(hb + off[3]), (const float*)(hb + off[4])};
-    return stage_now(h, &hbat, slot);
-  }
-  const int ns = h->n_h2d;
-  for (int i = 0; i < ns; ++i)  // the steps that read the slot have run
-    CK(hipStreamWaitEvent(h->h2d_s[i], s.done, 0));
-  void* dst[5] = {(void*)s.dev.obs, (void*)s.dev.actions, (void*)s.dev.rewards,
-                  (void*)s.dev.discounts, (void*)s.dev.behaviour_logits};
-  void* hb_dev = nullptr;
-  if (hipHostGetDevicePointer(&hb_dev, hb, 0) != hipSuccess || (((uintptr_t)hb_dev) & 15) != 0) {
-    (void)hipGetLastError();
-    hb_dev = nullptr;
-  }
-  if (hb_dev && (h->h2d_small_pull || h->h2d_pull_wg > 0)) {
-    PullArgs pa{};
-    for (int f = 1; f < 5; ++f) {
-      if (f == 3 && ppo) continue;
-      pa.src[pa.nf] = (const char*)hb_dev + off[f];
-      pa.dst[pa.nf] = (char*)dst[f];
-      pa.bytes[pa.nf] = (long long)(N * rb[f] / T);
-      ++pa.nf;
-    }
-    h2d_pull_kernel<<<8, 256, 0, h->h2d>>>(pa);
-    CK_LAUNCH("h2d_pull");
-  } else {
-    for (int f = 1; f < 5; ++f)
-      if (!(f == 3 && ppo))
-        CK(hipMemcpyAsync(dst[f], hb + off[f], N * rb[f] / T, hipMemcpyDefault, h->h2d));
-  }
-  // obs rows: runs of adjacent source rows become one copy, dealt round-robin over the streams
-  const char* const* ob = reinterpret_cast<const char* const*>(rows->obs);
-  int k = 0;
-  for (int b = 0; b < n;) {
-    int e = b + 1;
-    while (e < n && ob[e] == ob[e - 1] + rb[0]) ++e;
-    char* d = (char*)dst[0] + (size_t)b * rb[0];
-    const size_t len = (size_t)(e - b) * rb[0];
-    CK(hipMemcpyAsync(d, ob[b], len, hipMemcpyDefault, h->h2d_s[k++ % ns]));
-    b = e;
-  }
-  for (int i = 1; i < ns; ++i) {
-    CK(hipEventRecord(h->h2d_join[i], h->h2d_s[i]));
-    CK(hipStreamWaitEvent(h->h2d, h->h2d_join[i], 0));
-  }
-  CK(hipEventRecord(s.ready, h->h2d));
-  return 0;
-}
-}  // namespace
-
 int impala_stage_wait(impala_learner* h, int slot) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
-  if (slot < 0 || slot >= h->n_slots) return fail(IMPALA_E_INVALID, "slot out of range");
-  if (int r = wait_staged(h, slot)) return r;
-  CK(hipEventSynchronize(h->ring[slot].ready));
+  if (slot < 0 || slot >= h->stage.n_slots) return fail(IMPALA_E_INVALID, "slot out of range");
+  if (int r = wait_staged(h->stage, slot)) return r;
+  CK(hipEventSynchronize(h->stage.slots[slot].ready));
   return 0;
 }
 
 int impala_slot_batch(impala_learner* h, int slot, void* stream, impala_batch* out) {
   if (!h || !out) return fail(IMPALA_E_INVALID, "null argument");
-  if (slot < 0 || slot >= h->n_slots) return fail(IMPALA_E_INVALID, "slot out of range");
-  if (int r = wait_staged(h, slot)) return r;  // its copies are enqueued (ready recorded)
+  if (slot < 0 || slot >= h->stage.n_slots) return fail(IMPALA_E_INVALID, "slot out of range");
+  if (int r = wait_staged(h->stage, slot)) return r;  // its copies are enqueued (ready recorded)
   CK(hipSetDevice(h->device));
-  CK(hipStreamWaitEvent((hipStream_t)stream, h->ring[slot].ready, 0));
-  *out = h->ring[slot].dev;
+  CK(hipStreamWaitEvent((hipStream_t)stream, h->stage.slots[slot].ready, 0));
+  *out = h->stage.slots[slot].dev;
   return 0;
 }
 
 int impala_slot_release(impala_learner* h, int slot, void* stream) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
-  if (slot < 0 || slot >= h->n_slots) return fail(IMPALA_E_INVALID, "slot out of range");
+  if (slot < 0 || slot >= h->stage.n_slots) return fail(IMPALA_E_INVALID, "slot out of range");
   CK(hipSetDevice(h->device));
-  CK(hipEventRecord(h->ring[slot].done, (hipStream_t)stream));
+  CK(hipEventRecord(h->stage.slots[slot].done, (hipStream_t)stream));
   return 0;
 }
 

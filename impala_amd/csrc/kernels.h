@@ -1028,7 +1028,7 @@ struct GatherArgs {
   int hidx[GATHER_HIDX];
 };
 
-// Host -> HBM pull copy for the staging ring (impala_stage, IMPALA_H2D_KERNEL=1): a few
+// Host -> HBM pull copy for the staging ring (impala_stage's four small fields): a few
 // workgroups read page-locked host memory over PCIe with 4 x 16-byte loads in flight per lane
 // (PCIe latency x bandwidth needs ~128 KB outstanding), on the copy stream beside the step.
 struct PullArgs {

@@ -256,8 +256,8 @@ int impala_train_step_rows(impala_learner* h, const impala_batch* ring, const in
 /* Host staging ring (SURVEY.md §8(b) impala_stage; replaces the 5·B pageable `.to(device)`
  * copies of learning.py:121-123).  The handle owns `nslots` device batch slots of B*T frames
  * and a non-blocking H2D stream:
- *   impala_stage_init     allocate the ring (1..8 slots; re-init frees the old ring) and, for the
- *                         SDMA copy path, prime it: the staging loop runs 24 rounds on a scratch
+ *   impala_stage_init     allocate the ring (1..8 slots; re-init frees the old ring) and prime
+ *                         the copy path: the staging loop runs 24 rounds on a scratch
  *                         page-locked batch, so the runtime's one-time SDMA-queue creations
  *                         (6-9 ms host stalls inside hipMemcpyAsync) fall here and not into the
  *                         first steps; ~50 ms (IMPALA_STAGE_PRIME=<rounds>, 0 = off)
@@ -271,8 +271,8 @@ int impala_train_step_rows(impala_learner* h, const impala_batch* ring, const in
  *   impala_slot_release   record on `stream` that the steps reading the slot are enqueued
  * With two slots, staging batch k+1 overlaps the step on batch k.  The copies are SDMA
  * (hipMemcpyAsync) of obs over 2 streams, plus one small pull-kernel launch for the other
- * four fields when they are page-locked and device-mapped (IMPALA_H2D_STREAMS,
- * IMPALA_H2D_SMALL_PULL, IMPALA_H2D_KERNEL select other paths).  Call
+ * four fields when they are page-locked and device-mapped, else four more SDMA copies (also
+ * on data-parallel handles; IMPALA_H2D_SMALL_PULL=0|1 overrides).  Call
  * impala_stage_wait on a slot before restaging it, as a producer refilling its host buffers
  * must: a host that stages without ever waiting runs ahead and the runtime stalls the copies. */
 int impala_stage_init(impala_learner* h, int nslots);
@@ -282,10 +282,10 @@ int impala_stage(impala_learner* h, const impala_batch* host, int slot);
  * rlmeta CircularBuffer rows).  rows->obs[b] .. rows->behaviour_logits[b] point at trajectory
  * b's T-row fields in host memory (obs T*3*64*64 bytes, actions T int64, rewards / discounts T
  * floats, behaviour_logits T*A floats; discounts may be NULL on PPO handles); n must equal the
- * batch size.  Each obs row is copied by SDMA straight from its own memory into the slot (rows
- * in page-locked memory -- e.g. a pinned replay arena -- make the copies asynchronous;
- * adjacent rows are merged into one copy); the small fields are collated by the host into a
- * page-locked block of the slot (the call waits for the slot's previous copies first). */
+ * batch size.  The library's thread pool (IMPALA_STAGE_THREADS, default 8; placed by
+ * IMPALA_STAGE_PIN) collates the rows into a page-locked block of the slot, in impala_stage's
+ * layout -- the call waits for the slot's previous copies first -- and impala_stage's copies
+ * out of that block follow. */
 typedef struct {
   const void* const* obs;
   const void* const* actions;

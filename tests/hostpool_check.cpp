@@ -1,10 +1,13 @@
 // CPU check of impala_amd/csrc/hostpool.h (tests/test_hostpool.py): the thread pool runs every
-// task exactly once per call, copy_stream copies exactly, and the staging thread runs jobs in
-// order, waits per slot and reports a failed job's status once.
+// task exactly once per call, copy_stream copies exactly, the staging thread runs jobs in
+// order, waits per slot and reports a failed job's status once, and the staged batch's layout
+// and the row collate (StageLayout, collate_rows) equal a plain per-field concatenation.
 #include "../impala_amd/csrc/hostpool.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -59,6 +62,51 @@ int main() {
     CHECK(st.wait(-1, m) == 0 && m.empty());      // reported once
     CHECK(order.size() == 40);
     for (int j = 0; j < 40; ++j) CHECK(order[j] == j);
+  }
+  // layout + collate: against a plain per-field concatenation, byte for byte.  IMPALA shape
+  // (obs row 73 728 B: one whole 64 KB piece and a ragged one) and PPO shape (obs row 12 288 B:
+  // one short piece; discounts null, its region of the block untouched); 3-worker pool and serial
+  for (int ppo = 0; ppo < 2; ++ppo) {
+    const size_t B = 3, T = ppo ? 1 : 6, A = 2;
+    const StageLayout L(B, T, A);
+    // the layout rule, spelled out: field f holds B rows of T frames of frame[f] bytes and
+    // starts at the end of field f - 1 rounded up to 256
+    const size_t frame[5] = {3 * 64 * 64, 8, 4, 4, A * 4};
+    size_t end = 0;
+    for (int f = 0; f < 5; ++f) {
+      CHECK(L.row[f] == T * frame[f] && L.bytes[f] == B * T * frame[f]);
+      CHECK(L.off[f] == (end + 255) / 256 * 256 && L.off[f] % 256 == 0);
+      end = L.off[f] + L.bytes[f];
+    }
+    CHECK(L.off[5] == (end + 255) / 256 * 256);
+    CHECK(L.row[0] == (ppo ? 12288u : 73728u));
+    // every row its own allocation, handed over in non-ascending address order
+    std::vector<std::vector<char>> store[5];
+    const void* ptr[5][3];
+    for (int f = 0; f < 5; ++f) {
+      for (size_t b = 0; b < B; ++b) {
+        store[f].emplace_back(L.row[f]);
+        for (size_t i = 0; i < L.row[f]; ++i)
+          store[f][b][i] = (char)(i * 31 + (i >> 8) * 7 + (i >> 16) * 13 + b * 101 + f * 17 + 3);
+      }
+      std::vector<const char*> p;
+      for (auto& v : store[f]) p.push_back(v.data());
+      std::sort(p.begin(), p.end());
+      ptr[f][0] = p[2], ptr[f][1] = p[0], ptr[f][2] = p[1];
+    }
+    const void* const* rows[5] = {ptr[0], ptr[1], ptr[2], ppo ? nullptr : ptr[3], ptr[4]};
+    std::vector<char> want(L.off[5], (char)0x5a);
+    for (int f = 0; f < 5; ++f)
+      for (size_t b = 0; b < B && rows[f]; ++b)
+        std::memcpy(want.data() + L.off[f] + b * L.row[f], rows[f][b], L.row[f]);
+    HostPool pool(3);
+    for (HostPool* p : {&pool, (HostPool*)nullptr}) {
+      // a 16-byte aligned block, as the page-locked one is (copy_stream's streaming stores)
+      std::vector<char> got(L.off[5] + 16, (char)0x5a);
+      char* g = got.data() + (16 - ((uintptr_t)got.data() & 15)) % 16;
+      collate_rows(L, rows, (int)B, g, p);
+      CHECK(std::memcmp(g, want.data(), L.off[5]) == 0);
+    }
   }
   std::printf("hostpool ok\n");
   return 0;

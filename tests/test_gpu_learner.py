@@ -10,11 +10,9 @@ pytestmark = pytest.mark.gpu
 
 
 # impala_stage copy paths: the default (obs over 2 SDMA streams, the small fields in one pull
-# launch), all SDMA copies, 3 obs streams, and the pull kernel for everything
+# launch) and all SDMA copies (the path of data-parallel handles and of unmapped host memory)
 H2D_MODES = {"default": {},
-             "sdma_only": {"IMPALA_H2D_SMALL_PULL": "0"},
-             "sdma_3streams": {"IMPALA_H2D_STREAMS": "3"},
-             "pull8": {"IMPALA_H2D_KERNEL": "8"}}
+             "sdma_only": {"IMPALA_H2D_SMALL_PULL": "0"}}
 
 
 def _dev():
@@ -146,9 +144,9 @@ def test_device_replay_gather_and_learn():
 
 @pytest.mark.parametrize("h2d", sorted(H2D_MODES))
 def test_host_staging_ring_matches_device_batches(h2d, monkeypatch):
-    """impala_stage ring (2 slots, copies of step k+1 enqueued before step k; hipMemcpyAsync or
-    the PCIe pull kernel) gives bitwise the same weights and metrics as the same batches handed
-    over already in HBM."""
+    """impala_stage ring (2 slots, copies of step k+1 enqueued before step k; the small fields by
+    the PCIe pull kernel or by hipMemcpyAsync) gives bitwise the same weights and metrics as the
+    same batches handed over already in HBM."""
     dev = _dev()
     for k, v in H2D_MODES[h2d].items():
         monkeypatch.setenv(k, v)
@@ -185,8 +183,8 @@ def test_host_staging_ring_matches_device_batches(h2d, monkeypatch):
 
 
 def test_two_handles_share_the_copy_streams():
-    """Two handles on one device share the staging copy streams (impala.hip acquire_h2d: one set
-    per device and stream count, reference-counted).  Interleaved staging of different batches
+    """Two handles on one device share the staging copy streams (csrc/stage.h acquire_h2d: one
+    pair per device, reference-counted).  Interleaved staging of different batches
     on both still gives each handle bitwise its device-batch result, and a handle keeps staging
     after the other is closed (the streams outlive the first handle's release)."""
     dev = _dev()
@@ -320,9 +318,9 @@ def test_optimizer_state_resume_matches_uninterrupted():
 @pytest.mark.parametrize("h2d", sorted(H2D_MODES))
 def test_learner_host_batches_distinct_per_step(h2d, monkeypatch):
     """ImpalaLearner.train_step on host (list-of-trajectories) batches reuses two page-locked
-    staging buffers in place; with a DIFFERENT batch every step (hipMemcpyAsync or the PCIe
-    pull kernel) the weights and metrics are bitwise those of the same batches handed over
-    already in HBM -- a stale or torn read of a reused host buffer would show here."""
+    staging buffers in place; with a DIFFERENT batch every step (the small fields by the PCIe
+    pull kernel or by hipMemcpyAsync) the weights and metrics are bitwise those of the same
+    batches handed over already in HBM -- a stale or torn read of a reused host buffer would show here."""
     dev = _dev()
     for k, v in H2D_MODES[h2d].items():
         monkeypatch.setenv(k, v)
@@ -558,16 +556,15 @@ def test_whole_model_checkpoint_after_learner_step(tmp_path):
     assert torch.equal(lg0, lg1) and torch.equal(v0, v1)
 
 
-@pytest.mark.parametrize("mode", ["collate", "rows"])
-def test_replay_rows_staged_match_device_batches(mode, monkeypatch):
+@pytest.mark.parametrize("mode", ["collate"])  # (the one mode left; the id stays)
+def test_replay_rows_staged_match_device_batches(mode):
     """ImpalaLearner over the host ReplayBuffer: each step's B trajectories are staged by
     impala_stage_rows from their own host rows -- collated by the library's thread pool into the
-    slot's page-locked block (default), or one SDMA copy per row (IMPALA_STAGE_ROWS=rows).  An
-    actor-side append replaces the oldest trajectory before every step while the learner
-    prefetches ahead.  Weights and metrics must be bitwise those of the same trajectories (as
-    sampled) handed over already collated in HBM."""
+    slot's page-locked block, which impala_stage's copies then move.  An actor-side append
+    replaces the oldest trajectory before every step while the learner prefetches ahead.
+    Weights and metrics must be bitwise those of the same trajectories (as sampled) handed over
+    already collated in HBM."""
     dev = _dev()
-    monkeypatch.setenv("IMPALA_STAGE_ROWS", mode)
     from impala_amd.engine import Engine
     from impala_amd.learner import ImpalaLearner
     from impala_amd.model import AtariPPOModel

@@ -18,11 +18,9 @@ KEYS = ("loss", "entropy", "td", "pg", "kl", "ratio", "target")
 
 
 # impala_stage copy paths: the default (obs over 2 SDMA streams, the small fields in one pull
-# launch), all SDMA copies, 3 obs streams, and the pull kernel for everything
+# launch) and all SDMA copies (the path of data-parallel handles and of unmapped host memory)
 H2D_MODES = {"default": {},
-             "sdma_only": {"IMPALA_H2D_SMALL_PULL": "0"},
-             "sdma_3streams": {"IMPALA_H2D_STREAMS": "3"},
-             "pull8": {"IMPALA_H2D_KERNEL": "8"}}
+             "sdma_only": {"IMPALA_H2D_SMALL_PULL": "0"}}
 
 
 def _load(name):
@@ -172,7 +170,7 @@ def test_ppo_grad_parts_match_whole():
 @pytest.mark.parametrize("h2d", sorted(H2D_MODES))
 def test_ppo_host_staging_ring_matches_device_batch(h2d, monkeypatch):
     """impala_stage on a PPO handle (no discounts field): bitwise the same step as the batch
-    handed over in HBM, with hipMemcpyAsync or the pull kernel."""
+    handed over in HBM, the small fields by the pull kernel or by hipMemcpyAsync."""
     dev = _dev()
     for k, v in H2D_MODES[h2d].items():
         monkeypatch.setenv(k, v)

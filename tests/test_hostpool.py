@@ -1,6 +1,6 @@
 """The staging ring's host side on the CPU (impala_amd/csrc/hostpool.h): the collate thread
-pool, the streaming copy and the staging thread (impala_stage_rows / _async), compiled with
-ROCm's clang++ and run; no GPU involved."""
+pool, the streaming copy, the staging thread, the staged batch's byte layout and the row collate
+(impala_stage_rows / _async), compiled with ROCm's clang++ and run; no GPU involved."""
 import os
 import shutil
 import subprocess
