@@ -23,9 +23,6 @@ constexpr int GRID = 16;                 // 16x16 super-pixels of 4x4
 constexpr int CH = 48;                   // 3 * 4 * 4
 constexpr int NPIX = P1;                 // 225 output pixels per frame
 constexpr int NPAD = 256;                // pixels padded to a multiple of 32 (wgrad k-steps)
-template <typename T> struct L;
-template <> struct L<__bf16> { static constexpr int LDI = 56; };  // 112 B rows: conflict-free
-template <> struct L<float> { static constexpr int LDI = 52; };
 }  // namespace c1
 
 // Fused forward image layout: row-major s2d rows of LDI_F elements, GRID*GRID + 2 rows (the
@@ -55,12 +52,6 @@ DEV int c1_canon_k(int kp) {  // k' -> ci*64 + kh*8 + kw
   return ci * 64 + ((tap >> 1) * 4 + b) * 8 + (tap & 1) * 4 + d;
 }
 
-// LDS row (grid cell) of output pixel p under tap (a, c)
-DEV int c1_row(int p, int tap) {
-  const int oy = p / H1, ox = p - oy * H1;
-  return (oy + (tap >> 1)) * c1::GRID + ox + (tap & 1);
-}
-
 // frame bytes -> LDS s2d image.  Thread t owns 16-byte vectors t, t+256, t+512 of the frame.
 template <typename T>
 DEV void c1_load_frame(const uint8_t* __restrict__ frame, int tid, uint4 v[3]) {
@@ -86,7 +77,7 @@ struct ObsRows {
   }
 };
 
-template <typename T, int LDI = c1::L<T>::LDI>
+template <typename T, int LDI>
 DEV void c1_stash_frame(T* img, int tid, const uint4 v[3]) {
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -146,15 +137,10 @@ DEV void c1_stash_frame_rot(T* img, int tid, const uint4 v[3]) {
   }
 }
 
-// ---------------------------------------------------------------------------------------
-// forward: act1[n][p][oc] = relu(sum W'[oc][k'] s2d * 1/255 + b1), weights in registers;
-// optionally the ReLU bit mask mask[n][p] (bit oc = act1 > 0) for the fused backward.
-// ---------------------------------------------------------------------------------------
-// W1 as bf16 conv1 A fragments (bf16 fragment layout: 8 consecutive k per lane), rows
-// oc = 16 i + (lane & 15): bf16 W1 as is; fp32 W1 split exactly into three bf16 terms
-// x = hi + mid + lo (round-to-nearest 8-bit pieces of a 24-bit significand: every product with
-// an image byte, exact in bf16, is exact in the fp32 accumulator, so the three MFMA passes
-// compute the fp32 products).  Shared by both conv1 forward kernels (bitwise-equal act1).
+// fp32 W1 for the bf16 conv1 MFMAs: split exactly into three bf16 terms x = hi + mid + lo
+// (round-to-nearest 8-bit pieces of a 24-bit significand: every product with an image byte,
+// exact in bf16, is exact in the fp32 accumulator, so the three MFMA passes compute the fp32
+// products).
 DEV void c1_split3(float x, __bf16& h, __bf16& m, __bf16& l) { split3(x, h, m, l); }
 // fp32 W1 staged once per workgroup as its three bf16 planes (plane p: [32][C1W_LD] bf16, rows
 // padded by 16: conflict-free 16-byte fragment reads), instead of every wave loading all of W1
@@ -180,101 +166,13 @@ DEV void c1_stage_w1_f32(const float* __restrict__ w1, __bf16* __restrict__ plan
   }
 }
 
-template <typename T>
-DEV void c1_load_w1(const T* __restrict__ w1, int lane,
-                    Frag<__bf16>::vec (&wa)[2][K1 / Frag<__bf16>::KSTEP][sizeof(T) == 4 ? 3 : 1]) {
-  using FB = Frag<__bf16>;
-  constexpr int NKB = K1 / FB::KSTEP;
-  const int klb = FB::KPL * (lane >> 4);
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) {
-      const T* src = w1 + (16 * i + (lane & 15)) * K1 + kb * FB::KSTEP + klb;
-      if constexpr (sizeof(T) == 2) {
-        wa[i][kb][0] = FB::load(src);
-      } else {
-        const f32x4 u0 = *reinterpret_cast<const f32x4*>(src), u1 = *reinterpret_cast<const f32x4*>(src + 4);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          __bf16 h, m, l;
-          c1_split3(c < 4 ? u0[c] : u1[c - 4], h, m, l);
-          wa[i][kb][0][c] = h;
-          wa[i][kb][1][c] = m;
-          wa[i][kb][2][c] = l;
-        }
-      }
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void conv1_fwd_s2d(const uint8_t* __restrict__ x,
-                                                     const T* __restrict__ w,  // [32][192] k'
-                                                     const float* __restrict__ bias,
-                                                     T* __restrict__ out,
-                                                     uint32_t* __restrict__ mask, int N) {
-  // the image in LDS as bf16 (exact bytes) in both modes; conv1 on bf16 MFMAs (fp32: three
-  // exact passes, c1_load_w1)
-  using FB = Frag<__bf16>;
-  typedef FB::vec VB;
-  constexpr int LDI = c1::L<__bf16>::LDI;
-  constexpr int NKB = K1 / FB::KSTEP, NT = sizeof(T) == 4 ? 3 : 1;
-  __shared__ __attribute__((aligned(16))) __bf16 img[c1::GRID * c1::GRID * LDI];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int kl = FB::KPL * (lane >> 4);
-  VB wa[2][NKB][NT];  // A fragments: rows oc = 16*i + (lane & 15), all of K
-  c1_load_w1<T>(w, lane, wa);
-  float bb[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) bb[i][q] = bias[16 * i + 4 * (lane >> 4) + q];
-  int f = blockIdx.x;
-  if (f >= N) return;
-  uint4 nv[3];
-  c1_load_frame<T>(x + (size_t)f * IMG, tid, nv);
-  for (; f < N; f += gridDim.x) {
-    __syncthreads();  // previous frame's readers are done
-    c1_stash_frame<__bf16>(img, tid, nv);
-    __syncthreads();
-    if (f + (int)gridDim.x < N) c1_load_frame<T>(x + (size_t)(f + gridDim.x) * IMG, tid, nv);
-    for (int tile = wave; tile < 15; tile += 4) {  // 15 x 16 pixel tiles cover the 225 pixels
-      const int p = min(tile * 16 + (lane & 15), c1::NPIX - 1);
-      const int base = c1_row(p, 0) * LDI;
-      f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) {
-        const int k = kb * FB::KSTEP + kl, tap = k / c1::CH, ch = k - tap * c1::CH;
-        const int off = ((tap >> 1) * c1::GRID + (tap & 1)) * LDI + ch;
-        const VB b = *reinterpret_cast<const VB*>(img + base + off);
-#pragma unroll
-        for (int tm = 0; tm < NT; ++tm) {
-          acc[0] = FB::mma(wa[0][kb][tm], b, acc[0]);
-          acc[1] = FB::mma(wa[1][kb][tm], b, acc[1]);
-        }
-      }
-      const int pc = tile * 16 + (lane & 15);
-      uint32_t bits = 0;  // ReLU mask of this pixel's 32 channels (bit oc), for the backward
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          v[q] = fmaxf(acc[i][q] * (1.f / 255.f) + bb[i][q], 0.f);
-          bits |= (v[q] > 0.f ? 1u : 0u) << (16 * i + 4 * (lane >> 4) + q);
-        }
-        if (pc < c1::NPIX) store4(out + ((size_t)f * c1::NPIX + pc) * OC1 + 16 * i + 4 * (lane >> 4), v);
-      }
-      bits = xor32_or(xor16_or(bits));
-      if (mask && pc < c1::NPIX && lane < 16) mask[(size_t)f * c1::NPIX + pc] = bits;
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------
 // conv1 + conv2 forward, fused per frame: the frame's act1 (15x15x32) is produced into LDS and
 // consumed there by conv2 (it is also written to HBM, with its ReLU bit mask, for the backward).
-//   conv1: as conv1_fwd_s2d (weights in registers, 15 pixel tiles over the 4 waves)
+//   conv1: act1[p][oc] = relu(sum W'[oc][k'] s2d * 1/255 + b1), with the ReLU bit mask
+//          mask[n][p] (bit oc = act1 > 0) for the backward; all of W1 as A fragments in
+//          registers, wave wq takes output rows oy = wq, wq + 4, wq + 8, wq + 12 (one 16-pixel
+//          tile each, lane & 15 = ox).
 //   conv2: act2[p][oc] = relu(sum_k W2[oc][k] act1[2oy+kh][2ox+kw][ci] + b2), k = tap*32 + ci;
 //          wave w owns oc tile w (its W2 rows stay in registers), 3 tiles of 16 output pixels,
 //          B fragments are 16-byte LDS reads of the act1 tile (one tap per 32-wide k-step).
@@ -454,8 +352,7 @@ DEV void conv12_fwd_body(const uint8_t* __restrict__ x, const T* __restrict__ w1
       wa2[ks] = *reinterpret_cast<const V*>(w2s + (16 * wave + (lane & 15)) * LW2 + ks * KS + kl);
     __syncthreads();  // the staging area becomes the frame tiles
   } else {
-    // fp32: W1 staged once as its three bf16 planes (c1_stage_w1_f32, the split of c1_load_w1),
-    // the fragments read from LDS
+    // fp32: W1 staged once as its three bf16 planes (c1_stage_w1_f32), the fragments read from LDS
     static_assert(3 * OC1 * C1W_LD * 2 <= (int)sizeof(T) * G * GSZ, "W1 plane staging");
     __bf16* w1p = reinterpret_cast<__bf16*>(smem);
     if (threadIdx.x < 256) c1_stage_w1_f32(reinterpret_cast<const float*>(w1), w1p, (int)threadIdx.x);
@@ -847,7 +744,7 @@ __global__ __launch_bounds__(c12f_threads<T>()) void conv12_fwd_s2d(
 // K = 4 taps x 64 oc, and wave w owns class w for the whole kernel, so its W2 fragments (the
 // A operand, ci x oc) stay in registers; the B operand is a 16-byte LDS read of the frame's
 // dY2 held in a zero-bordered 9x9 cell grid (no bounds tests).  The ReLU mask of act1 comes
-// from the bit mask conv1_fwd_s2d writes (one 32-bit word per pixel).  The conv1 weight
+// from the bit mask the fused forward writes (one 32-bit word per pixel).  The conv1 weight
 // gradient then reads dY1 and the frame's s2d image from LDS: wave w owns tap w (48 channels
 // = 3 column tiles) for both 16-row oc tiles.  Each workgroup takes a contiguous run of frames
 // and writes one fp32 partial slab [32][192] (k' order) + bias sums, reduced by reduce_grads.

@@ -102,16 +102,16 @@ Split plan_split(long M, int tiles, int target_wgs, int chunk = 64) {
 
 // kernel ids for the live launch timer (impala_timer_*)
 enum KernelId {
-  K_CONV1_FWD = 0, K_CONV2_FWD, K_CONV12_FWD, K_CONV3_FWD, K_FC_FWD, K_HEADS_FWD, K_HEAD_STEP, K_FC_DGRAD,
-  K_LN_BWD, K_CONV3_DGRAD, K_LNC3_BWD, K_FC_WGRAD, K_CONV3_WGRAD, K_CONV2_WGRAD, K_CONV12_BWD, K_REDUCE,
-  K_SUMSQ, K_ADAM, K_FC_BWD, K_WGRAD23, K_CONV123_FWD, K_LNC12_BWD,
+  K_CONV12_FWD = 0, K_CONV3_FWD, K_FC_FWD, K_HEADS_FWD, K_HEAD_STEP, K_LNC3_BWD, K_CONV3_WGRAD,
+  K_CONV2_WGRAD, K_CONV12_BWD, K_REDUCE, K_SUMSQ, K_ADAM, K_FC_BWD, K_WGRAD23, K_CONV123_FWD,
+  K_LNC12_BWD,
   K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
-    "conv1_fwd", "conv2_fwd", "conv1_fwd_conv2_fwd", "conv3_fwd", "fc_fwd", "heads_fwd", "head_step", "fc_dgrad",
-    "ln_bwd", "conv3_dgrad", "ln_bwd_conv3_dgrad", "fc_wgrad", "conv3_wgrad", "conv2_wgrad",
-    "conv2_dgrad_conv1_wgrad", "reduce_grads", "sumsq", "adam", "fc_wgrad_fc_dgrad",
-    "conv3_wgrad_conv2_wgrad", "conv1_conv2_conv3_fwd", "ln_conv3_conv2_dgrad_conv1_wgrad"};
+    "conv1_fwd_conv2_fwd", "conv3_fwd", "fc_fwd", "heads_fwd", "head_step", "ln_bwd_conv3_dgrad",
+    "conv3_wgrad", "conv2_wgrad", "conv2_dgrad_conv1_wgrad", "reduce_grads", "sumsq", "adam",
+    "fc_wgrad_fc_dgrad", "conv3_wgrad_conv2_wgrad", "conv1_conv2_conv3_fwd",
+    "ln_conv3_conv2_dgrad_conv1_wgrad"};
 
 struct impala_learner {
   impala_config cfg;
@@ -141,17 +141,14 @@ struct impala_learner {
   float *s_w1, *s_b1, *s_w2, *s_b2, *s_w3, *s_b3, *s_ln, *s_fc, *s_bfc, *s_h, *s_bh;
   float *loss_part, *sumsq_part, *adam_sc;
   int64_t* step;
-  bool fc_merged = true;      // FC weight + input gradients in one launch (fc_bwd_kernel)
   bool wg23_merged = true;    // conv3 + conv2 weight gradients in one launch (wgrad23_kernel)
   bool c3_tail = true;        // bf16: conv3 + LayerNorm as the tail of the fused conv1/conv2 forward
   bool lc12 = true;           // LayerNorm/conv3 dgrad + conv2 dgrad/conv1 wgrad in one launch
   Split sp1, sp2, sp3, spfc, sph;
   // n_red_wg: slab-reduction workgroups = clip-norm partials (one sum of squares each)
-  int n_ln_wg = 0, ln_fpw = 2, n_loss_wg = 0, S_seg = 32, n_red_wg = 0;
+  int n_ln_wg = 0, ln_fpw = 0, n_loss_wg = 0, S_seg = 32, n_red_wg = 0;
   RedArgs red{};
   int n_cu = 256;
-  bool lnc3_fused = true;      // LayerNorm backward + conv3 dgrad in one per-frame kernel
-  bool fwd_fused = true;       // conv1 + conv2 forward in one per-frame kernel
   int c1_fpw = 1, c1_wg = 1;  // conv1 wgrad: frames per workgroup, workgroups (= splits)
   int c12f_fpw = 0;           // conv1+conv2 forward frames per workgroup (0: N / CUs)
   float* vt_dbg = nullptr;    // impala_set_debug_vtrace: the step's V-trace outputs
@@ -248,40 +245,27 @@ int launch_forward(impala_learner* h, const uint8_t* obs, int n, hipStream_t st,
   const T* sw = reinterpret_cast<const T*>(h->shadow);
   const Shadow& sh = h->sh;
   const float* vv = h->vecs;
+  // conv1 + conv2 per frame (act1 consumed from LDS)
+  const int fpw = h->c12f_fpw > 0 ? h->c12f_fpw : std::max(1, cdiv(n, h->n_cu));
+  // at most c3t_fmax<T>() frames per workgroup (bf16 6, fp32 5): conv3 + ReLU + LayerNorm
+  // run as the kernel's tail (one launch for the whole conv trunk)
+  C3Tail<T> c3{};
   bool conv3_done = false;
-  if (h->fwd_fused) {  // conv1 + conv2 per frame (act1 consumed from LDS)
-    const int fpw = h->c12f_fpw > 0 ? h->c12f_fpw : std::max(1, cdiv(n, h->n_cu));
-    // at most c3t_fmax<T>() frames per workgroup (bf16 6, fp32 5): conv3 + ReLU + LayerNorm
-    // run as the kernel's tail (one launch for the whole conv trunk)
-    C3Tail<T> c3{};
-    if (h->c3_tail && fpw <= c3t_fmax<T>()) {
-      c3.w3 = sw + sh.w3; c3.b3 = vv + Vecs::b3; c3.gam = vv + Vecs::lng; c3.bet = vv + Vecs::lnb;
-      c3.act3 = (T*)h->act3; c3.y = (T*)h->y; c3.stats = h->lnstat;
-      conv3_done = true;
-    }
-    // the frames from the batch arrays, or (impala_train_step_rows) from a replay ring in place
-    auto fwd = [&](const auto& rm) {
-      using O = std::decay_t<decltype(rm)>;
-      return klaunch(h, conv3_done ? K_CONV123_FWD : K_CONV12_FWD, "conv12_fwd", conv12_fwd_s2d<T, O>,
-                     dim3(cdiv(n, fpw)), dim3(c12f_threads<T>()), st, obs, sw + sh.w1,
-                     vv + Vecs::b1, sw + sh.w2, vv + Vecs::b2, (T*)h->act1, h->mask1,
-                     (T*)h->act2, n, fpw, c3, with_heads ? nullptr : step_stamp(h), rm);
-    };
-    if (int r = h->rows_on && !with_heads ? fwd(h->obs_rows) : fwd(ObsDirect{})) return r;
-  } else {
-    if (!with_heads)  // the unfused forward (IMPALA_FWD_FUSED=0): the clock gets a stamp launch
-      if (unsigned long long* ss = step_stamp(h))
-        if (int r = klaunch(h, -1, "clock_stamp", clock_stamp_kernel, dim3(1), dim3(64), st, ss))
-          return r;
-    if (int r = klaunch(h, K_CONV1_FWD, "conv1_fwd", conv1_fwd_s2d<T>, dim3(min(n, h->n_cu * 4)),
-                        dim3(256), st, obs, sw + sh.w1, vv + Vecs::b1, (T*)h->act1, h->mask1, n))
-      return r;
-    Conv2Fwd<T> op{n * P2, sw + sh.w2, vv + Vecs::b2, (const T*)h->act1, (T*)h->act2};
-    if (int r = klaunch(h, K_CONV2_FWD, "conv2_fwd", gemm_tile<T, 64, 128, BK(64), 1, 4, Conv2Fwd<T>>,
-                        dim3(persist_grid(h, cdiv((long)n * P2, 128))), dim3(256), st, op, 1))
-      return r;
+  if (h->c3_tail && fpw <= c3t_fmax<T>()) {
+    c3.w3 = sw + sh.w3; c3.b3 = vv + Vecs::b3; c3.gam = vv + Vecs::lng; c3.bet = vv + Vecs::lnb;
+    c3.act3 = (T*)h->act3; c3.y = (T*)h->y; c3.stats = h->lnstat;
+    conv3_done = true;
   }
-  if (!conv3_done) {
+  // the frames from the batch arrays, or (impala_train_step_rows) from a replay ring in place
+  auto fwd = [&](const auto& rm) {
+    using O = std::decay_t<decltype(rm)>;
+    return klaunch(h, conv3_done ? K_CONV123_FWD : K_CONV12_FWD, "conv12_fwd", conv12_fwd_s2d<T, O>,
+                   dim3(cdiv(n, fpw)), dim3(c12f_threads<T>()), st, obs, sw + sh.w1,
+                   vv + Vecs::b1, sw + sh.w2, vv + Vecs::b2, (T*)h->act1, h->mask1,
+                   (T*)h->act2, n, fpw, c3, with_heads ? nullptr : step_stamp(h), rm);
+  };
+  if (int r = h->rows_on && !with_heads ? fwd(h->obs_rows) : fwd(ObsDirect{})) return r;
+  if (!conv3_done) {  // more frames per workgroup than the tail takes, or IMPALA_C3_TAIL=0
     Conv3LnFwd<T> op{};
     op.C = n * P3; op.w = sw + sh.w3; op.b = vv + Vecs::b3; op.x = (const T*)h->act2;
     op.out = (T*)h->act3; op.gam = vv + Vecs::lng; op.bet = vv + Vecs::lnb; op.y = (T*)h->y;
@@ -321,7 +305,7 @@ int reduce_segments(impala_learner* h, int s_lo, int s_hi, hipStream_t st, int f
 
 // The backward is three stages on one stream:
 //   head_fc  head_step_kernel (heads forward, loss, dz, heads weight gradient), then the FC
-//            weight and input gradients (fc_bwd_kernel, or gemm_wg<FcWgrad> + gemm_tile<FcDgrad>)
+//            weight and input gradients (fc_bwd_kernel)
 //   ln_c3    LayerNorm backward + conv3 dgrad, and the conv3 weight gradient
 //   c2_c1    conv2 weight gradient, and conv2 dgrad + conv1 wgrad
 // A part runs a range of stages, then one reduction of the slab segments those stages (and no
@@ -372,7 +356,7 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, co
   // and the two per-frame chains in one launch (same frame runs)
   const bool both = bp->first <= BS_LN_C3 && bp->last == BS_C2_C1;
   const bool wg23 = h->wg23_merged && both;
-  const bool lc12 = h->lc12 && h->lnc3_fused && h->ln_fpw == h->c1_fpw && both;
+  const bool lc12 = h->lc12 && h->ln_fpw == h->c1_fpw && both;
 
   // ---- head_fc: heads fwd, log-softmax / V-trace / loss, dz, heads weight gradient; then the
   // FC weight and input gradients ----
@@ -406,21 +390,12 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, co
     FcWgrad<T, HID> ow{};
     ow.M = N; ow.x = (const T*)h->dz; ow.y = (const T*)h->y;
     FcDgrad<T, HID> od{N, sw + sh.wfc, (const T*)h->dz, h->dy};
-    if (h->fc_merged) {  // both in one launch
-      using C = FcBwdCfg<T, WG2, HID>;
-      const int gx = FLAT / C::WBC, gy = HID / 64, gz = h->spfc.S;
-      const int n_rt = FLAT / C::DR, n_dt = n_rt * cdiv(N, C::DC);
-      return klaunch(h, K_FC_BWD, "fc_wgrad_fc_dgrad", fc_bwd_kernel<T, WG2, HID>,
-                     dim3(gx * gy * gz + n_dt), dim3(256 * WG2), st, ow, h->s_fc, h->s_bfc,
-                     h->spfc.mps, gx, gy, gz, od, n_rt);
-    }
-    if (int r = klaunch(h, K_FC_WGRAD, "fc_wgrad", gemm_wg<T, 64, 256, 1, 4, 32, WG2, FcWgrad<T, HID>>,
-                        dim3(FLAT / 256, HID / 64, h->spfc.S), dim3(256 * WG2), st, ow, h->s_fc,
-                        h->s_bfc, h->spfc.mps))
-      return r;
-    return klaunch(h, K_FC_DGRAD, "fc_dgrad", gemm_tile<T, 64, 64, BK(128), 2, 2, FcDgrad<T, HID>>,
-                   dim3(persist_grid(h, (long)cdiv(N, 64) * (FLAT / 64))), dim3(256), st, od,
-                   FLAT / 64);
+    using C = FcBwdCfg<T, WG2, HID>;
+    const int gx = FLAT / C::WBC, gy = HID / 64, gz = h->spfc.S;
+    const int n_rt = FLAT / C::DR, n_dt = n_rt * cdiv(N, C::DC);
+    return klaunch(h, K_FC_BWD, "fc_wgrad_fc_dgrad", fc_bwd_kernel<T, WG2, HID>,
+                   dim3(gx * gy * gz + n_dt), dim3(256 * WG2), st, ow, h->s_fc, h->s_bfc,
+                   h->spfc.mps, gx, gy, gz, od, n_rt);
   };
 
   // ---- ln_c3: LayerNorm backward + conv3 dgrad (with lc12, c2_c1's per-frame kernel too), and
@@ -438,30 +413,17 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, co
                        h->ln_fpw, rm);
       };
       if (int r = h->rows_on ? bwd(h->obs_rows) : bwd(ObsDirect{})) return r;
-    } else if (h->lnc3_fused) {  // LayerNorm backward + conv3 dgrad per frame
+    } else {  // LayerNorm backward + conv3 dgrad per frame
       if (int r = klaunch(h, K_LNC3_BWD, "ln_bwd_conv3_dgrad", lnc3_bwd<T>, dim3(h->n_ln_wg),
                           dim3(lnc3_threads<T>()), st, (const float*)h->dy, (const T*)h->act3,
                           (const float*)h->lnstat, (const float*)(h->vecs + Vecs::lng), sw + sh.w3,
                           sw + sh.w3t, (const T*)h->act2, (T*)h->dact3, (T*)h->dact2, h->s_ln, N,
                           h->ln_fpw))
         return r;
-    } else {
-      if (int r = klaunch(h, K_LN_BWD, "ln_bwd", ln_bwd_kernel<T>, dim3(h->n_ln_wg), dim3(256), st,
-                          (const float*)h->dy, (const T*)h->act3, (const float*)h->lnstat,
-                          (const float*)(h->vecs + Vecs::lng), (T*)h->dact3, h->s_ln, N, h->ln_fpw))
-        return r;
     }
-    // IMPALA_LNC3_FUSED=0: dact2 comes from a separate conv3 dgrad
-    auto conv3_dgrad = [&]() -> int {
-      if (h->lnc3_fused) return 0;
-      Conv3Dgrad<T> op{N * P2, sw + sh.w3, (const T*)h->dact3, (const T*)h->act2, (T*)h->dact2};
-      return klaunch(h, K_CONV3_DGRAD, "conv3_dgrad", gemm_tile<T, 64, 128, BK(64), 1, 4, Conv3Dgrad<T>>,
-                     dim3(persist_grid(h, cdiv((long)N * P2, 128))), dim3(256), st, op, 1);
-    };
     Conv3Wgrad<T> o3{};
     o3.M = N * P3; o3.x = (const T*)h->dact3; o3.in = (const T*)h->act2;
-    if (wg23) {  // conv2's weight gradient reads dact2: after the conv3 dgrad
-      if (int r = conv3_dgrad()) return r;
+    if (wg23) {  // conv2's weight gradient reads dact2, which the per-frame kernel has written
       Conv2Wgrad<T> o2{};
       o2.M = N * P2; o2.x = (const T*)h->dact2; o2.in = (const T*)h->act1;
       const int g3x = K3 / 64, g3z = h->sp3.S, g2x = K2 / Wg2Tile<T>::BC, g2z = h->sp2.S;
@@ -471,11 +433,9 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, co
     }
     // 64 x 64 tiles (9 column tiles x ~28 splits): 4.1 MB of partial slabs instead of 9.4 MB
     // for 64 x 192 tiles x 64 splits, and 9.1 vs 9.8 us (profiles/r02b)
-    if (int r = klaunch(h, K_CONV3_WGRAD, "conv3_wgrad", gemm_wg<T, 64, 64, 2, 2, 32, WG4, Conv3Wgrad<T>>,
-                        dim3(K3 / 64, 1, h->sp3.S), dim3(256 * WG4), st, o3, h->s_w3, h->s_b3,
-                        h->sp3.mps))
-      return r;
-    return conv3_dgrad();
+    return klaunch(h, K_CONV3_WGRAD, "conv3_wgrad", gemm_wg<T, 64, 64, 2, 2, 32, WG4, Conv3Wgrad<T>>,
+                   dim3(K3 / 64, 1, h->sp3.S), dim3(256 * WG4), st, o3, h->s_w3, h->s_b3,
+                   h->sp3.mps);
   };
 
   // ---- c2_c1: conv2 weight gradient (unless wg23 ran it), then conv2 input gradient
@@ -622,6 +582,29 @@ int impala_internal::create_learner(const impala_config* cfg, int device, int hi
   CK(hipSetDevice(device));
   impala_learner* h = new (std::nothrow) impala_learner();
   if (!h) return fail(IMPALA_E_INVALID, "out of host memory");
+  // ---- every environment read of this function; nothing below depends on the environment ----
+  // separate launches of stages the default step fuses (=0): the kernels the host falls back to
+  // at large frame runs and in the data-parallel parts, selectable so small tests can run them
+  if (const char* e = std::getenv("IMPALA_C3_TAIL")) h->c3_tail = e[0] != '0';
+  if (const char* e = std::getenv("IMPALA_LC12")) h->lc12 = e[0] != '0';
+  if (const char* e = std::getenv("IMPALA_WG23_MERGED")) h->wg23_merged = e[0] != '0';
+  // hipGraph replay of whole steps (opt-in): it cuts the host enqueue cost of a step ~3x, but
+  // on MI355X / ROCm 7 the replayed step ran slower on the device than direct launches
+  // (174 vs 165 us, DESIGN.md), so direct launches are the default
+  if (const char* g = std::getenv("IMPALA_GRAPH")) h->use_graph = g[0] == '1';
+  // workgroup targets of the FC and conv weight-gradient splits (0: the defaults below)
+  int fc_wg = 0, wg3 = 256, wg2 = 256;
+  if (const char* e = std::getenv("IMPALA_FC_WG")) fc_wg = std::max(16, std::atoi(e));
+  if (const char* e = std::getenv("IMPALA_WG3_TARGET")) wg3 = std::max(1, std::atoi(e));
+  if (const char* e = std::getenv("IMPALA_WG2_TARGET")) wg2 = std::max(1, std::atoi(e));
+  // frames per workgroup: conv2 dgrad + conv1 wgrad, conv1 + conv2 forward (0: N / CUs)
+  int c1_fpw = 0;
+  if (const char* e = std::getenv("IMPALA_C1_FPW")) c1_fpw = std::max(1, std::atoi(e));
+  if (const char* e = std::getenv("IMPALA_C12F_FPW")) h->c12f_fpw = std::max(0, std::atoi(e));
+  // split loads per thread the slab reduction's split-group count aims for
+  int lpt = 16;
+  if (const char* e = std::getenv("IMPALA_RED_LPT")) lpt = std::max(1, std::atoi(e));
+
   h->cfg = *cfg;
   h->device = device;
   h->A = cfg->num_actions;
@@ -641,13 +624,9 @@ int impala_internal::create_learner(const impala_config* cfg, int device, int hi
   h->S_seg = next_pow2(cfg->rollout_length);
   h->n_loss_wg = cdiv(cfg->batch_size, 64 / h->S_seg);  // fused head: 64/S trajectories per WG
   if (dqn) h->n_loss_wg = cdiv(N, DQN_F);               // dueling head: DQN_F transitions per WG
-  if (const char* lf = std::getenv("IMPALA_LNC3_FUSED")) h->lnc3_fused = lf[0] != '0';
-  if (h->lnc3_fused) {  // frames per workgroup of the fused kernel (one slab each)
-    h->ln_fpw = std::max(1, cdiv(N, h->n_cu));
-    h->n_ln_wg = cdiv(N, h->ln_fpw);
-  } else {
-    h->n_ln_wg = cdiv(N, 4 * h->ln_fpw);
-  }
+  // frames per workgroup of the LayerNorm backward + conv3 dgrad kernels (one slab each)
+  h->ln_fpw = std::max(1, cdiv(N, h->n_cu));
+  h->n_ln_wg = cdiv(N, h->ln_fpw);
 
   // upper bound on the reduce workgroups (each segment: count/4 float4 columns, >= 16 per WG)
   h->n_red_wg = 11 + (OC1 * K1 + OC1 + OC2 * K2 + OC2 + OC3 * K3 + OC3 + 2 * FLAT + HID * FLAT +
@@ -656,19 +635,13 @@ int impala_internal::create_learner(const impala_config* cfg, int device, int hi
   // FC weight-gradient splits: 96 workgroups for bf16; fp32 128 (8 splits: fc_bwd 20.3 us and
   // the reduction 7.55 against 20.7 / 7.75 for 256 workgroups, 27.8 us for 64;
   // tools/var_specs/{fc32b,spfc32}.py)
-  int fc_wg = h->bf16 ? 96 : 128;
-  if (const char* e = std::getenv("IMPALA_FC_WG")) fc_wg = std::max(16, std::atoi(e));
+  if (fc_wg == 0) fc_wg = h->bf16 ? 96 : 128;
   h->spfc = plan_split(N, (FLAT / 256) * (HID / 64), fc_wg);
   // the conv weight gradients' m splits: ~256 workgroups each (IMPALA_WG3_TARGET /
   // IMPALA_WG2_TARGET override the count for A/B runs; more splits, more slab bytes to reduce)
-  int wg3 = 256, wg2 = 256;
-  if (const char* e = std::getenv("IMPALA_WG3_TARGET")) wg3 = std::max(1, std::atoi(e));
-  if (const char* e = std::getenv("IMPALA_WG2_TARGET")) wg2 = std::max(1, std::atoi(e));
   h->sp3 = plan_split((long)N * P3, K3 / 64, wg3);
   h->sp2 = plan_split((long)N * P2, K2 / 128, wg2);
-  h->c1_fpw = std::max(1, cdiv(N, h->n_cu));
-  if (const char* e = std::getenv("IMPALA_C1_FPW")) h->c1_fpw = std::max(1, std::atoi(e));
-  if (const char* e = std::getenv("IMPALA_C12F_FPW")) h->c12f_fpw = std::max(0, std::atoi(e));
+  h->c1_fpw = c1_fpw > 0 ? c1_fpw : std::max(1, cdiv(N, h->n_cu));
   h->c1_wg = cdiv(N, h->c1_fpw);
   h->sp1.S = h->c1_wg;  // slab splits of conv1 (one per workgroup)
 
@@ -737,15 +710,6 @@ int impala_internal::create_learner(const impala_config* cfg, int device, int hi
   h->loss_part = (float*)(w + o_lpart); h->sumsq_part = (float*)(w + o_spart);
   h->adam_sc = (float*)(w + o_adsc);
   h->step = (int64_t*)(w + o_step);
-  if (const char* ff = std::getenv("IMPALA_FWD_FUSED")) h->fwd_fused = ff[0] != '0';
-  if (const char* e = std::getenv("IMPALA_FC_MERGED")) h->fc_merged = e[0] != '0';
-  if (const char* e = std::getenv("IMPALA_WG23_MERGED")) h->wg23_merged = e[0] != '0';
-  if (const char* e = std::getenv("IMPALA_C3_TAIL")) h->c3_tail = e[0] != '0';
-  if (const char* e = std::getenv("IMPALA_LC12")) h->lc12 = e[0] != '0';
-  // hipGraph replay of whole steps (opt-in): it cuts the host enqueue cost of a step ~3x, but
-  // on MI355X / ROCm 7 the replayed step ran slower on the device than direct launches
-  // (174 vs 165 us, DESIGN.md), so direct launches are the default
-  if (const char* g = std::getenv("IMPALA_GRAPH")) h->use_graph = g[0] == '1';
   // the capture stream exists only for graph replay: every stream a process creates takes a
   // share of its GPU_MAX_HW_QUEUES hardware queues (profiles/r06w)
   if (h->use_graph && hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking) != hipSuccess) {
@@ -755,10 +719,8 @@ int impala_internal::create_learner(const impala_config* cfg, int device, int hi
   {
     RedArgs& ra = h->red;
     int ns = 0;
-    // split loads per thread the split-group count aims for (IMPALA_RED_LPT): 16 -> 10.3 us,
+    // split loads per thread the split-group count aims for (lpt, IMPALA_RED_LPT): 16 -> 10.3 us,
     // 8 -> 10.7, 4 -> 11.2, 2 -> 11.6 (rocprof, B=64 T=20 bf16, profiles/r01k)
-    int lpt = 16;
-    if (const char* e = std::getenv("IMPALA_RED_LPT")) lpt = std::max(1, std::atoi(e));
     auto add = [&](const float* slab, int S, int count, int kind, long long canon) {
       int sg = 1;
       while (sg < 16 && sg * lpt < S) sg <<= 1;  // ~lpt+ loads per thread, <= 16 groups
@@ -1187,7 +1149,7 @@ int impala_train_step_rows(impala_learner* h, const impala_batch* ring, const in
     return fail(IMPALA_E_UNSUPPORTED, "impala_train_step_rows: IMPALA handles of world_size 1");
   // only the default launches read the batch through the row map: the fused forward
   // (conv12_fwd_s2d), the fused head and the fused per-frame backward (lnc3_conv12_bwd)
-  const bool default_path = h->fwd_fused && h->lc12 && h->lnc3_fused && h->ln_fpw == h->c1_fpw;
+  const bool default_path = h->lc12 && h->ln_fpw == h->c1_fpw;
   if (!default_path)
     return fail(IMPALA_E_UNSUPPORTED, "impala_train_step_rows: not on the default kernel path");
   if (n != h->cfg.batch_size || n > kObsRowsMax)

@@ -450,84 +450,6 @@ __global__ void finalize_ppo_kernel(const float* part, int nparts, int N, float 
 }
 
 
-// LayerNorm backward + conv3 ReLU mask; per-workgroup partials of d gamma, d beta.
-template <typename T>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ dy,
-                                                     const T* __restrict__ x,
-                                                     const float* __restrict__ stats,
-                                                     const float* __restrict__ gam,
-                                                     T* __restrict__ dx,
-                                                     float* __restrict__ slab, int N, int fpw) {
-  __shared__ float red[4][2][FLAT / 4];  // reused in 4 passes of 256 columns
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float dg[16], db[16], gm[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    dg[i] = 0.f;
-    db[i] = 0.f;
-    gm[i] = gam[lane * 16 + i];
-  }
-  // the next frame's x / dy / stats are loaded while the current one is computed
-  const int nb = (blockIdx.x * 4 + wave) * fpw;
-  const int nf = max(0, min(fpw, N - nb));
-  float xn[16], dn[16], mn = 0.f, rn = 0.f;
-  auto fetch = [&](int n) {
-#pragma unroll
-    for (int i = 0; i < 16; i += 4) {
-      load4(x + (size_t)n * FLAT + lane * 16 + i, xn + i);
-      load4(dy + (size_t)n * FLAT + lane * 16 + i, dn + i);
-    }
-    mn = stats[2 * n];
-    rn = stats[2 * n + 1];
-  };
-  if (nf > 0) fetch(nb);
-  for (int f = 0; f < nf; ++f) {
-    const int n = nb + f;
-    float xv[16], d[16], xh[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { xv[i] = xn[i]; d[i] = dn[i]; }
-    const float mean = mn, rstd = rn;
-    if (f + 1 < nf) fetch(n + 1);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      xh[i] = (xv[i] - mean) * rstd;
-      const float gd = d[i] * gm[i];
-      s1 += gd;
-      s2 += gd * xh[i];
-      dg[i] += d[i] * xh[i];
-      db[i] += d[i];
-    }
-    s1 = wave_sum(s1) * (1.f / FLAT);
-    s2 = wave_sum(s2) * (1.f / FLAT);
-    float o[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float g = rstd * (d[i] * gm[i] - s1 - xh[i] * s2);
-      o[i] = xv[i] > 0.f ? g : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i += 4) store4(dx + (size_t)n * FLAT + lane * 16 + i, o + i);
-  }
-  // deterministic cross-wave reduction, 256 columns (16 lanes x 16) per pass
-  for (int pass = 0; pass < 4; ++pass) {
-    if ((lane >> 4) == pass) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        red[wave][0][(lane & 15) * 16 + i] = dg[i];
-        red[wave][1][(lane & 15) * 16 + i] = db[i];
-      }
-    }
-    __syncthreads();
-    const int c = threadIdx.x;  // 0..255
-    const float g = red[0][0][c] + red[1][0][c] + red[2][0][c] + red[3][0][c];
-    const float b = red[0][1][c] + red[1][1][c] + red[2][1][c] + red[3][1][c];
-    slab[(size_t)blockIdx.x * 2 * FLAT + pass * 256 + c] = g;
-    slab[(size_t)blockIdx.x * 2 * FLAT + FLAT + pass * 256 + c] = b;
-    __syncthreads();
-  }
-}
-
 // =========================================================================================
 // Shadow-weight emission: canonical (state_dict) index -> kernel layouts (see net.h).
 // =========================================================================================

@@ -12,36 +12,6 @@
 
 using namespace net;
 
-// conv2: rows oc (64), cols (n, oh, ow) in N*36, k = (kh*4+kw)*32 + ci over act1.
-template <typename T> struct Conv2Fwd {
-  static constexpr bool A_KMAJOR = false;
-  static constexpr bool TILE_EPI = false;
-  static constexpr int K = K2;
-  int C;
-  const T* w;
-  const float* b;
-  const T* x;
-  T* out;
-  struct ColCtx { const T* p; };
-  DEV ColCtx col_ctx(int c) const {
-    const int n = c / P2, p = c - n * P2, oh = p / H2, ow = p - oh * H2;
-    return ColCtx{x + ((size_t)(n * H1 + ST2 * oh) * H1 + ST2 * ow) * OC1};
-  }
-  DEV const T* a_row(int r, int) const { return w + r * K; }
-  DEV typename Frag<T>::vec load_b(const ColCtx& cc, int k) const {
-    const int tap = k >> 5, ci = k & 31, kh = tap >> 2, kw = tap & 3;
-    return Frag<T>::load(cc.p + (kh * H1 + kw) * OC1 + ci);
-  }
-  struct Epi { float b[4]; };
-  DEV Epi epi(int r, int) const { return Epi{{b[r], b[r + 1], b[r + 2], b[r + 3]}}; }
-  DEV void store(int r, int c, float v[4], const Epi& e) const {
-    float o[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = fmaxf(v[i] + e.b[i], 0.f);
-    store4(out + (size_t)c * OC2 + r, o);
-  }
-};
-
 // conv3: rows oc (64), cols (n, oh, ow) in N*16, k = (kh*3+kw)*64 + ci over act2.
 // act3 row n is the flattened feature vector in (p*64 + c) order.
 template <typename T> struct Conv3Fwd {
@@ -161,48 +131,6 @@ template <typename T, int HID> struct FcDgrad {
   struct Epi {};
   DEV Epi epi(int, int) const { return Epi{}; }
   DEV void store(int r, int c, float v[4], const Epi&) const { store4(dy + (size_t)c * FLAT + r, v); }
-};
-
-// conv3 dgrad (gather form): rows ci (64), cols input pixel (n, iy, ix) in N*36,
-// k = (kh*3+kw)*64 + oc; B = dact3[n][iy-kh][ix-kw][oc] (0 outside the 4x4 output).
-// Epilogue applies conv2's ReLU mask (act2 > 0).
-template <typename T> struct Conv3Dgrad {
-  static constexpr bool A_KMAJOR = true;
-  static constexpr bool TILE_EPI = false;
-  static constexpr int K = K3;
-  int C;
-  const T* w;     // w3 [64 oc][576 = tap*64 + ci]; A[ci][tap*64 + oc] read k-major
-  const T* dy;    // dact3 [n][16][64]
-  const T* act;   // act2 (mask)
-  T* dx;          // dact2
-  struct ColCtx { const T* p; int iy, ix; };
-  DEV ColCtx col_ctx(int c) const {
-    const int n = c / P2, p = c - n * P2, iy = p / H2, ix = p - iy * H2;
-    return ColCtx{dy + (size_t)n * P3 * OC3, iy, ix};
-  }
-  DEV const T* a_row(int, int) const { return nullptr; }
-  DEV const T* a_kptr(int k, int r, int) const {
-    const int tap = k >> 6, oc = k & 63;
-    return w + (size_t)oc * K3 + tap * OC2 + r;
-  }
-  DEV typename Frag<T>::vec load_b(const ColCtx& cc, int k) const {
-    const int tap = k >> 6, oc = k & 63, kh = tap / 3, kw = tap - kh * 3;
-    const int oy = cc.iy - kh, ox = cc.ix - kw;
-    if (oy < 0 || oy >= H3 || ox < 0 || ox >= H3) return Frag<T>::zero();
-    return Frag<T>::load(cc.p + (oy * H3 + ox) * OC3 + oc);
-  }
-  struct Epi { float a[4]; };  // act2 at the output position (conv2's ReLU mask)
-  DEV Epi epi(int r, int c) const {
-    Epi e;
-    load4(act + (size_t)c * OC2 + r, e.a);
-    return e;
-  }
-  DEV void store(int r, int c, float v[4], const Epi& e) const {
-    float o[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = e.a[i] > 0.f ? v[i] : 0.f;
-    store4(dx + (size_t)c * OC2 + r, o);
-  }
 };
 
 template <typename T, int HID> struct FcWgrad {  // dWfc[o][j] = sum_n dz[n][o] y[n][j]

@@ -268,7 +268,9 @@ class ImpalaLearner(Learner):
     def _rows_in_place(self) -> bool:
         """Whether the learner's steps read a DeviceReplayBuffer's slots in place
         (IMPALA_REPLAY_ROWS=0 turns it off; world size 1 only, batch <= 256; a handle that turns
-        out not to support it -- an unfuse switch is set -- falls back to gathers for good)."""
+        out not to support it -- IMPALA_LC12=0, or a frames-per-workgroup override such as
+        IMPALA_C1_FPW that unpairs the per-frame backward's runs -- falls back to gathers for
+        good)."""
         if self._rows_ok is None:
             from impala_amd.replay import DeviceReplayBuffer
             self._rows_ok = (isinstance(self._replay_buffer, DeviceReplayBuffer) and

@@ -248,8 +248,8 @@ int impala_gather_rows_hidx(const void* const* src, void* const* dst, const size
  * enqueued; the forward, the fused head and the per-frame backward read the ring's rows
  * through a row map in their launch arguments.  Bitwise equal to impala_train_step on the
  * gathered batch.  IMPALA_E_UNSUPPORTED when the handle does not run the default fused
- * kernels (an unfuse switch: IMPALA_FWD_FUSED, IMPALA_LNC3_FUSED or IMPALA_LC12 = 0),
- * world_size > 1 or PPO: gather, then impala_train_step. */
+ * per-frame backward (IMPALA_LC12 = 0, or unequal IMPALA_C1_FPW / run lengths), world_size > 1
+ * or PPO: gather, then impala_train_step. */
 int impala_train_step_rows(impala_learner* h, const impala_batch* ring, const int64_t* rows, int n,
                            int64_t capacity, void* stream);
 

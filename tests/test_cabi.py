@@ -45,6 +45,9 @@ def test_host_only_entry_points():
     assert cfg.vtrace_grad_mode == _lib.VTRACE_GRAD_MODES["sg_advantage"] == 0
     names = [lib.impala_kernel_name(i).decode() for i in range(lib.impala_kernel_count())]
     assert "conv2_dgrad_conv1_wgrad" in names and "adam" in names and len(names) == len(set(names))
+    # launches that no longer exist on their own (each is part of a fused launch)
+    for gone in ("conv1_fwd", "conv2_fwd", "fc_dgrad", "ln_bwd", "conv3_dgrad", "fc_wgrad"):
+        assert gone not in names, gone
 
 
 @pytest.mark.parametrize("field,value", [("batch_size", 0), ("rollout_length", 1),

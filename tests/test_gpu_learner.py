@@ -735,7 +735,8 @@ def test_learner_reads_device_replay_rows_in_place(monkeypatch):
     """ImpalaLearner over a DeviceReplayBuffer reads the sampled slots in place (no gather):
     bitwise the learner that gathers them (IMPALA_REPLAY_ROWS=0), with appends between the
     steps (prefetch 0: sampled and read at the step) and without (prefetch 2); and a handle on
-    non-default kernels (IMPALA_FWD_FUSED=0) falls back to gathers with the same result."""
+    the separate per-frame backward kernels (IMPALA_LC12=0), which do not read the batch through
+    the row map, falls back to gathers with the same result."""
     dev = _dev()
     from impala_amd.learner import ImpalaLearner
     from impala_amd.model import AtariPPOModel
@@ -769,8 +770,8 @@ def test_learner_reads_device_replay_rows_in_place(monkeypatch):
         assert not ok0 and ok1
         assert l0 == l1, (prefetch, appends)
         assert torch.equal(p0, p1), (prefetch, appends)
-    p2, l2, ok2 = run(True, 2, False, env=("IMPALA_FWD_FUSED", "0"))
-    p3, l3, _ = run(False, 2, False, env=("IMPALA_FWD_FUSED", "0"))
+    p2, l2, ok2 = run(True, 2, False, env=("IMPALA_LC12", "0"))
+    p3, l3, _ = run(False, 2, False, env=("IMPALA_LC12", "0"))
     assert ok2 is False  # fell back
     assert l2 == l3 and torch.equal(p2, p3)
 
