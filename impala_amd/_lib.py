@@ -79,8 +79,13 @@ DQN_EXPORTS = (
     "dqn_destroy", "dqn_bind_state", "dqn_bind_target", "dqn_sync_target", "dqn_refresh_weights",
     "dqn_set_step", "dqn_set_metrics", "dqn_set_metrics_host", "dqn_forward", "dqn_act",
     "dqn_train_step", "dqn_loss_head",
+    "dqn_replay_block", "dqn_replay_create", "dqn_replay_destroy", "dqn_replay_bind",
+    "dqn_replay_state", "dqn_replay_extend", "dqn_replay_extend_rollout", "dqn_replay_sample",
+    "dqn_replay_update", "dqn_train_step_replay", "dqn_replay_weights",
 )
-DQN_ABI_VERSION = 1
+DQN_ABI_VERSION = 2
+DQN_REPLAY_BLOCK = 512  # rows per block sum of the replay's two-level sampling
+DQN_MAX_BATCH = 4096
 DQN_NUM_METRICS = 9
 # ApexLearner metric keys (agents/dqn/learning.py:185-190) -> metrics slot (DQN_M_*)
 DQN_METRIC_SLOTS = (("train_step/q", 0), ("train_step/target", 1), ("train_step/priorities", 2),
@@ -255,6 +260,17 @@ def _declare(lib):
     lib.dqn_train_step.argtypes = [_P, C.POINTER(DqnBatch), _P]
     lib.dqn_loss_head.argtypes = [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P,
                                   _P]
+    lib.dqn_replay_create.argtypes = [C.c_int64, C.c_double, C.c_int, C.POINTER(_P)]
+    lib.dqn_replay_destroy.argtypes = [_P]
+    lib.dqn_replay_bind.argtypes = [_P, _P, _P, _P, _P, _P]
+    lib.dqn_replay_state.argtypes = [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.dqn_replay_extend.argtypes = [_P, _P, _P, _P, _P, C.c_int64, _P, _P]
+    lib.dqn_replay_extend_rollout.argtypes = [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int,
+                                              C.c_float, _P, _P]
+    lib.dqn_replay_sample.argtypes = [_P, C.c_uint64, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]
+    lib.dqn_replay_update.argtypes = [_P, _P, _P, C.c_int64, _P]
+    lib.dqn_train_step_replay.argtypes = [_P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]
+    lib.dqn_replay_weights.argtypes = [_P, _P, _P, _P]
     for name in DQN_EXPORTS:
         getattr(lib, name).restype = (C.c_char_p if name == "dqn_last_error" else
                                       C.c_size_t if name == "dqn_param_count" else C.c_int)

@@ -1,6 +1,6 @@
 """Build the HIP extension in-tree: ``python -m impala_amd.build``.
 
-Compiles ``impala_amd/csrc/{impala,sac}.hip`` for gfx950 into ``impala_amd/libimpala_hip.so`` with
+Compiles ``impala_amd/csrc/{impala,sac,dqn_replay}.hip`` for gfx950 into ``impala_amd/libimpala_hip.so`` with
 hipcc (cross-compiles without a GPU).  The .so is git-ignored and travels with the tree.
 """
 from __future__ import annotations
@@ -23,8 +23,10 @@ def sources():
 
 def hip_units():
     """The translation units linked into the one library (impala.hip: IMPALA / PPO learner and,
-    through csrc/dqn.h on the same launchers, the Ape-X DQN learner; sac.hip: SAC learner)."""
-    return [os.path.join(SRC_DIR, f) for f in ("impala.hip", "sac.hip")]
+    through csrc/dqn.h on the same launchers, the Ape-X DQN learner; sac.hip: SAC learner;
+    dqn_replay.hip: the kernels of the DQN learner's device-side replay, kept out of impala.hip's
+    code object)."""
+    return [os.path.join(SRC_DIR, f) for f in ("impala.hip", "sac.hip", "dqn_replay.hip")]
 
 
 # Per-unit flags.  impala.hip's kernels start on 1 KB boundaries of the code object (the

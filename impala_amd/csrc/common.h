@@ -227,3 +227,12 @@ DEV void gelu_fwd_grad(float z, float& h, float& g) {
   h = 0.5f * z * (1.f + e);
   g = 0.5f * (1.f + e) + z * (0.39894228040143267794f * expf(-0.5f * z * z));
 }
+
+// splitmix64's finaliser: the mixer of every counter-based uniform in the library.  act_heads_kernel,
+// dqn_act_kernel and the replay's draws key it as mix(mix(seed ^ mix(counter)) + index).
+DEV uint64_t act_mix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}

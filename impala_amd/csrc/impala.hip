@@ -1487,3 +1487,4 @@ int impala_ppo_loss_head(const float* logits, const float* values, const int64_t
 
 // the Ape-X DQN entry points (include/dqn_hip.h) on the launchers above
 #include "dqn.h"
+#include "dqn_replay.h"

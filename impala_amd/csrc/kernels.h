@@ -885,12 +885,7 @@ __global__ void split_heads_kernel(const float* __restrict__ heads, int n, int A
 // index, as torch.argmax) where the frame's deterministic flag is set, else a draw from
 // softmax(logits) by inverse CDF on a counter-based uniform (seed, counter, frame), the
 // distribution torch's softmax(-1).multinomial(1) samples from.
-DEV uint64_t act_mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// (the counter-based uniform's mixer is act_mix64, common.h)
 __global__ __launch_bounds__(256) void act_heads_kernel(const float* __restrict__ heads, int n, int A,
                                                         const uint8_t* __restrict__ det, int det_all,
                                                         uint64_t seed, uint64_t counter,

@@ -1,10 +1,13 @@
 """Ape-X DQN on the HIP learner: ``AtariDQNModel``
 (models/distributed_models.py:72-104), ``ApexLearner`` (agents/dqn/learning.py:97-191),
 ``PrioritizedReplay`` (rlmeta ReplayBuffer + PrioritizedSampler as agents/dqn/builder.py:82-89
-builds them) and ``ApexDQNBuilder`` (agents/dqn/builder.py:76-120).
+builds them), ``NativePrioritizedReplay`` (the same ring on the library's ``dqn_replay``) and
+``ApexDQNBuilder`` (agents/dqn/builder.py:76-120).
 
 The network is IMPALA's trunk with a 512-wide projection and a dueling head; the step is one
-``dqn_train_step`` call (include/dqn_hip.h).  The compute path is the HIP library only.
+``dqn_train_step`` call (include/dqn_hip.h) or, over a ``NativePrioritizedReplay``, one
+``dqn_train_step_replay`` call: sample, step and priority update.  The compute path is the HIP
+library only.
 """
 from __future__ import annotations
 
@@ -24,6 +27,8 @@ from impala_amd.model import (OBS_SHAPE, _Node, layer_init_truncated, picklable_
                               rebind_views)
 
 HIDDEN = 512
+# calls of dqn_train_step_replay made through DqnEngine.train_step_replay (this process)
+REPLAY_STEP_CALLS = 0
 
 
 def net_specs(num_actions: int = 15) -> List[Tuple[str, Tuple[int, ...]]]:
@@ -189,6 +194,20 @@ class DqnEngine:
                           _lib.ptr(prio))
         _check(_lib.lib().dqn_train_step(self._h, C.byref(b), _lib.stream_ptr(None)), "dqn_train_step")
         return prio
+
+    def train_step_replay(self, replay: "NativePrioritizedReplay", seed: int, counter: int):
+        """Sample ``batch_size`` rows of ``replay`` keyed by (seed, counter), one learner step on
+        them and the priority update, as one ``dqn_train_step_replay`` call; returns the sampled
+        keys [N] i64 and the new priorities [N] (device)."""
+        global REPLAY_STEP_CALLS
+        self._fresh()
+        keys = torch.empty(self.N, dtype=torch.int64, device=self.device)
+        prio = torch.empty(self.N, device=self.device)
+        REPLAY_STEP_CALLS += 1
+        _check(_lib.lib().dqn_train_step_replay(self._h, replay._h, int(seed), int(counter),
+                                                _lib.ptr(keys), _lib.ptr(prio),
+                                                _lib.stream_ptr(None)), "dqn_train_step_replay")
+        return keys, prio
 
 
 class AtariDQNModel(nn.Module):
@@ -440,8 +459,180 @@ class PrioritizedReplay:
             time.sleep(0.01)
 
 
+def _replay_columns(items):
+    """``(s [n,3,64,64], a [n], target [n])`` from either form ``PrioritizedReplay.extend`` takes."""
+    if isinstance(items, (list,)) and items and isinstance(items[0], (tuple, list)):
+        cols = list(zip(*items))
+        s = torch.cat([x if x.dim() == 4 else x.unsqueeze(0) for x in cols[0]])
+        a = torch.cat([x.reshape(-1) for x in cols[1]])
+        t = torch.cat([x.reshape(-1) for x in cols[2]])
+        return s, a, t
+    return items
+
+
+class NativePrioritizedReplay(PrioritizedReplay):
+    """``PrioritizedReplay`` on the library's ``dqn_replay`` (include/dqn_hip.h): the same
+    constructor, attributes and methods, every one through a ``dqn_replay_*`` entry point.  The
+    tensors ``s``, ``a``, ``target``, ``priorities`` are the bound ring arrays; the float64
+    weights, their block sums and the running maximum priority belong to the library.
+
+    ``sample`` draws by the header's contract from ``(seed, counter)``; the counter advances once
+    per call (``reset(seed)`` rewinds it), so a seeded replay repeats its draws.
+    ``extend_rollout`` is the actor's ``_async_make_replay`` (agents/dqn/learning.py:56-65).
+    """
+
+    def __init__(self, capacity: int, priority_exponent: float = 0.6, device="cuda",
+                 seed: Optional[int] = None, obs_shape=OBS_SHAPE):
+        self.capacity = int(capacity)
+        self.alpha = float(priority_exponent)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("NativePrioritizedReplay lives on the HIP path only (cuda device)")
+        if tuple(obs_shape) != OBS_SHAPE:
+            raise ValueError(f"NativePrioritizedReplay stores observations of shape {OBS_SHAPE}")
+        self._h = _lib._P()
+        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", idx)
+        _check(_lib.lib().dqn_replay_create(self.capacity, self.alpha, idx, C.byref(self._h)),
+               "dqn_replay_create")
+        self.s = torch.zeros((self.capacity,) + OBS_SHAPE, dtype=torch.uint8, device=self.device)
+        self.a = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
+        self.target = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+        self.priorities = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+        _check(_lib.lib().dqn_replay_bind(self._h, _lib.ptr(self.s), _lib.ptr(self.a),
+                                          _lib.ptr(self.target), _lib.ptr(self.priorities),
+                                          self._stream()), "dqn_replay_bind")
+        self.reset(seed)
+
+    def _stream(self) -> int:
+        return int(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            _lib.lib().dqn_replay_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, seed: Optional[int] = None) -> None:
+        self._seed = (0 if seed is None else int(seed)) & (2 ** 64 - 1)
+        self._counter = 0
+
+    def _state(self) -> Tuple[int, int]:
+        size, cursor = C.c_int64(), C.c_int64()
+        _check(_lib.lib().dqn_replay_state(self._h, C.byref(size), C.byref(cursor)), "dqn_replay_state")
+        return size.value, cursor.value
+
+    @property
+    def _size(self) -> int:
+        return self._state()[0]
+
+    @property
+    def _cursor(self) -> int:
+        return self._state()[1]
+
+    def next_draw(self) -> Tuple[int, int]:
+        """The (seed, counter) of the next sample; the counter advances."""
+        c = self._counter
+        self._counter += 1
+        return self._seed, c
+
+    def extend(self, items, priorities=None) -> torch.Tensor:
+        s, a, t = _replay_columns(items)
+        n = s.shape[0]
+        if n > self.capacity:
+            raise ValueError("more items than the ring holds")
+        s = s.to(self.device, torch.uint8).contiguous()
+        a = a.reshape(-1).to(self.device, torch.int64).contiguous()
+        t = t.reshape(-1).to(self.device, torch.float32).contiguous()
+        p = None
+        if priorities is not None:
+            p = torch.as_tensor(priorities, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+            if p.numel() != n:
+                raise ValueError("one priority per item")
+        if a.numel() != n or t.numel() != n:
+            raise ValueError("s, a, target: one row per item")
+        keys = torch.empty(n, dtype=torch.int64, device=self.device)
+        _check(_lib.lib().dqn_replay_extend(self._h, _lib.ptr(s), _lib.ptr(a), _lib.ptr(t), _lib.ptr(p),
+                                            n, _lib.ptr(keys), self._stream()), "dqn_replay_extend")
+        return keys
+
+    def extend_rollout(self, s, a, r, done, q_pi, q_star, n_step: int = 3,
+                       gamma: float = 0.99) -> torch.Tensor:
+        """One actor rollout of L steps -> L - 1 transitions with their n-step targets and initial
+        priorities ``|target - q_pi|`` (``dqn_replay_extend_rollout``).  Returns the keys written."""
+        L = s.shape[0]
+        f32 = lambda x: x.reshape(-1).to(self.device, torch.float32).contiguous()
+        s = s.to(self.device, torch.uint8).contiguous()
+        a = a.reshape(-1).to(self.device, torch.int64).contiguous()
+        d = done.reshape(-1).to(self.device).ne(0).to(torch.uint8).contiguous()
+        r, q_pi, q_star = f32(r), f32(q_pi), f32(q_star)
+        if not all(x.numel() == L for x in (a, r, d, q_pi, q_star)):
+            raise ValueError("extend_rollout: every field has one entry per step")
+        keys = torch.empty(max(L - 1, 0), dtype=torch.int64, device=self.device)
+        _check(_lib.lib().dqn_replay_extend_rollout(
+            self._h, _lib.ptr(s), _lib.ptr(a), _lib.ptr(r), _lib.ptr(d), _lib.ptr(q_pi),
+            _lib.ptr(q_star), L, int(n_step), float(gamma), _lib.ptr(keys), self._stream()),
+            "dqn_replay_extend_rollout")
+        return keys
+
+    def weights(self) -> torch.Tensor:
+        """A copy of the library's float64 weights [capacity] (``priorities ** alpha``)."""
+        return self._weights_and_max()[0]
+
+    def max_priority(self) -> torch.Tensor:
+        return self._weights_and_max()[1]
+
+    def _weights_and_max(self):
+        w = torch.empty(self.capacity, dtype=torch.float64, device=self.device)
+        m = torch.empty(1, dtype=torch.float32, device=self.device)
+        _check(_lib.lib().dqn_replay_weights(self._h, _lib.ptr(w), _lib.ptr(m), self._stream()),
+               "dqn_replay_weights")
+        return w, m
+
+    def probabilities(self) -> torch.Tensor:
+        w = self.weights()[:self._size]
+        return (w / w.sum()).float()
+
+    def sample(self, n: int, gather: bool = True):
+        """-> (keys [n] i64, (s, a, target), probabilities [n]); with ``gather=False`` the middle
+        element is None and only keys and probabilities are produced."""
+        if self._size == 0:
+            raise RuntimeError("sample from an empty replay")
+        n = int(n)
+        keys = torch.empty(n, dtype=torch.int64, device=self.device)
+        probs = torch.empty(n, dtype=torch.float32, device=self.device)
+        rows = None
+        if gather:
+            rows = (torch.empty((n,) + OBS_SHAPE, dtype=torch.uint8, device=self.device),
+                    torch.empty(n, dtype=torch.int64, device=self.device),
+                    torch.empty(n, dtype=torch.float32, device=self.device))
+        seed, counter = self.next_draw()
+        out = rows or (None, None, None)
+        _check(_lib.lib().dqn_replay_sample(self._h, seed, counter, n, _lib.ptr(keys), _lib.ptr(probs),
+                                            _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]),
+                                            self._stream()), "dqn_replay_sample")
+        return keys, rows, probs
+
+    def update(self, keys, priorities) -> None:
+        p = torch.as_tensor(priorities, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+        k = torch.as_tensor(keys).reshape(-1).to(self.device, torch.int64).contiguous()
+        if k.numel() != p.numel():
+            raise ValueError("one priority per key")
+        for i in range(0, k.numel(), _lib.DQN_MAX_BATCH):  # one workgroup per call: <= 4096 keys
+            kc, pc = k[i:i + _lib.DQN_MAX_BATCH], p[i:i + _lib.DQN_MAX_BATCH]
+            _check(_lib.lib().dqn_replay_update(self._h, _lib.ptr(kc), _lib.ptr(pc), kc.numel(),
+                                                self._stream()), "dqn_replay_update")
+
+
 class ApexLearner(Learner):
-    """agents/dqn/learning.py:97-191 with ``_train_step`` as one ``dqn_train_step`` call."""
+    """agents/dqn/learning.py:97-191 with ``_train_step`` as one ``dqn_train_step`` call, or --
+    over a ``NativePrioritizedReplay`` -- sample, step and priority update as one
+    ``dqn_train_step_replay`` call (``last_keys`` / ``last_priorities`` then hold its outputs)."""
 
     def __init__(self, model, replay_buffer, optimizer=None, batch_size: int = 512,
                  max_grad_norm: float = 40.0, importance_sampling_exponent: float = 0.4,
@@ -486,14 +677,21 @@ class ApexLearner(Learner):
     def train_step(self):
         """Sample, one device step, then the periodic target sync and weight push.  The ``debug/*``
         keys are the reference learner's; the times are host wall-clock milliseconds and the two
-        rates are transitions per second."""
+        rates are transitions per second.  Over a ``NativePrioritizedReplay`` the sample is part
+        of the one call, and ``debug/replay_sample_per_second`` and ``debug/forward_dt`` are
+        reported over the whole call."""
         clock = time.perf_counter
         begin = clock()
-        keys, batch, probabilities = self._replay_buffer.sample(self._batch_size)
-        batch = tuple(x.to(self._device) for x in batch)
-        sampled = clock()
-        metrics = self._train_step(keys, batch, probabilities)
-        stepped = clock()
+        if isinstance(self._replay_buffer, NativePrioritizedReplay):
+            metrics = self._train_step_replay()
+            sampled = stepped = clock()
+            forward_begin = begin
+        else:
+            keys, batch, probabilities = self._replay_buffer.sample(self._batch_size)
+            batch = tuple(x.to(self._device) for x in batch)
+            sampled = forward_begin = clock()
+            metrics = self._train_step(keys, batch, probabilities)
+            stepped = clock()
         self._step_counter += 1
 
         def every(period, action):  # -> ms spent in `action` when this step is a multiple of period
@@ -508,12 +706,23 @@ class ApexLearner(Learner):
         metrics.update({
             "debug/replay_sample_per_second": self._batch_size / max(sampled - begin, 1e-9),
             "debug/gradient_per_second": self._batch_size / max(stepped - begin, 1e-9),
-            "debug/forward_dt": (stepped - sampled) * 1e3,
+            "debug/forward_dt": (stepped - forward_begin) * 1e3,
             "debug/target_sync_time": sync_ms,
             "debug/update_time": push_ms,
             "debug/total_time": (clock() - begin) * 1e3,
         })
         return metrics
+
+    def _train_step_replay(self) -> Dict[str, torch.Tensor]:
+        e = self._engine
+        m = torch.empty(_lib.DQN_NUM_METRICS, dtype=torch.float32, device=e.device)
+        e.bind_metrics(m)
+        seed, counter = self._replay_buffer.next_draw()
+        self.last_keys, self.last_priorities = e.train_step_replay(self._replay_buffer, seed, counter)
+        v = m.unbind(0)
+        out = {name: v[i] for name, i in _lib.DQN_METRIC_SLOTS}
+        out["debug/priority_update_time"] = 0
+        return out
 
     def _train_step(self, keys, batch, probabilities) -> Dict[str, torch.Tensor]:  # :159-191
         e = self._engine
@@ -567,16 +776,21 @@ class ApexDQNBuilder(Builder):
         self._learner_model = None
         self._actor_model = None
 
-    def make_replay(self):  # builder.py:82-89
-        return PrioritizedReplay(self.cfg.agent.replay_buffer_size,
-                                 priority_exponent=float(self.cfg.agent.priority_exponent),
-                                 device=self.cfg.distributed.train_device,
-                                 seed=self.cfg.training.seed)
+    def make_replay(self, native: bool = False):  # builder.py:82-89
+        """``native=True``: the ring on the library's ``dqn_replay`` (NativePrioritizedReplay)."""
+        cls = NativePrioritizedReplay if native else PrioritizedReplay
+        return cls(self.cfg.agent.replay_buffer_size,
+                   priority_exponent=float(self.cfg.agent.priority_exponent),
+                   device=self.cfg.distributed.train_device,
+                   seed=self.cfg.training.seed)
 
     def make_actor(self, model, rb=None, deterministic: bool = False):  # builder.py:91-97
-        # ApexActor's targets need rlego.n_step_bootstrapped_returns, which is absent; the actor
-        # side is out of scope here
-        raise NotImplementedError("Ape-X actors are not part of the MI355X learner path")
+        # ApexActor's n-step targets and initial priorities are
+        # NativePrioritizedReplay.extend_rollout (dqn_replay_extend_rollout); the env loop around
+        # them stays out of scope here (SURVEY.md §2 rows 12-14)
+        raise NotImplementedError(
+            "Ape-X actors are not part of the MI355X learner path: feed rollouts to "
+            "NativePrioritizedReplay.extend_rollout (model.act gives q_pi / q_star)")
 
     def learner_kwargs(self) -> dict:
         """make_learner's constructor arguments (builder.py:99-110): Adam from

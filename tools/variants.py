@@ -6,6 +6,8 @@ usage: tools/variants.py <spec.py>   where spec.py defines VARIANTS = {name: [(f
 import os, runpy, shutil, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from impala_amd.build import hip_units  # noqa: E402
 OUT = os.path.join(ROOT, "build_variants")
 
 
@@ -22,8 +24,9 @@ def build(name, edits):
     os.makedirs(OUT, exist_ok=True)
     out = os.path.join(OUT, name + ".so")
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-           "-I", os.path.join(ROOT, "include"), "-o", out, os.path.join(src, "impala.hip"),
-           os.path.join(src, "sac.hip")]
+           "-I", os.path.join(ROOT, "include"), "-o", out]
+    # the product's translation units (impala_amd/build.py), from the edited copy
+    cmd += [os.path.join(src, os.path.basename(u)) for u in hip_units()]
     subprocess.run(cmd, check=True)
     shutil.rmtree(tmp)
     return out
