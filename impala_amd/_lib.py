@@ -306,11 +306,44 @@ class Unsupported(RuntimeError):
     """IMPALA_E_UNSUPPORTED: the handle cannot run this entry point (its caller falls back)."""
 
 
-def check(status: int, what: str = "") -> None:
+def check(status: int, what: str = "", last_error: str = "impala_last_error") -> None:
+    """Raise on a non-zero status, with the message of the ABI's own ``last_error`` accessor."""
     if status != 0:
-        msg = lib().impala_last_error().decode(errors="replace")
+        msg = getattr(lib(), last_error)().decode(errors="replace")
         cls = Unsupported if status == IMPALA_E_UNSUPPORTED else RuntimeError
         raise cls(f"{what or 'impala'} failed (status {status}): {msg}")
+
+
+class NativeHandle:
+    """Owner of one library handle ``_h``: a subclass names its destroy entry point (and its
+    ABI's error accessor), opens the handle once with ``_open`` and inherits the lifetime.  After
+    ``close()`` the handle is None, which every entry point refuses (status 1001)."""
+    _destroy: str
+    _last_error = "impala_last_error"
+    _h = None
+
+    def _open(self, create: str, *args) -> None:
+        """``create(*args, &handle)``: every create entry point takes its out-pointer last."""
+        h = _P()
+        check(getattr(lib(), create)(*args, C.byref(h)), create, self._last_error)
+        self._h = h
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h:
+            getattr(lib(), self._destroy)(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def device_index(device) -> int:
+        """The device's index, or the current device's when it has none (``"cuda"``)."""
+        import torch
+        return device.index if device.index is not None else torch.cuda.current_device()
 
 
 def ptr(t) -> int:

@@ -86,15 +86,6 @@ class ImpalaActorFactory:
 
 
 class ImpalaBuilder(Builder):
-    def __init__(self, cfg):
-        self.cfg = cfg
-        self._learner_model = None
-        self._actor_model = None
-
-    def _learner_cfg(self, key, default):
-        lc = self.cfg.get("learner", {}) if isinstance(self.cfg, dict) else getattr(self.cfg, "learner", {})
-        return lc.get(key, default) if lc else default
-
     def make_replay(self):  # builder.py:30-36
         cap = self.cfg.agent.replay_buffer_size
         seed = self.cfg.training.seed
@@ -149,11 +140,6 @@ class ImpalaBuilder(Builder):
 class PPOBuilder(Builder):
     """agents/ppo/builder.py:24-53 on the HIP learner."""
 
-    def __init__(self, cfg):
-        self.cfg = cfg
-        self._learner_model = None
-        self._actor_model = None
-
     def make_replay(self):  # builder.py:30-36: CircularBuffer(size, torch.cat) + UniformSampler
         return ReplayBuffer(self.cfg.agent.replay_buffer_size, seed=self.cfg.training.seed)
 
@@ -166,13 +152,10 @@ class PPOBuilder(Builder):
         from impala_amd.ppo import PPOLearner
         opt = ImpalaAdam(lr=float(self.cfg.agent.optimizer.lr),
                          eps=float(self.cfg.agent.optimizer.eps))
-        dtype = None
-        lc = self.cfg.get("learner", {}) if isinstance(self.cfg, dict) else getattr(self.cfg, "learner", {})
-        if lc:
-            dtype = lc.get("dtype", None)
         # the reference passes no cfg to the learner: constructor defaults (batch 256, clip 0.5,
         # entropy 0.01, push period 8) apply, whatever conf/agent/ppo.yaml says
-        return PPOLearner(self._learner_model if model is None else model, rb, opt, dtype=dtype)
+        return PPOLearner(self._learner_model if model is None else model, rb, opt,
+                          dtype=self._learner_cfg("dtype", None))
 
     def make_network(self, env_spec=None):  # builder.py:46-53
         obs_shape, n_act = (3, 64, 64), 15

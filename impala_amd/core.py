@@ -68,6 +68,11 @@ class Learner(abc.ABC):  # agents/core.py:49-65
 
 
 class Builder(abc.ABC):  # agents/core.py:68-91
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self._learner_model = None
+        self._actor_model = None
+
     @abc.abstractmethod
     def make_replay(self):
         ...
@@ -83,6 +88,12 @@ class Builder(abc.ABC):  # agents/core.py:68-91
     @abc.abstractmethod
     def make_network(self, env_spec):
         ...
+
+    def _learner_cfg(self, key, default):
+        """``cfg.learner.<key>`` (this project's extensions of the reference's config), or
+        ``default`` without such a section or key."""
+        lc = self.cfg.get("learner", {}) if isinstance(self.cfg, dict) else getattr(self.cfg, "learner", {})
+        return lc.get(key, default) if lc else default
 
     @property
     def actor_model(self):

@@ -18,15 +18,16 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 from impala_amd import _lib
+from impala_amd._lib import check, lib
 from impala_amd.core import Builder, Learner
+from impala_amd.flat import FlatModule, spec_count, trunk_init_flat
 from impala_amd.learner import ImpalaAdam
-from impala_amd.model import (OBS_SHAPE, _Node, layer_init_truncated, picklable_state,
-                              rebind_views)
+from impala_amd.model import OBS_SHAPE
 
 HIDDEN = 512
+_ERR = "dqn_last_error"  # the DQN ABI reports through its own accessor (_lib.check)
 # calls of dqn_train_step_replay made through DqnEngine.train_step_replay (this process)
 REPLAY_STEP_CALLS = 0
 
@@ -52,19 +53,12 @@ def param_specs(num_actions: int = 15):
 
 def param_count(num_actions: int = 15) -> int:
     """Parameters of one net (the online net alone): dqn_param_count."""
-    return sum(int(np.prod(s)) for _, s in net_specs(num_actions))
-
-
-def _check(status: int, what: str) -> None:
-    if status != 0:
-        msg = _lib.lib().dqn_last_error().decode(errors="replace")
-        cls = _lib.Unsupported if status == _lib.IMPALA_E_UNSUPPORTED else RuntimeError
-        raise cls(f"{what} failed (status {status}): {msg}")
+    return spec_count(net_specs(num_actions))
 
 
 def default_config() -> _lib.DqnConfig:
     cfg = _lib.DqnConfig()
-    _check(_lib.lib().dqn_config_default(C.byref(cfg)), "dqn_config_default")
+    check(lib().dqn_config_default(C.byref(cfg)), "dqn_config_default", _ERR)
     return cfg
 
 
@@ -80,16 +74,17 @@ def dqn_loss_head(adv, v, actions, targets, probabilities=None,
     actions = actions.reshape(-1).contiguous().to(torch.int64)
     if probabilities is not None:
         probabilities = probabilities.reshape(-1).contiguous().float()
-    _check(_lib.lib().dqn_loss_head(_lib.ptr(adv), _lib.ptr(v), _lib.ptr(actions), _lib.ptr(targets),
-                                    _lib.ptr(probabilities), N, A, importance_sampling_exponent,
-                                    _lib.ptr(out["dadv"]), _lib.ptr(out["dv"]),
-                                    _lib.ptr(out["priorities"]), _lib.ptr(out["metrics"]),
-                                    _lib.stream_ptr(None)), "dqn_loss_head")
+    check(lib().dqn_loss_head(_lib.ptr(adv), _lib.ptr(v), _lib.ptr(actions), _lib.ptr(targets),
+                              _lib.ptr(probabilities), N, A, importance_sampling_exponent,
+                              _lib.ptr(out["dadv"]), _lib.ptr(out["dv"]),
+                              _lib.ptr(out["priorities"]), _lib.ptr(out["metrics"]),
+                              _lib.stream_ptr(None)), "dqn_loss_head", _ERR)
     return out
 
 
-class DqnEngine:
+class DqnEngine(_lib.NativeHandle):
     """One ``dqn_learner`` handle bound to an ``AtariDQNModel``'s flat buffers."""
+    _destroy, _last_error = "dqn_destroy", _ERR
 
     def __init__(self, model: "AtariDQNModel", batch_size: int = 512, dtype: Optional[str] = None,
                  lr: float = 6.25e-5, eps: float = 1e-4, betas=(0.9, 0.999),
@@ -108,52 +103,39 @@ class DqnEngine:
         cfg.adam_beta1, cfg.adam_beta2 = betas
         cfg.max_grad_norm = max_grad_norm
         cfg.importance_sampling_exponent = importance_sampling_exponent
-        self._h = _lib._P()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _check(_lib.lib().dqn_create(C.byref(cfg), idx, C.byref(self._h)), "dqn_create")
+        self._open("dqn_create", C.byref(cfg), self.device_index(self.device))
         n = model.flat.numel()
         self.inference_only = inference_only
         self.exp_avg = None if inference_only else torch.zeros(n, device=self.device)
         self.exp_avg_sq = None if inference_only else torch.zeros(n, device=self.device)
         self.metrics = torch.zeros(_lib.DQN_NUM_METRICS, device=self.device)
         sp = _lib.stream_ptr(None)
-        _check(_lib.lib().dqn_bind_state(self._h, _lib.ptr(model.flat),
-                                         0 if inference_only else _lib.ptr(model.flat_grad),
-                                         _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
-                                         _lib.ptr(self.metrics), sp), "dqn_bind_state")
-        _check(_lib.lib().dqn_bind_target(self._h, _lib.ptr(model.target_flat), sp), "dqn_bind_target")
+        check(lib().dqn_bind_state(self._h, _lib.ptr(model.flat),
+                                   0 if inference_only else _lib.ptr(model.flat_grad),
+                                   _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
+                                   _lib.ptr(self.metrics), sp), "dqn_bind_state", _ERR)
+        check(lib().dqn_bind_target(self._h, _lib.ptr(model.target_flat), sp), "dqn_bind_target", _ERR)
         self._version = model._version
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            _lib.lib().dqn_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _fresh(self):
         if self._version != self.model._version:  # the flat buffers were written from outside
-            _check(_lib.lib().dqn_refresh_weights(self._h, _lib.stream_ptr(None)), "dqn_refresh_weights")
+            check(lib().dqn_refresh_weights(self._h, _lib.stream_ptr(None)), "dqn_refresh_weights", _ERR)
             self._version = self.model._version
 
     def bind_metrics(self, m: torch.Tensor) -> None:
         self.metrics = m
-        _check(_lib.lib().dqn_set_metrics(self._h, _lib.ptr(m)), "dqn_set_metrics")
+        check(lib().dqn_set_metrics(self._h, _lib.ptr(m)), "dqn_set_metrics", _ERR)
 
     def set_step(self, step: int) -> None:
-        _check(_lib.lib().dqn_set_step(self._h, int(step), _lib.stream_ptr(None)), "dqn_set_step")
+        check(lib().dqn_set_step(self._h, int(step), _lib.stream_ptr(None)), "dqn_set_step", _ERR)
 
     def forward(self, obs: torch.Tensor, target: bool = False) -> torch.Tensor:
         self._fresh()
         obs = obs.contiguous()
         n = obs.shape[0]
         q = torch.empty(n, self.A, device=self.device)
-        _check(_lib.lib().dqn_forward(self._h, _lib.ptr(obs), n, 1 if target else 0, _lib.ptr(q),
-                                      _lib.stream_ptr(None)), "dqn_forward")
+        check(lib().dqn_forward(self._h, _lib.ptr(obs), n, 1 if target else 0, _lib.ptr(q),
+                                _lib.stream_ptr(None)), "dqn_forward", _ERR)
         return q
 
     def act(self, obs: torch.Tensor, eps, seed: int, counter: int):
@@ -171,14 +153,14 @@ class DqnEngine:
         a = torch.empty(n, dtype=torch.int64, device=self.device)
         g = torch.empty(n, dtype=torch.int64, device=self.device)
         q_pi, q_star = torch.empty(n, device=self.device), torch.empty(n, device=self.device)
-        _check(_lib.lib().dqn_act(self._h, _lib.ptr(obs), n, _lib.ptr(eps_t), eps_all, int(seed),
-                                  int(counter), _lib.ptr(a), _lib.ptr(q_pi), _lib.ptr(q_star),
-                                  _lib.ptr(g), _lib.stream_ptr(None)), "dqn_act")
+        check(lib().dqn_act(self._h, _lib.ptr(obs), n, _lib.ptr(eps_t), eps_all, int(seed),
+                            int(counter), _lib.ptr(a), _lib.ptr(q_pi), _lib.ptr(q_star),
+                            _lib.ptr(g), _lib.stream_ptr(None)), "dqn_act", _ERR)
         return a, q_pi, q_star, g
 
     def sync_target(self) -> None:
         self._fresh()
-        _check(_lib.lib().dqn_sync_target(self._h, _lib.stream_ptr(None)), "dqn_sync_target")
+        check(lib().dqn_sync_target(self._h, _lib.stream_ptr(None)), "dqn_sync_target", _ERR)
 
     def train_step(self, obs, actions, targets, probabilities=None) -> torch.Tensor:
         """One learner step; returns the new priorities |err| [N] (device)."""
@@ -192,7 +174,7 @@ class DqnEngine:
                     self.device, torch.float32)]
         b = _lib.DqnBatch(_lib.ptr(keep[0]), _lib.ptr(keep[1]), _lib.ptr(keep[2]), _lib.ptr(keep[3]),
                           _lib.ptr(prio))
-        _check(_lib.lib().dqn_train_step(self._h, C.byref(b), _lib.stream_ptr(None)), "dqn_train_step")
+        check(lib().dqn_train_step(self._h, C.byref(b), _lib.stream_ptr(None)), "dqn_train_step", _ERR)
         return prio
 
     def train_step_replay(self, replay: "NativePrioritizedReplay", seed: int, counter: int):
@@ -204,13 +186,13 @@ class DqnEngine:
         keys = torch.empty(self.N, dtype=torch.int64, device=self.device)
         prio = torch.empty(self.N, device=self.device)
         REPLAY_STEP_CALLS += 1
-        _check(_lib.lib().dqn_train_step_replay(self._h, replay._h, int(seed), int(counter),
-                                                _lib.ptr(keys), _lib.ptr(prio),
-                                                _lib.stream_ptr(None)), "dqn_train_step_replay")
+        check(lib().dqn_train_step_replay(self._h, replay._h, int(seed), int(counter),
+                                          _lib.ptr(keys), _lib.ptr(prio),
+                                          _lib.stream_ptr(None)), "dqn_train_step_replay", _ERR)
         return keys, prio
 
 
-class AtariDQNModel(nn.Module):
+class AtariDQNModel(FlatModule):
     """Drop-in for ``models.distributed_models.AtariDQNModel`` on an MI355X: the online and the
     target net are one flat fp32 buffer each, exposed as ``nn.Parameter`` views under the
     reference's ``state_dict`` names (``target_net.*`` with ``requires_grad=False``)."""
@@ -225,56 +207,26 @@ class AtariDQNModel(nn.Module):
         self.action_dim = action_dim
         self.compute_dtype = dtype
         device = torch.device(device)
-        n = param_count(action_dim)
-        self.flat = torch.zeros(n, dtype=torch.float32, device=device)
-        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=device)
-        self.target_flat = torch.zeros(n, dtype=torch.float32, device=device)
         self._specs = net_specs(action_dim)
-        self._version = 0
+        self._attach_segments(device)
         self._train_engine = None
         self._infer_engine = None
         self._act_seed = int.from_bytes(os.urandom(8), "little") >> 2
         self._act_calls = 0
-        self.add_module("online_net", _Node())
-        self.add_module("target_net", _Node())
-        self._register(self.online_net, self.flat, self.flat_grad, True)
-        self._register(self.target_net, self.target_flat, None, False)
         self.reset_parameters(seed)
-        self.downstream = None
 
-    def _register(self, root, flat, grad, requires_grad):
-        off = 0
-        for name, shape in self._specs:
-            cnt = int(np.prod(shape))
-            parts = name.split(".")
-            mod = root
-            for p in parts[:-1]:
-                if not hasattr(mod, p):
-                    mod.add_module(p, _Node())
-                mod = getattr(mod, p)
-            param = nn.Parameter(flat[off:off + cnt].view(shape), requires_grad=requires_grad)
-            if grad is not None:
-                param.grad = grad[off:off + cnt].view(shape)
-            mod.register_parameter(parts[-1], param)
-            off += cnt
-        assert off == flat.numel()
+    def _segment_table(self):
+        return [("online_net", self._specs, "flat", "flat_grad"),
+                ("target_net", self._specs, "target_flat", None)]
 
     # ---------------------------------------------------------------- parameters
     def reset_parameters(self, seed: Optional[int] = None) -> None:
-        """Reference init: layers built in the reference's order on the CPU, ``layer_init_truncated``
-        on the 3 convs and 3 Linears (models/common.py:151-158), LayerNorm (1, 0); the target net
-        is a copy of the online net (distributed_models.py:77)."""
+        """Reference init (``trunk_init_flat``, after seeding the global torch RNG with ``seed``);
+        the target net is a copy of the online net (distributed_models.py:77)."""
         if seed is not None:
             torch.manual_seed(int(seed))
-        trunc = layer_init_truncated
-        layers = [trunc(nn.Conv2d(3, 32, 8, stride=4), 3 * 64),
-                  trunc(nn.Conv2d(32, 64, 4, stride=2), 32 * 16),
-                  trunc(nn.Conv2d(64, 64, 3, stride=1), 64 * 9)]
-        layers += [nn.LayerNorm(1024), trunc(nn.Linear(1024, HIDDEN), 1024),
-                   trunc(nn.Linear(HIDDEN, self.action_dim), HIDDEN), trunc(nn.Linear(HIDDEN, 1), HIDDEN)]
-        flat = torch.cat([t.detach().reshape(-1) for l in layers for t in (l.weight, l.bias)])
         with torch.no_grad():
-            self.flat.copy_(flat.to(self.flat.device))
+            self.flat.copy_(trunk_init_flat(HIDDEN, self.action_dim).to(self.flat.device))
             self.target_flat.copy_(self.flat)
         self.params_changed()
 
@@ -284,23 +236,6 @@ class AtariDQNModel(nn.Module):
             if target is not None:
                 self.target_flat.copy_(torch.as_tensor(np.asarray(target, dtype=np.float32)).to(
                     self.flat.device))
-        self.params_changed()
-
-    def params_changed(self) -> None:
-        self._version = getattr(self, "_version", 0) + 1
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        res = super().load_state_dict(state_dict, strict=strict, assign=False)
-        self.params_changed()
-        return res
-
-    def __getstate__(self):
-        return picklable_state(self)
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        rebind_views(self.online_net, self._specs, self.flat, self.flat_grad)
-        rebind_views(self.target_net, self._specs, self.target_flat, None)
         self.params_changed()
 
     # ---------------------------------------------------------------- compute
@@ -337,22 +272,20 @@ class AtariDQNModel(nn.Module):
             with torch.no_grad():
                 self.target_flat.copy_(self.flat)
 
-    def push(self) -> None:
-        if self.downstream is not None:
-            self.downstream.load_flat_from(self)
-
-    def load_flat_from(self, other: "AtariDQNModel") -> None:
-        with torch.no_grad():
-            self.flat.copy_(other.flat.to(self.flat.device, non_blocking=True))
-            self.target_flat.copy_(other.target_flat.to(self.flat.device, non_blocking=True))
-        self.params_changed()
-
     def clone_to(self, device) -> "AtariDQNModel":
-        m = AtariDQNModel(OBS_SHAPE, self.action_dim, device=device, dtype=self.compute_dtype)
-        m.load_flat_from(self)
-        for p in m.parameters():
-            p.requires_grad_(False)
-        return m
+        return self._frozen_clone(AtariDQNModel(OBS_SHAPE, self.action_dim, device=device,
+                                                dtype=self.compute_dtype))
+
+
+def _replay_columns(items):
+    """``(s [n,3,64,64], a [n], target [n])`` from either form ``PrioritizedReplay.extend`` takes."""
+    if isinstance(items, (list,)) and items and isinstance(items[0], (tuple, list)):
+        cols = list(zip(*items))
+        s = torch.cat([x if x.dim() == 4 else x.unsqueeze(0) for x in cols[0]])
+        a = torch.cat([x.reshape(-1) for x in cols[1]])
+        t = torch.cat([x.reshape(-1) for x in cols[2]])
+        return s, a, t
+    return items
 
 
 class PrioritizedReplay:
@@ -370,41 +303,46 @@ class PrioritizedReplay:
         self.capacity = int(capacity)
         self.alpha = float(priority_exponent)
         self.device = torch.device(device)
-        self.s = torch.zeros((self.capacity,) + tuple(obs_shape), dtype=torch.uint8, device=self.device)
-        self.a = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
-        self.target = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
-        self.priorities = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
-        self._size = 0
-        self._cursor = 0
+        self._alloc_ring(obs_shape)
+        self._init_sampler()
+        self.reset(seed)
+
+    def _alloc_ring(self, obs_shape) -> None:
+        cap, dev = self.capacity, self.device
+        self.s = torch.zeros((cap,) + tuple(obs_shape), dtype=torch.uint8, device=dev)
+        self.a = torch.zeros(cap, dtype=torch.int64, device=dev)
+        self.target = torch.zeros(cap, dtype=torch.float32, device=dev)
+        self.priorities = torch.zeros(cap, dtype=torch.float32, device=dev)
+
+    def _init_sampler(self) -> None:
+        self._ring_state = (0, 0)
         self._max_priority = torch.ones((), dtype=torch.float32, device=self.device)
         self._gen = torch.Generator(device=self.device)
-        self.reset(seed)
 
     def reset(self, seed: Optional[int] = None) -> None:
         self._gen.manual_seed(0 if seed is None else int(seed))
 
-    def __len__(self) -> int:
-        return self._size
+    def _state(self) -> Tuple[int, int]:
+        """-> (transitions stored, next slot written)."""
+        return self._ring_state
 
-    @property
-    def size(self) -> int:
+    _size = property(lambda self: self._state()[0])
+    _cursor = property(lambda self: self._state()[1])
+    size = _size
+
+    def __len__(self) -> int:
         return self._size
 
     def extend(self, items, priorities=None) -> torch.Tensor:
         """items: ``(s [n,3,64,64], a [n], target [n])`` or a list of per-transition triples (each
         with or without a leading dim).  Items without a priority get the current maximum.
         Returns the ring keys written."""
-        if isinstance(items, (list,)) and items and isinstance(items[0], (tuple, list)):
-            cols = list(zip(*items))
-            s = torch.cat([x if x.dim() == 4 else x.unsqueeze(0) for x in cols[0]])
-            a = torch.cat([x.reshape(-1) for x in cols[1]])
-            t = torch.cat([x.reshape(-1) for x in cols[2]])
-        else:
-            s, a, t = items
+        s, a, t = _replay_columns(items)
         n = s.shape[0]
         if n > self.capacity:
             raise ValueError("more items than the ring holds")
-        keys = (torch.arange(n, device=self.device) + self._cursor) % self.capacity
+        size, cursor = self._ring_state
+        keys = (torch.arange(n, device=self.device) + cursor) % self.capacity
         self.s[keys] = s.to(self.device)
         self.a[keys] = a.reshape(-1).to(self.device, torch.int64)
         self.target[keys] = t.reshape(-1).to(self.device, torch.float32)
@@ -414,8 +352,7 @@ class PrioritizedReplay:
             p = torch.as_tensor(priorities, dtype=torch.float32).reshape(-1).to(self.device)
             self.priorities[keys] = p
             self._max_priority = torch.maximum(self._max_priority, p.max())
-        self._cursor = (self._cursor + n) % self.capacity
-        self._size = min(self.capacity, self._size + n)
+        self._ring_state = (min(self.capacity, size + n), (cursor + n) % self.capacity)
         return keys
 
     async def async_extend(self, items, priorities=None):
@@ -459,18 +396,7 @@ class PrioritizedReplay:
             time.sleep(0.01)
 
 
-def _replay_columns(items):
-    """``(s [n,3,64,64], a [n], target [n])`` from either form ``PrioritizedReplay.extend`` takes."""
-    if isinstance(items, (list,)) and items and isinstance(items[0], (tuple, list)):
-        cols = list(zip(*items))
-        s = torch.cat([x if x.dim() == 4 else x.unsqueeze(0) for x in cols[0]])
-        a = torch.cat([x.reshape(-1) for x in cols[1]])
-        t = torch.cat([x.reshape(-1) for x in cols[2]])
-        return s, a, t
-    return items
-
-
-class NativePrioritizedReplay(PrioritizedReplay):
+class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
     """``PrioritizedReplay`` on the library's ``dqn_replay`` (include/dqn_hip.h): the same
     constructor, attributes and methods, every one through a ``dqn_replay_*`` entry point.  The
     tensors ``s``, ``a``, ``target``, ``priorities`` are the bound ring arrays; the float64
@@ -480,43 +406,27 @@ class NativePrioritizedReplay(PrioritizedReplay):
     per call (``reset(seed)`` rewinds it), so a seeded replay repeats its draws.
     ``extend_rollout`` is the actor's ``_async_make_replay`` (agents/dqn/learning.py:56-65).
     """
+    _destroy, _last_error = "dqn_replay_destroy", _ERR
 
     def __init__(self, capacity: int, priority_exponent: float = 0.6, device="cuda",
                  seed: Optional[int] = None, obs_shape=OBS_SHAPE):
-        self.capacity = int(capacity)
-        self.alpha = float(priority_exponent)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
+        device = torch.device(device)
+        if device.type != "cuda":
             raise RuntimeError("NativePrioritizedReplay lives on the HIP path only (cuda device)")
         if tuple(obs_shape) != OBS_SHAPE:
             raise ValueError(f"NativePrioritizedReplay stores observations of shape {OBS_SHAPE}")
-        self._h = _lib._P()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        _check(_lib.lib().dqn_replay_create(self.capacity, self.alpha, idx, C.byref(self._h)),
-               "dqn_replay_create")
-        self.s = torch.zeros((self.capacity,) + OBS_SHAPE, dtype=torch.uint8, device=self.device)
-        self.a = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
-        self.target = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
-        self.priorities = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
-        _check(_lib.lib().dqn_replay_bind(self._h, _lib.ptr(self.s), _lib.ptr(self.a),
-                                          _lib.ptr(self.target), _lib.ptr(self.priorities),
-                                          self._stream()), "dqn_replay_bind")
-        self.reset(seed)
+        idx = self.device_index(device)
+        self._open("dqn_replay_create", int(capacity), float(priority_exponent), idx)
+        super().__init__(capacity, priority_exponent, torch.device("cuda", idx), seed)
+        check(lib().dqn_replay_bind(self._h, _lib.ptr(self.s), _lib.ptr(self.a),
+                                    _lib.ptr(self.target), _lib.ptr(self.priorities),
+                                    self._stream()), "dqn_replay_bind", _ERR)
+
+    def _init_sampler(self) -> None:
+        """The weights, the running maximum priority, size and cursor belong to the library."""
 
     def _stream(self) -> int:
         return int(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            _lib.lib().dqn_replay_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self, seed: Optional[int] = None) -> None:
         self._seed = (0 if seed is None else int(seed)) & (2 ** 64 - 1)
@@ -524,16 +434,8 @@ class NativePrioritizedReplay(PrioritizedReplay):
 
     def _state(self) -> Tuple[int, int]:
         size, cursor = C.c_int64(), C.c_int64()
-        _check(_lib.lib().dqn_replay_state(self._h, C.byref(size), C.byref(cursor)), "dqn_replay_state")
+        check(lib().dqn_replay_state(self._h, C.byref(size), C.byref(cursor)), "dqn_replay_state", _ERR)
         return size.value, cursor.value
-
-    @property
-    def _size(self) -> int:
-        return self._state()[0]
-
-    @property
-    def _cursor(self) -> int:
-        return self._state()[1]
 
     def next_draw(self) -> Tuple[int, int]:
         """The (seed, counter) of the next sample; the counter advances."""
@@ -557,8 +459,8 @@ class NativePrioritizedReplay(PrioritizedReplay):
         if a.numel() != n or t.numel() != n:
             raise ValueError("s, a, target: one row per item")
         keys = torch.empty(n, dtype=torch.int64, device=self.device)
-        _check(_lib.lib().dqn_replay_extend(self._h, _lib.ptr(s), _lib.ptr(a), _lib.ptr(t), _lib.ptr(p),
-                                            n, _lib.ptr(keys), self._stream()), "dqn_replay_extend")
+        check(lib().dqn_replay_extend(self._h, _lib.ptr(s), _lib.ptr(a), _lib.ptr(t), _lib.ptr(p),
+                                      n, _lib.ptr(keys), self._stream()), "dqn_replay_extend", _ERR)
         return keys
 
     def extend_rollout(self, s, a, r, done, q_pi, q_star, n_step: int = 3,
@@ -574,10 +476,10 @@ class NativePrioritizedReplay(PrioritizedReplay):
         if not all(x.numel() == L for x in (a, r, d, q_pi, q_star)):
             raise ValueError("extend_rollout: every field has one entry per step")
         keys = torch.empty(max(L - 1, 0), dtype=torch.int64, device=self.device)
-        _check(_lib.lib().dqn_replay_extend_rollout(
+        check(lib().dqn_replay_extend_rollout(
             self._h, _lib.ptr(s), _lib.ptr(a), _lib.ptr(r), _lib.ptr(d), _lib.ptr(q_pi),
             _lib.ptr(q_star), L, int(n_step), float(gamma), _lib.ptr(keys), self._stream()),
-            "dqn_replay_extend_rollout")
+            "dqn_replay_extend_rollout", _ERR)
         return keys
 
     def weights(self) -> torch.Tensor:
@@ -590,8 +492,8 @@ class NativePrioritizedReplay(PrioritizedReplay):
     def _weights_and_max(self):
         w = torch.empty(self.capacity, dtype=torch.float64, device=self.device)
         m = torch.empty(1, dtype=torch.float32, device=self.device)
-        _check(_lib.lib().dqn_replay_weights(self._h, _lib.ptr(w), _lib.ptr(m), self._stream()),
-               "dqn_replay_weights")
+        check(lib().dqn_replay_weights(self._h, _lib.ptr(w), _lib.ptr(m), self._stream()),
+              "dqn_replay_weights", _ERR)
         return w, m
 
     def probabilities(self) -> torch.Tensor:
@@ -613,9 +515,9 @@ class NativePrioritizedReplay(PrioritizedReplay):
                     torch.empty(n, dtype=torch.float32, device=self.device))
         seed, counter = self.next_draw()
         out = rows or (None, None, None)
-        _check(_lib.lib().dqn_replay_sample(self._h, seed, counter, n, _lib.ptr(keys), _lib.ptr(probs),
-                                            _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]),
-                                            self._stream()), "dqn_replay_sample")
+        check(lib().dqn_replay_sample(self._h, seed, counter, n, _lib.ptr(keys), _lib.ptr(probs),
+                                      _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]),
+                                      self._stream()), "dqn_replay_sample", _ERR)
         return keys, rows, probs
 
     def update(self, keys, priorities) -> None:
@@ -625,8 +527,8 @@ class NativePrioritizedReplay(PrioritizedReplay):
             raise ValueError("one priority per key")
         for i in range(0, k.numel(), _lib.DQN_MAX_BATCH):  # one workgroup per call: <= 4096 keys
             kc, pc = k[i:i + _lib.DQN_MAX_BATCH], p[i:i + _lib.DQN_MAX_BATCH]
-            _check(_lib.lib().dqn_replay_update(self._h, _lib.ptr(kc), _lib.ptr(pc), kc.numel(),
-                                                self._stream()), "dqn_replay_update")
+            check(lib().dqn_replay_update(self._h, _lib.ptr(kc), _lib.ptr(pc), kc.numel(),
+                                          self._stream()), "dqn_replay_update", _ERR)
 
 
 class ApexLearner(Learner):
@@ -640,11 +542,7 @@ class ApexLearner(Learner):
                  model_push_period: int = 10, dtype: Optional[str] = None) -> None:
         self._model = model
         self._replay_buffer = replay_buffer
-        if optimizer is None:
-            optimizer = ImpalaAdam(lr=6.25e-5, eps=1e-4)
-        elif isinstance(optimizer, torch.optim.Optimizer):
-            optimizer = ImpalaAdam.from_torch(optimizer)
-        self._optimizer = optimizer
+        self._optimizer = optimizer = ImpalaAdam.of(optimizer, lr=6.25e-5, eps=1e-4)
         self._batch_size = batch_size
         self._max_grad_norm = max_grad_norm
         self._importance_sampling_exponent = importance_sampling_exponent
@@ -770,11 +668,6 @@ class FlexibleEpsFunc:
 
 class ApexDQNBuilder(Builder):
     """agents/dqn/builder.py:76-120 on the HIP learner."""
-
-    def __init__(self, cfg):
-        self.cfg = cfg
-        self._learner_model = None
-        self._actor_model = None
 
     def make_replay(self, native: bool = False):  # builder.py:82-89
         """``native=True``: the ring on the library's ``dqn_replay`` (NativePrioritizedReplay)."""

@@ -19,7 +19,9 @@ DTYPES = {"fp32": _lib.IMPALA_DTYPE_F32, "f32": _lib.IMPALA_DTYPE_F32,
           "bfloat16": _lib.IMPALA_DTYPE_BF16}
 
 
-class Engine:
+class Engine(_lib.NativeHandle):
+    _destroy = "impala_destroy"
+
     def __init__(self, model, batch_size: int, rollout_length: int = 20, dtype: Optional[str] = None,
                  lr: float = 1e-4, eps: float = 1e-5, betas: Tuple[float, float] = (0.9, 0.999),
                  max_grad_norm: float = 0.5, entropy_coeff: float = 0.01, world_size: int = 1,
@@ -60,10 +62,8 @@ class Engine:
         cfg.ppo_clip = float(ppo_clip)
         cfg.vtrace_grad_mode = _lib.vtrace_grad_mode(vtrace_grad_mode)
         self.cfg = cfg
-        h = C.c_void_p()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        check(L.impala_create(C.byref(cfg), idx, C.byref(h)), "impala_create")
-        self._h = h
+        self._open("impala_create", C.byref(cfg), self.device_index(self.device))
+        h = self._h
         n = model.flat.numel()
         assert n == _lib.param_count(self.num_actions)
         if inference_only:
@@ -80,19 +80,6 @@ class Engine:
         self._version = model._version
         self._metrics_host = False  # impala_set_metrics_host bound (bind_metrics)
         self._dp = False  # dp_init ran: the handle has its own RCCL communicator
-
-    # ------------------------------------------------------------------ lifecycle
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                _lib.lib().impala_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    def __del__(self):
-        self.close()
 
     @property
     def frames(self) -> int:

@@ -39,6 +39,16 @@ class ImpalaAdam:
             raise ValueError("weight_decay / amsgrad / maximize are not used by the reference")
         return ImpalaAdam(lr=float(g["lr"]), eps=float(g["eps"]), betas=tuple(g["betas"]))
 
+    @staticmethod
+    def of(optimizer, **defaults) -> "ImpalaAdam":
+        """A learner's ``optimizer`` argument as a descriptor: None -> ``ImpalaAdam(**defaults)``,
+        a torch Adam -> ``from_torch``, a descriptor as it is."""
+        if optimizer is None:
+            return ImpalaAdam(**defaults)
+        if isinstance(optimizer, torch.optim.Optimizer):
+            return ImpalaAdam.from_torch(optimizer)
+        return optimizer
+
 
 def _collate(batch, device) -> Tuple[torch.Tensor, ...]:
     """learning.py:123,142: list of B trajectories [s, a, r, g, mu] -> (B,T,...) device tensors.
@@ -123,11 +133,7 @@ class ImpalaLearner(Learner):
         learning.py:121 does."""
         self._model = model
         self._replay_buffer = replay_buffer
-        if optimizer is None:
-            optimizer = ImpalaAdam()
-        elif isinstance(optimizer, torch.optim.Optimizer):
-            optimizer = ImpalaAdam.from_torch(optimizer)
-        self._optimizer = optimizer
+        self._optimizer = optimizer = ImpalaAdam.of(optimizer)
         self._batch_size = batch_size
         self._max_grad_norm = max_grad_norm
         self._entropy_coeff = entropy_coeff

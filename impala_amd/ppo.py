@@ -61,11 +61,7 @@ class PPOLearner(Learner):
                  world_size: Optional[int] = None):
         self._model = model
         self._replay_buffer = replay_buffer
-        if optimizer is None:
-            optimizer = ImpalaAdam()
-        elif isinstance(optimizer, torch.optim.Optimizer):
-            optimizer = ImpalaAdam.from_torch(optimizer)
-        self._optimizer = optimizer
+        self._optimizer = optimizer = ImpalaAdam.of(optimizer)
         self._batch_size = batch_size
         self._max_grad_norm = max_grad_norm
         self._entropy_coeff = entropy_coeff

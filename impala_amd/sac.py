@@ -31,7 +31,8 @@ import torch.nn as nn
 
 from impala_amd import _lib
 from impala_amd.core import Actor, Builder, Learner
-from impala_amd.model import picklable_state, rebind_views
+from impala_amd.flat import FlatModule, _Node  # noqa: F401 (_Node: older pickles name it here)
+from impala_amd.learner import ImpalaAdam
 
 HIDDEN = 256
 LOG_STD_MAX = 2
@@ -58,33 +59,6 @@ def critic_specs(prefix: str, D: int, K: int) -> List[Tuple[str, Tuple[int, ...]
                 (f"{prefix}.{q}.body.2.weight", (HIDDEN, HIDDEN)), (f"{prefix}.{q}.body.2.bias", (HIDDEN,)),
                 (f"{prefix}.{q}.body.4.weight", (1, HIDDEN)), (f"{prefix}.{q}.body.4.bias", (1,))]
     return out
-
-
-def _count(specs) -> int:
-    return sum(int(np.prod(s)) for _, s in specs)
-
-
-class _Node(nn.Module):
-    pass
-
-
-def _attach(root: nn.Module, specs, flat: torch.Tensor, grad: Optional[torch.Tensor],
-            requires_grad: bool = True) -> None:
-    off = 0
-    for name, shape in specs:
-        cnt = int(np.prod(shape))
-        parts = name.split(".")
-        mod = root
-        for p in parts[:-1]:
-            if not hasattr(mod, p) or not isinstance(getattr(mod, p), nn.Module):
-                mod.add_module(p, _Node())
-            mod = getattr(mod, p)
-        param = nn.Parameter(flat[off:off + cnt].view(shape), requires_grad=requires_grad)
-        if grad is not None:
-            param.grad = grad[off:off + cnt].view(shape)
-        mod.register_parameter(parts[-1], param)
-        off += cnt
-    assert off == flat.numel()
 
 
 def _uniform_linear(fan_in: int, fan_out: int, scale: float = 0.33) -> nn.Linear:
@@ -126,7 +100,7 @@ def _dev_f32(x, device) -> torch.Tensor:
     return t.float().contiguous()
 
 
-class SoftCritic(nn.Module):
+class SoftCritic(FlatModule):
     """models/sac_model.py:154-178.  ``critic`` / ``target_critic`` / ``log_alpha`` /
     ``target_entropy`` as the reference's state_dict; target parameters do not require grad."""
 
@@ -136,17 +110,11 @@ class SoftCritic(nn.Module):
         self.obs_dim, self.act_dim = _prod(observation_space), _prod(action_space)
         D, K = self.obs_dim, self.act_dim
         device = torch.device(device)
-        n = _count(critic_specs("critic", D, K))
-        self.flat = torch.zeros(n, dtype=torch.float32, device=device)
-        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=device)
-        self.target_flat = torch.zeros(n, dtype=torch.float32, device=device)
+        self._attach_segments(device)
         self.la_buf = torch.zeros(4, dtype=torch.float32, device=device)  # value, grad, m, v
-        _attach(self, critic_specs("critic", D, K), self.flat, self.flat_grad)
-        _attach(self, critic_specs("target_critic", D, K), self.target_flat, None, requires_grad=False)
         self.log_alpha = nn.Parameter(self.la_buf[0:1].view(()))
         self.log_alpha.grad = self.la_buf[1:2].view(())
         self.register_buffer("target_entropy", torch.tensor(-float(K), dtype=torch.float32, device=device))
-        self._version = 0
         self._engine = None
         with torch.no_grad():
             self.la_buf[0] = math.log(alpha)
@@ -154,25 +122,19 @@ class SoftCritic(nn.Module):
                 self.flat.copy_(init_critic_flat(D, K).to(device))
                 self.target_flat.copy_(self.flat)
 
-    def params_changed(self) -> None:
-        self._version += 1
-
-    def __getstate__(self):  # whole-model torch.save: drop the native engine handle
-        return picklable_state(self)
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
+    def _segment_table(self):
         D, K = self.obs_dim, self.act_dim
-        rebind_views(self, critic_specs("critic", D, K), self.flat, self.flat_grad)
-        rebind_views(self, critic_specs("target_critic", D, K), self.target_flat, None)
+        return [(None, critic_specs("critic", D, K), "flat", "flat_grad"),
+                (None, critic_specs("target_critic", D, K), "target_flat", None)]
+
+    def _rebound(self) -> None:  # log_alpha is a view of la_buf, outside the two segments
         self.log_alpha.data = self.la_buf[0:1].view(())
         self.log_alpha.grad = self.la_buf[1:2].view(())
-        self.params_changed()
 
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        res = super().load_state_dict(state_dict, strict=strict, assign=False)
-        self.params_changed()
-        return res
+    def load_flat_from(self, other: "SoftCritic") -> None:
+        with torch.no_grad():  # log_alpha too: la_buf[0] (its grad and Adam state stay this copy's)
+            self.la_buf[0:1].copy_(other.la_buf[0:1].to(self.la_buf.device, non_blocking=True))
+        super().load_flat_from(other)
 
     @property
     def alpha(self) -> torch.Tensor:
@@ -192,7 +154,7 @@ class SoftCritic(nn.Module):
         return self._q(s, a, 1)
 
 
-class SoftActor(nn.Module):
+class SoftActor(FlatModule):
     """models/sac_model.py:181-203 (with Actor / ActorBody / ContionusHead).  ``forward`` ->
     (mean, log_std); ``act(obs, eps)`` -> tanh-squashed noisy action on the CPU; ``policy(s)``
     -> (action, log_prob, std) with rsample noise drawn on the device."""
@@ -204,62 +166,29 @@ class SoftActor(nn.Module):
         self.observation_space, self.action_space = observation_space, action_space
         self.compute_dtype = dtype
         device = torch.device(device)
-        specs = actor_specs(self.obs_dim, self.act_dim)
-        n = _count(specs)
-        self.flat = torch.zeros(n, dtype=torch.float32, device=device)
-        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=device)
-        _attach(self, specs, self.flat, self.flat_grad)
+        self._attach_segments(device)
         self.actor.head.register_buffer("action_scale", torch.tensor(action_scale, dtype=torch.float32))
         self.actor.head.register_buffer("action_bias", torch.tensor(action_bias, dtype=torch.float32))
-        self._version = 0
         self._train_engine = None
         self._infer_engine = None
-        self.downstream = None
         if init:
             with torch.no_grad():
                 self.flat.copy_(init_actor_flat(self.obs_dim, self.act_dim).to(device))
 
+    def _segment_table(self):
+        return [(None, actor_specs(self.obs_dim, self.act_dim), "flat", "flat_grad")]
+
     # ------------------------------------------------------------- parameters
-    def params_changed(self) -> None:
-        self._version += 1
-
-    def __getstate__(self):  # whole-model torch.save: drop the native engine handles
-        return picklable_state(self)
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        rebind_views(self, actor_specs(self.obs_dim, self.act_dim), self.flat, self.flat_grad)
-        self.params_changed()
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        res = super().load_state_dict(state_dict, strict=strict, assign=False)
-        self.params_changed()
-        return res
-
-    def load_flat_from(self, other: "SoftActor") -> None:
-        with torch.no_grad():
-            self.flat.copy_(other.flat.to(self.flat.device, non_blocking=True))
-        self.params_changed()
-
     def clone_to(self, device) -> "SoftActor":
-        m = SoftActor(self.observation_space, self.action_space,
-                      float(self.actor.head.action_scale), float(self.actor.head.action_bias),
-                      device=device, dtype=self.compute_dtype, init=False)
-        m.load_flat_from(self)
-        for p in m.parameters():
-            p.requires_grad_(False)
-        return m
+        return self._frozen_clone(SoftActor(
+            self.observation_space, self.action_space, float(self.actor.head.action_scale),
+            float(self.actor.head.action_bias), device=device, dtype=self.compute_dtype, init=False))
 
     def __deepcopy__(self, memo):  # learning.py:134 copy.deepcopy(target_actor)
         m = self.clone_to(self.flat.device)
         for p in m.parameters():
             p.requires_grad_(True)
         return m
-
-    def push(self) -> None:
-        """rlmeta DownstreamModel.push: publish the learner weights to the inference copy."""
-        if self.downstream is not None:
-            self.downstream.load_flat_from(self)
 
     # ------------------------------------------------------------- compute
     def _engine(self, n: int) -> "SACEngine":
@@ -300,8 +229,9 @@ class SoftActor(nn.Module):
         return action, logp, std
 
 
-class SACEngine:
+class SACEngine(_lib.NativeHandle):
     """One ``sac_learner`` handle bound to the modules' flat buffers (see module doc)."""
+    _destroy = "sac_destroy"
 
     def __init__(self, actor: SoftActor, critic: Optional[SoftCritic], target_actor: Optional[SoftActor],
                  batch_size: int = 256, dtype: Optional[str] = None, critic_lr: float = 3e-3,
@@ -343,9 +273,7 @@ class SACEngine:
         cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.tune_alpha = bool(tune_alpha)
         self.cfg = cfg
-        h = C.c_void_p()
-        _lib.check(L.sac_create(C.byref(cfg), dev.index or 0, C.byref(h)), "sac_create")
-        self._h = h
+        self._open("sac_create", C.byref(cfg), self.device_index(dev))
         self._versions = None
         self._bind()
 
@@ -445,28 +373,12 @@ class SACEngine:
         _lib.check(_lib.lib().sac_timer_read(self._h, C.byref(ms), C.byref(n)), "sac_timer_read")
         return float(ms.value), int(n.value)
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            _lib.lib().sac_destroy(h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _adam_hparams(opt, default_lr: float):
-    if opt is None:
-        return default_lr, 1e-5, (0.9, 0.999)
-    if not isinstance(opt, torch.optim.Adam):
+    if opt is not None and not isinstance(opt, torch.optim.Adam):
         raise TypeError("the HIP SAC learner implements torch.optim.Adam only")
-    g = opt.param_groups[0]
-    if g.get("weight_decay", 0) or g.get("amsgrad", False) or g.get("maximize", False):
-        raise ValueError("weight_decay / amsgrad / maximize are not used by the reference")
-    return float(g["lr"]), float(g["eps"]), tuple(g["betas"])
+    a = ImpalaAdam(lr=default_lr) if opt is None else ImpalaAdam.from_torch(opt)
+    return a.lr, a.eps, a.betas
 
 
 class SACLearner(Learner):
@@ -746,15 +658,6 @@ class SACActor(Actor):
 
 class SACBuilder(Builder):
     """agents/sac/builder.py:22-74 on the HIP learner."""
-
-    def __init__(self, cfg):
-        self.cfg = cfg
-        self._learner_model = None
-        self._actor_model = None
-
-    def _learner_cfg(self, key, default):
-        lc = self.cfg.get("learner", {}) if isinstance(self.cfg, dict) else getattr(self.cfg, "learner", {})
-        return lc.get(key, default) if lc else default
 
     def make_replay(self):  # builder.py:30-36
         return DeviceTransitionReplay(int(self.cfg.agent.replay_buffer_size),

@@ -244,6 +244,71 @@ def test_replay_update_changes_later_draws():
     assert float(rb.priorities[k[0]]) == 1e4
 
 
+def test_replay_extend_takes_item_lists_and_columns_alike():
+    """The per-item list form (items with and without a leading dim) and the column form go
+    through the same ``_replay_columns`` and leave the same ring, keys and priorities."""
+    from impala_amd.dqn import PrioritizedReplay
+    cols = _items(5, start=3)
+    items = [(s.unsqueeze(0), a.reshape(1), t.reshape(1)) for s, a, t in zip(*cols)]
+    items[1] = tuple(x.squeeze(0) for x in items[1])  # s [3,64,64], a and target 0-d
+    pri = torch.tensor([1., 2, 3, 4, 5])
+    rings = []
+    for pick in (lambda lo, hi: tuple(x[lo:hi] for x in cols), lambda lo, hi: items[lo:hi]):
+        rb = PrioritizedReplay(4, device="cpu", seed=0)
+        keys = [rb.extend(_items(2)), rb.extend(pick(0, 3), priorities=pri[:3]),
+                rb.extend(pick(3, 5))]  # wraps; the last two take the running maximum
+        rings.append((keys, rb.s, rb.a, rb.target, rb.priorities, len(rb), rb.size, rb._cursor))
+    for x, y in zip(*rings):
+        if isinstance(x, list):
+            assert [k.tolist() for k in x] == [k.tolist() for k in y] == [[0, 1], [2, 3, 0], [1, 2]]
+        elif isinstance(x, torch.Tensor):
+            assert torch.equal(x, y)
+        else:
+            assert x == y
+    assert rings[0][3].tolist() == [5., 6., 7., 4.] and rings[0][5:] == (4, 4, 3)
+    assert rings[0][4].tolist() == [3., 3., 3., 2.]  # no priority: the running maximum
+
+
+def test_native_replay_shares_the_base_constructor():
+    from impala_amd.dqn import NativePrioritizedReplay, PrioritizedReplay
+    mro = NativePrioritizedReplay.__mro__
+    assert mro.index(PrioritizedReplay) < mro.index(_lib.NativeHandle)
+    assert "_alloc_ring" not in vars(NativePrioritizedReplay)  # the ring is the base's
+    assert NativePrioritizedReplay._size is PrioritizedReplay._size  # one accessor, _state()
+    calls = []
+    orig = PrioritizedReplay._alloc_ring
+    PrioritizedReplay._alloc_ring = lambda self, shape: calls.append(shape)
+    try:
+        with pytest.raises(RuntimeError, match="HIP path only"):
+            NativePrioritizedReplay(2, device="cpu")
+    finally:
+        PrioritizedReplay._alloc_ring = orig
+    assert calls == []  # refused by the subclass before any allocation
+
+
+def test_native_replay_runs_the_base_constructor(monkeypatch):
+    """The whole constructor path without a GPU: the create entry point and the allocations are
+    stubbed, so ``__init__`` runs handle creation, then ``PrioritizedReplay.__init__`` (fields,
+    ring, ``reset``), and ends in the library's own refusal of ``dqn_replay_bind`` on the null
+    handle the stub left."""
+    from impala_amd.dqn import OBS_SHAPE, NativePrioritizedReplay, PrioritizedReplay
+    log = []
+
+    def alloc(self, shape):
+        log.append(("alloc", tuple(shape), self.capacity, self.alpha, str(self.device)))
+        self.s = self.a = self.target = self.priorities = None
+
+    monkeypatch.setattr(_lib.NativeHandle, "_open", lambda self, *a: log.append(("open",) + a))
+    monkeypatch.setattr(PrioritizedReplay, "_alloc_ring", alloc)
+    monkeypatch.setattr(NativePrioritizedReplay, "_stream", lambda self: 0)
+    rb = NativePrioritizedReplay.__new__(NativePrioritizedReplay)
+    with pytest.raises(RuntimeError, match=r"dqn_replay_bind failed \(status 1001\)"):
+        rb.__init__(6, priority_exponent=0.5, device="cuda:1", seed=9)
+    assert log == [("open", "dqn_replay_create", 6, 0.5, 1), ("alloc", OBS_SHAPE, 6, 0.5, "cuda:1")]
+    assert (rb._seed, rb._counter) == (9, 0)  # the base constructor's reset(seed), overridden
+    assert not hasattr(rb, "_gen")  # the sampler state stays the library's
+
+
 # ---------------------------------------------------------------- builder
 def test_builder_config_surface():
     from impala_amd.config import load_config

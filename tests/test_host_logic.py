@@ -201,6 +201,28 @@ def test_adam_descriptor_from_torch():
         ImpalaAdam.from_torch(torch.optim.SGD([p], lr=0.1))
 
 
+def test_adam_descriptor_of_a_learners_optimizer_argument():
+    """ImpalaAdam.of: None -> the learner's defaults, a torch Adam -> from_torch, a descriptor
+    unchanged; sac._adam_hparams goes through the same from_torch and keeps its own messages."""
+    from impala_amd.learner import ImpalaAdam
+    from impala_amd.sac import _adam_hparams
+    p = torch.nn.Parameter(torch.zeros(3))
+    assert ImpalaAdam.of(None) == ImpalaAdam()
+    assert ImpalaAdam.of(None, lr=6.25e-5, eps=1e-4) == ImpalaAdam(lr=6.25e-5, eps=1e-4)
+    d = ImpalaAdam(lr=2e-4, eps=1e-6, betas=(0.8, 0.9))
+    assert ImpalaAdam.of(d, lr=1.0) is d
+    assert ImpalaAdam.of(torch.optim.Adam([p], lr=3e-4, eps=1e-5), lr=1.0) == ImpalaAdam(3e-4, 1e-5)
+    with pytest.raises(TypeError):
+        ImpalaAdam.of(torch.optim.SGD([p], lr=0.1))
+    assert _adam_hparams(None, 3e-3) == (3e-3, 1e-5, (0.9, 0.999))
+    assert _adam_hparams(torch.optim.Adam([p], lr=3e-4, eps=1e-4, betas=(0.8, 0.9)), 1.0) == \
+        (3e-4, 1e-4, (0.8, 0.9))
+    with pytest.raises(TypeError, match="SAC learner"):
+        _adam_hparams(torch.optim.SGD([p], lr=0.1), 1.0)
+    with pytest.raises(ValueError, match="weight_decay"):
+        _adam_hparams(torch.optim.Adam([p], weight_decay=0.1), 1.0)
+
+
 def test_actor_make_replay_format():
     from impala_amd.builder import ImpalaActor
 
