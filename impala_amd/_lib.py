@@ -39,6 +39,7 @@ def vtrace_grad_mode(mode) -> int:
         raise ValueError(f"vtrace grad mode {mode!r}: one of {sorted(VTRACE_GRAD_MODES.values())}")
     return int(mode)
 ABI_VERSION = 3
+MAX_ROWS = 256  # kObsRowsMax: the batch rows a step reads in place from a ring
 NUM_METRICS = 9  # slots 0-6 METRIC_NAMES, 7 step, 8 PPO train/target
 METRIC_NAMES = ("train/loss", "train/entropy", "train/td", "train/pg", "train/kl",
                 "train/ratio", "train/grad_norm")
@@ -57,7 +58,8 @@ EXPORTS = (
     "impala_grad_bucket_offset_fc",
     "impala_ppo_train_step", "impala_ppo_loss_head", "impala_vtrace", "impala_loss_head", "impala_kernel_count",
     "impala_kernel_name", "impala_timer_start", "impala_timer_read", "impala_gather_rows",
-    "impala_gather_rows_hidx", "impala_train_step_rows",
+    "impala_gather_rows_hidx", "impala_train_step_rows", "impala_ppo_train_step_rows",
+    "impala_ppo_extend_rollout",
     "impala_stage_init", "impala_stage", "impala_stage_rows", "impala_stage_rows_async",
     "impala_stage_wait",
     "impala_slot_batch",
@@ -126,6 +128,13 @@ class ImpalaPpoBatch(C.Structure):
                 ("behaviour_logits", C.c_void_p)]
 
 
+class ImpalaPpoRing(C.Structure):
+    """impala_ppo_ring: a PPO transition ring's four device arrays, its capacity and A."""
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("targets", C.c_void_p),
+                ("behaviour_logits", C.c_void_p), ("capacity", C.c_int64),
+                ("num_actions", C.c_int)]
+
+
 class SacConfig(C.Structure):
     _fields_ = [
         ("obs_dim", C.c_int), ("act_dim", C.c_int), ("batch_size", C.c_int), ("dtype", C.c_int),
@@ -180,6 +189,10 @@ def _declare(lib):
     lib.impala_set_metrics.argtypes = [_P, _P]
     lib.impala_set_metrics_host.argtypes = [_P, _P]
     lib.impala_train_step_rows.argtypes = [_P, C.POINTER(ImpalaBatch), _P, C.c_int, C.c_int64, _P]
+    lib.impala_ppo_train_step_rows.argtypes = [_P, C.POINTER(ImpalaPpoBatch), _P, C.c_int,
+                                               C.c_int64, _P]
+    lib.impala_ppo_extend_rollout.argtypes = [C.POINTER(ImpalaPpoRing), C.c_int64, _P, _P, _P, _P,
+                                              _P, _P, C.c_int64, C.c_float, C.c_float, _P]
     lib.impala_forward.argtypes = [_P, _P, C.c_int, _P, _P, _P]
     lib.impala_act.argtypes = [_P, _P, C.c_int, _P, C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P,
                                _P]

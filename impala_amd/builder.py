@@ -15,7 +15,7 @@ import torch
 from impala_amd.core import Actor, Builder
 from impala_amd.learner import ImpalaAdam, ImpalaLearner
 from impala_amd.model import AtariPPOModel
-from impala_amd.replay import DeviceReplayBuffer, ReplayBuffer
+from impala_amd.replay import DeviceReplayBuffer, DeviceTransitionBuffer, ReplayBuffer
 
 
 class ImpalaActor(Actor):
@@ -141,12 +141,20 @@ class PPOBuilder(Builder):
     """agents/ppo/builder.py:24-53 on the HIP learner."""
 
     def make_replay(self):  # builder.py:30-36: CircularBuffer(size, torch.cat) + UniformSampler
-        return ReplayBuffer(self.cfg.agent.replay_buffer_size, seed=self.cfg.training.seed)
+        cap = self.cfg.agent.replay_buffer_size
+        seed = self.cfg.training.seed
+        kind = self._learner_cfg("replay", "device")
+        if kind == "device" and torch.cuda.is_available():
+            A = self._learner_model.action_dim if self._learner_model is not None else 15
+            return DeviceTransitionBuffer(cap, A, device=self.cfg.distributed.train_device,
+                                          seed=seed)
+        return ReplayBuffer(cap, seed=seed)
 
     def make_actor(self, model, rb=None, deterministic: bool = False):  # builder.py:38-39
-        # PPOActorRemote._make_replay (agents/ppo/learning.py:65-69) references an undefined
-        # `values`; the actor side is out of scope here (SURVEY.md §2 rows 12-14)
-        raise NotImplementedError("PPO actors are not part of the MI355X learner path")
+        # the reference builds PPOActorRemote(model, rb): `deterministic` is ignored and the
+        # actor's defaults (gamma 0.99, lambda 0.95, rollout_length 128) apply
+        from impala_amd.ppo import PPOActorFactory
+        return PPOActorFactory(model, rb)
 
     def make_learner(self, model, rb):  # builder.py:41-44: PPOLearner(model, rb, optimizer)
         from impala_amd.ppo import PPOLearner

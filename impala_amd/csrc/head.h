@@ -19,8 +19,9 @@
 //
 // F = (64 / S) * T <= 64 frames (S = segment = next pow2 >= T), i.e. one wavefront of lanes.
 #pragma once
+#include "conv1.h"
 #include "gemm.h"
-#include "kernels.h"
+#include "head_math.h"
 #include "net.h"
 
 using namespace net;

@@ -30,6 +30,7 @@
 #include "kernels.h"
 #include "lnc3.h"
 #include "ops.h"
+#include "ppo_replay_launch.h"
 
 namespace {
 
@@ -379,8 +380,11 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, co
     if constexpr (HID == HID_DQN) {  // the dueling head in head_step's slot (dqn_head.h)
       if (int r = launch_dqn_head<T>(h, b, st)) return r;
     } else if (int r = h->cfg.algo == IMPALA_ALGO_PPO
-                    ? klaunch(h, K_HEAD_STEP, "head_step", head_step_kernel<T, true>, hg, dim3(256), st, ha,
-                              ObsDirect{})
+                    ? (h->rows_on ? klaunch(h, K_HEAD_STEP, "head_step",
+                                            ppo_replay_dev::head_rows_kernel(sizeof(T) == 2), hg, dim3(256),
+                                            st, ha, h->obs_rows)  // (instantiated in ppo_replay.hip)
+                                  : klaunch(h, K_HEAD_STEP, "head_step", head_step_kernel<T, true>, hg, dim3(256),
+                                            st, ha, ObsDirect{}))
                     : h->rows_on
                     ? klaunch(h, K_HEAD_STEP, "head_step", head_step_kernel<T, false, ObsRows>, hg, dim3(256),
                               st, ha, h->obs_rows)
@@ -1142,27 +1146,35 @@ int impala_train_step(impala_learner* h, const impala_batch* b, void* stream) {
   });
 }
 
-int impala_train_step_rows(impala_learner* h, const impala_batch* ring, const int64_t* rows, int n,
-                           int64_t capacity, void* stream) {
-  if (!h || !ring || !rows) return fail(IMPALA_E_INVALID, "null argument");
-  if (h->cfg.world_size != 1 || h->cfg.algo != IMPALA_ALGO_IMPALA)
-    return fail(IMPALA_E_UNSUPPORTED, "impala_train_step_rows: IMPALA handles of world_size 1");
+namespace {
+// impala_train_step_rows / impala_ppo_train_step_rows: the step on n ring slots read in place.
+// What needs no handle is refused first (null pointers, n, the row range), then what the handle
+// cannot run (IMPALA_E_UNSUPPORTED), then the sizes that depend on it.
+int step_rows(impala_learner* h, const impala_batch* ring, const int64_t* rows, int n, int64_t capacity,
+              void* stream, int algo, const char* entry) {
+  const std::string who = std::string(entry) + ": ";
+  if (!ring || !rows) return fail(IMPALA_E_INVALID, who + "null argument");
+  if (n < 1 || n > kObsRowsMax)
+    return fail(IMPALA_E_INVALID, who + "n must equal batch_size (at most 256)");
+  if (capacity < 1) return fail(IMPALA_E_INVALID, who + "bad capacity");
+  for (int i = 0; i < n; ++i)
+    if (rows[i] < 0 || rows[i] >= capacity)
+      return fail(IMPALA_E_INVALID, who + "row index out of range");
+  if (!h) return fail(IMPALA_E_INVALID, who + "null handle");
+  const bool ppo = algo == IMPALA_ALGO_PPO;
+  if (h->cfg.world_size != 1 || h->cfg.algo != algo)
+    return fail(IMPALA_E_UNSUPPORTED, who + (ppo ? "PPO" : "IMPALA") + " handles of world_size 1");
   // only the default launches read the batch through the row map: the fused forward
   // (conv12_fwd_s2d), the fused head and the fused per-frame backward (lnc3_conv12_bwd)
   const bool default_path = h->lc12 && h->ln_fpw == h->c1_fpw;
-  if (!default_path)
-    return fail(IMPALA_E_UNSUPPORTED, "impala_train_step_rows: not on the default kernel path");
-  if (n != h->cfg.batch_size || n > kObsRowsMax)
-    return fail(IMPALA_E_INVALID, "impala_train_step_rows: n must equal batch_size (at most 256)");
-  if (capacity < 1 || capacity > INT32_MAX / h->cfg.rollout_length)
-    return fail(IMPALA_E_INVALID, "impala_train_step_rows: bad capacity");
-  for (int i = 0; i < n; ++i)
-    if (rows[i] < 0 || rows[i] >= capacity)
-      return fail(IMPALA_E_INVALID, "impala_train_step_rows: row index out of range");
+  if (!default_path) return fail(IMPALA_E_UNSUPPORTED, who + "not on the default kernel path");
+  if (n != h->cfg.batch_size)
+    return fail(IMPALA_E_INVALID, who + "n must equal batch_size (at most 256)");
+  if (capacity > INT32_MAX / h->cfg.rollout_length) return fail(IMPALA_E_INVALID, who + "bad capacity");
   if (int r = check_bound(h)) return r;
-  if (int r = check_batch(ring)) return r;
+  if (int r = check_batch(ring, ppo)) return r;
   CK(hipSetDevice(h->device));
-  h->obs_rows.T = h->cfg.rollout_length;
+  h->obs_rows.T = h->cfg.rollout_length;  // (1 on PPO handles: flat transitions)
   for (int i = 0; i < n; ++i) h->obs_rows.rows[i] = (int)rows[i];
   h->rows_on = true;
   // direct launches: the rows change every step, a captured graph would hold the first ones
@@ -1170,6 +1182,52 @@ int impala_train_step_rows(impala_learner* h, const impala_batch* ring, const in
   if (r == 0) r = enqueue_update(h, (hipStream_t)stream);
   h->rows_on = false;
   return r;
+}
+}  // namespace
+
+int impala_train_step_rows(impala_learner* h, const impala_batch* ring, const int64_t* rows, int n,
+                           int64_t capacity, void* stream) {
+  return step_rows(h, ring, rows, n, capacity, stream, IMPALA_ALGO_IMPALA, "impala_train_step_rows");
+}
+
+int impala_ppo_train_step_rows(impala_learner* h, const impala_ppo_batch* ring, const int64_t* rows, int n,
+                               int64_t capacity, void* stream) {
+  if (!ring) return fail(IMPALA_E_INVALID, "impala_ppo_train_step_rows: null argument");
+  const impala_batch b{ring->obs, ring->actions, ring->targets, nullptr, ring->behaviour_logits};
+  return step_rows(h, &b, rows, n, capacity, stream, IMPALA_ALGO_PPO, "impala_ppo_train_step_rows");
+}
+
+int impala_ppo_extend_rollout(const impala_ppo_ring* ring, int64_t cursor, const uint8_t* obs,
+                              const int64_t* actions, const float* rewards, const uint8_t* done,
+                              const float* logits, const float* values, int64_t L, float gamma,
+                              float lambda, void* stream) {
+  const char* who = "impala_ppo_extend_rollout: ";
+  if (!ring || !ring->obs || !ring->actions || !ring->targets || !ring->behaviour_logits || !obs ||
+      !actions || !rewards || !done || !logits || !values)
+    return fail(IMPALA_E_INVALID, std::string(who) + "null pointer");
+  if (L < 2 || L > ppo_replay_dev::kMaxRollout)
+    return fail(IMPALA_E_INVALID, std::string(who) + "L must be in [2, 1025]");
+  if (!(gamma >= 0.f && gamma <= 1.f) || !(lambda >= 0.f && lambda <= 1.f))
+    return fail(IMPALA_E_INVALID, std::string(who) + "gamma and lambda must be in [0, 1]");
+  if (ring->num_actions < 1 || ring->num_actions > net::MAX_A)
+    return fail(IMPALA_E_INVALID, std::string(who) + "num_actions must be in [1, 15]");
+  const int64_t K = L - 1, cap = ring->capacity;
+  if (cap < 1 || K > cap)
+    return fail(IMPALA_E_INVALID, std::string(who) + "K = L - 1 transitions exceed the capacity");
+  if (cursor < 0 || cursor >= cap) return fail(IMPALA_E_INVALID, std::string(who) + "cursor out of range");
+  hipStream_t st = (hipStream_t)stream;
+  // the obs rows: the ring wraps at most once, so one or two copies
+  constexpr size_t kRow = 3 * 64 * 64;
+  const int64_t first = std::min(K, cap - cursor);
+  CK(hipMemcpyAsync(ring->obs + (size_t)cursor * kRow, obs, (size_t)first * kRow, hipMemcpyDeviceToDevice, st));
+  if (first < K)
+    CK(hipMemcpyAsync(ring->obs, obs + (size_t)first * kRow, (size_t)(K - first) * kRow,
+                      hipMemcpyDeviceToDevice, st));
+  hipError_t e = ppo_replay_dev::launch_rollout(actions, rewards, done, logits, values, L, ring->num_actions,
+                                                gamma, lambda, cursor, cap, ring->actions, ring->targets,
+                                                ring->behaviour_logits, st);
+  if (e != hipSuccess) return fail((int)e, std::string("launch ppo_rollout: ") + hipGetErrorString(e));
+  return 0;
 }
 
 namespace {

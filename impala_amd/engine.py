@@ -278,6 +278,38 @@ class Engine(_lib.NativeHandle):
               "impala_train_step_rows")
         self._updated()
 
+    def ppo_ring_batch(self, ring):
+        """ring_batch for a PPO handle: a transition ring's four device arrays -- (obs u8
+        [C,3,64,64], actions i64 [C], value targets [C], behaviour logits [C,A]) -- checked once
+        -> (the library's PPO batch struct of their base addresses, C) for ppo_train_step_rows."""
+        if len(ring) != 4:
+            raise ValueError("a PPO ring is (obs, actions, targets, behaviour logits)")
+        C_, A = ring[0].shape[0], self.num_actions
+        exp = (((C_, 3, 64, 64), torch.uint8), ((C_,), torch.int64), ((C_,), torch.float32),
+               ((C_, A), torch.float32))
+        for t, (shape, dt) in zip(ring, exp):
+            if tuple(t.shape) != shape or t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"ring field: expected contiguous {dt} {shape} on {self.device}, "
+                                 f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return _lib.ImpalaPpoBatch(*[ptr(t) for t in ring]), int(C_)
+
+    def ppo_train_step_rows(self, ring, rows, stream=None):
+        """The PPO update on the transitions ``rows`` (host int64 slot indices, one per batch row)
+        read in place from a transition ring -- the four device arrays, or ppo_ring_batch's
+        result for them -- (impala_ppo_train_step_rows; bitwise the same step as train_step on
+        the gathered batch).  Raises _lib.Unsupported when the handle does not run the default
+        fused kernels."""
+        import numpy as np
+        b, cap = ring if isinstance(ring[0], _lib.ImpalaPpoBatch) else self.ppo_ring_batch(ring)
+        idx = rows if isinstance(rows, np.ndarray) and rows.dtype == np.int64 and \
+            rows.flags.c_contiguous else np.ascontiguousarray(rows, dtype=np.int64)
+        if self._version != self.model._version:
+            self.refresh_weights(stream)
+        check(_lib.lib().impala_ppo_train_step_rows(self._h, b, idx.ctypes.data, idx.size, cap,
+                                                    stream_ptr(stream)),
+              "impala_ppo_train_step_rows")
+        self._updated()
+
     def compute_grads(self, *batch, stream=None):
         b = self._batch(*batch)
         self._sync_weights(stream)

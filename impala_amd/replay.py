@@ -15,6 +15,10 @@ Two implementations with that interface:
   copied to its HBM slot with an async H2D on a side stream, so each trajectory crosses PCIe
   once however often it is replayed; ``sample`` gathers B slots on the device with the HIP
   gather kernel and returns the collated ``(B,T,...)`` batch already resident in HBM.
+
+``DeviceTransitionBuffer`` is PPO's counterpart (flat transitions, four arrays): the actor's
+rollout becomes transitions on the device (``impala_ppo_extend_rollout``) and the step reads
+the sampled slots in place.
 """
 from __future__ import annotations
 
@@ -278,3 +282,150 @@ class DeviceReplayBuffer(ReplayBuffer):
             size = self._size
         probs = np.full(batch_size, 1.0 / size)
         return keys, batch, probs
+
+
+class DeviceTransitionBuffer(ReplayBuffer):
+    """PPO's transition replay in HBM (``agents/ppo/builder.py:30-36``: CircularBuffer(size,
+    collate_fn=torch.cat) + UniformSampler, flat transitions ``[s, a, target, pi_ref]``).
+
+    It owns the ring's four device arrays -- obs u8 [C,3,64,64], actions i64 [C], value targets
+    f32 [C], behaviour logits f32 [C,A] -- and keeps the base class's cursor, size, keys and
+    generator, so for one seed and one number of stored items it draws exactly the slots the
+    host ``ReplayBuffer`` draws.
+
+    * ``extend_rollout``  the native ingest (``impala_ppo_extend_rollout``): one rollout of L
+      steps becomes K = L - 1 transitions, the lambda-return targets computed on the device.
+    * ``extend`` / ``append``  ready-made transition items from foreign actors, collated and
+      copied with torch (not a hot path).
+    * ``sample_rows``  the draw alone; the step reads the slots in place
+      (``Engine.ppo_train_step_rows``).  ``sample`` gathers them on the device.
+
+    It serves ONE host thread and ONE stream at a time, as the native DQN replay does: ingest,
+    gathers and in-place steps are all enqueued on the caller's current stream, which alone
+    orders a step after the ingests before it and an overwrite after the steps that read the
+    slot.  Nothing here waits on the device except the reuse of the pinned staging buffer."""
+
+    def __init__(self, capacity: int = 20000, num_actions: int = 15, device="cuda",
+                 seed: Optional[int] = None):
+        super().__init__(capacity, seed)
+        self._data = []  # (the base class's host rows: unused, the ring lives in HBM)
+        self.device = torch.device(device)
+        C, A = self.capacity, int(num_actions)
+        self.A = A
+        d = self.device
+        self.obs = torch.empty(C, 3, 64, 64, dtype=torch.uint8, device=d)
+        self.act = torch.zeros(C, dtype=torch.int64, device=d)
+        self.tgt = torch.zeros(C, dtype=torch.float32, device=d)
+        self.mu = torch.zeros(C, A, dtype=torch.float32, device=d)
+        self._ring = None       # the library's impala_ppo_ring of the four arrays
+        self._st_host = None    # pinned staging bytes of one rollout, and their device copy
+        self._st_dev = None
+        self._st_event = None   # the last H2D out of _st_host
+
+    @property
+    def fields(self):
+        """The ring's four arrays (obs, actions, value targets, behaviour logits)."""
+        return (self.obs, self.act, self.tgt, self.mu)
+
+    def _advance(self, n: int) -> List[int]:
+        """Book n rows appended at the cursor (under the lock): their keys."""
+        slots = (self._cursor + np.arange(n)) % self.capacity
+        keys = np.arange(self._next_key, self._next_key + n, dtype=np.int64)
+        self._keys[slots] = keys
+        self._next_key += n
+        self._cursor = int((self._cursor + n) % self.capacity)
+        self._size = min(self._size + n, self.capacity)
+        self._cv.notify_all()
+        return keys.tolist()
+
+    # byte layout of one staged rollout: obs | actions | rewards | values | logits | done
+    def _stage_views(self, buf, L):
+        A, o = self.A, 0
+        out = []
+        for n, dt in ((L * 12288, torch.uint8), (L * 8, torch.int64), (L * 4, torch.float32),
+                      (L * 4, torch.float32), (L * A * 4, torch.float32), (L, torch.uint8)):
+            out.append(buf[o:o + n].view(dt))
+            o += n
+        return out, o
+
+    def extend_rollout(self, obs, actions, rewards, done, logits, values, gamma: float = 0.99,
+                       lambda_: float = 0.95) -> List[int]:
+        """One rollout of L steps -- obs u8 [L,3,64,64], actions [L], rewards [L], done [L],
+        logits [L,A], values [L] (trailing unit dims allowed) -> K = L - 1 transitions appended
+        at the cursor with the lambda-return targets of include/impala_hip.h
+        (impala_ppo_extend_rollout); returns their keys.  Host tensors are staged through one
+        pinned buffer and one H2D copy; device tensors are read where they are."""
+        from impala_amd import _lib
+        L = int(obs.shape[0])
+        A = self.A
+        fs = [torch.as_tensor(x) for x in (obs, actions, rewards, values, logits, done)]
+        dts = (torch.uint8, torch.int64, torch.float32, torch.float32, torch.float32, torch.uint8)
+        shapes = ((L, 3, 64, 64), (L,), (L,), (L,), (L, A), (L,))
+        fs = [f.reshape(s) for f, s in zip(fs, shapes)]
+        with self._cv:
+            if all(f.device == self.device for f in fs):
+                dev = [f.to(dt).contiguous() for f, dt in zip(fs, dts)]
+            else:
+                nbytes = L * (12288 + 8 + 4 + 4 + 4 * A + 1)
+                if self._st_host is None or self._st_host.numel() < nbytes:
+                    self._st_host = torch.empty(nbytes, dtype=torch.uint8,
+                                                pin_memory=torch.cuda.is_available())
+                    self._st_dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                elif self._st_event is not None:
+                    self._st_event.synchronize()  # the previous H2D has left the pinned buffer
+                host, _ = self._stage_views(self._st_host, L)
+                for h, f, s in zip(host, fs, shapes):
+                    h.view(s).copy_(f)  # (casts to the staged dtype)
+                self._st_dev[:nbytes].copy_(self._st_host[:nbytes], non_blocking=True)
+                self._st_event = torch.cuda.Event()
+                self._st_event.record(torch.cuda.current_stream(self.device))
+                dev, _ = self._stage_views(self._st_dev, L)
+            if self._ring is None:
+                self._ring = _lib.ImpalaPpoRing(*[_lib.ptr(t) for t in self.fields],
+                                                self.capacity, A)
+            o, a, r, v, mu, d = dev
+            _lib.check(_lib.lib().impala_ppo_extend_rollout(
+                self._ring, self._cursor, _lib.ptr(o), _lib.ptr(a), _lib.ptr(r), _lib.ptr(d),
+                _lib.ptr(mu), _lib.ptr(v), L, float(gamma), float(lambda_),
+                _lib.stream_ptr(None)), "impala_ppo_extend_rollout")
+            return self._advance(L - 1)
+
+    def extend(self, items) -> List[int]:
+        """Ready-made transition items ``[s, a, target, pi_ref]`` (or one collated 4-tuple)."""
+        from impala_amd.ppo import collate_transitions
+        s, a, t, mu = collate_transitions(items, self.device)
+        keys: List[int] = []
+        with self._cv:
+            for i0 in range(0, s.shape[0], self.capacity):
+                n = min(self.capacity, s.shape[0] - i0)
+                first = min(n, self.capacity - self._cursor)
+                for dst, src in zip(self.fields, (s, a, t, mu.reshape(-1, self.A))):
+                    dst[self._cursor:self._cursor + first].copy_(src[i0:i0 + first])
+                    if first < n:
+                        dst[:n - first].copy_(src[i0 + first:i0 + n])
+                keys += self._advance(n)
+        return keys
+
+    def append(self, item) -> int:
+        return self.extend([item])[0]
+
+    def sample_rows(self, batch_size: int):
+        """-> (keys, RowSample, probs): the host generator's draw (the same call the host
+        ``ReplayBuffer.sample`` makes), without a gather.  A slot overwritten between this call
+        and the step is read with its new transition (the draw is of slots; the stream orders
+        the overwrite before the step)."""
+        with self._cv:
+            idx = self._indices(batch_size)
+            keys = self._keys[idx].copy()
+            size = self._size
+        return keys, RowSample(self, idx), np.full(batch_size, 1.0 / size)
+
+    def read_rows(self, rs: "RowSample", enqueue, stream=None):
+        """``enqueue(fields, idx, stream)`` on the caller's stream (see the class note)."""
+        cur = torch.cuda.current_stream(self.device) if stream is None else stream
+        return enqueue(self.fields, rs.idx, cur)
+
+    def sample(self, batch_size: int, stream=None):
+        """-> (keys, (obs, actions, targets, logits) gathered on the device, probs)."""
+        keys, rs, probs = self.sample_rows(batch_size)
+        return keys, rs.gather(stream), probs

@@ -9,6 +9,10 @@
  *   impala_compute_grads   learning.py:141-170 (zero_grad .. loss.backward + metrics)
  *   impala_ppo_train_step  agents/ppo/learning.py:131-143  PPOLearner._train_step
  *                          (losses.py:131-155 ppo_loss, backward, clip, Adam)
+ *   impala_ppo_train_step_rows  the same step on transitions read in place from a ring in
+ *                          HBM (agents/ppo/builder.py:30-36 replay + learning.py:121-123)
+ *   impala_ppo_extend_rollout   agents/ppo/learning.py:65-69 PPOActorRemote._make_replay (the
+ *                          lambda-return targets; the reference line cannot run: parity unpinned)
  *   impala_apply_update    learning.py:172-176 (clip_grad_norm_ + optimizer.step), after the
  *                          caller's gradient all-reduce in the data-parallel learner
  *   impala_forward         models/distributed_models.py:17-19 AtariPPOModel.forward
@@ -252,6 +256,53 @@ int impala_gather_rows_hidx(const void* const* src, void* const* dst, const size
  * or PPO: gather, then impala_train_step. */
 int impala_train_step_rows(impala_learner* h, const impala_batch* ring, const int64_t* rows, int n,
                            int64_t capacity, void* stream);
+
+/* impala_ppo_train_step on n == batch_size <= 256 transitions read in place from a ring:
+ * `ring` holds the ring's four arrays -- obs u8 [capacity][3][64][64], actions i64 [capacity],
+ * value targets f32 [capacity], behaviour logits f32 [capacity][A] (device memory) -- and
+ * rows[] (host int64, each in [0, capacity)) the sampled slots.  Bitwise equal to
+ * impala_ppo_train_step on the gathered batch.  IMPALA_E_UNSUPPORTED under the conditions
+ * impala_train_step_rows names (there: PPO handles; here: IMPALA handles): gather, then
+ * impala_ppo_train_step.  The null-pointer, n and row-range checks need no handle and run
+ * first. */
+int impala_ppo_train_step_rows(impala_learner* h, const impala_ppo_batch* ring,
+                               const int64_t* rows, int n, int64_t capacity, void* stream);
+
+/* A PPO transition ring in HBM (caller-owned; DeviceTransitionBuffer). */
+typedef struct {
+  uint8_t* obs;              /* [capacity][3][64][64] */
+  int64_t* actions;          /* [capacity]            */
+  float*   targets;          /* [capacity]            */
+  float*   behaviour_logits; /* [capacity][num_actions] */
+  int64_t  capacity;
+  int      num_actions;      /* 1..15 */
+} impala_ppo_ring;
+
+/* PPOActorRemote._make_replay (agents/ppo/learning.py:65-69) on one rollout of L steps (device
+ * arrays: obs u8 [L][3][64][64], actions i64 [L], rewards f32 [L], done u8 [L], logits f32
+ * [L][A], values f32 [L]): appends K = L - 1 transitions (obs[t], actions[t], target[t],
+ * logits[t]) to ring rows (cursor + t) % capacity; no other row is written.  It takes no learner
+ * handle, like impala_gather_rows, and keeps no cursor: the caller advances its own by K.
+ *
+ * target = rlax lambda_returns(r[:-1], discount[:-1], v[1:], lambda), reading the `values` that
+ * learning.py:68 leaves undefined as the actor's v.  In fp32, every operation rounded once (no
+ * fused multiply-add), in this order:
+ *   d_t = done[t] ? 0 : gamma;  oml = 1 - lambda;  acc = v[L-1]
+ *   for t = K-1 .. 0:  p = oml * v[t+1];  q = lambda * acc;  s = p + q;  m = d_t * s;
+ *                      acc = r[t] + m;  target[t] = acc
+ * PARITY UNPINNED: rlego is absent and the reference line cannot run as shipped, as for V-trace
+ * (impala_vtrace) and the n-step targets (dqn_replay_extend_rollout); the restatement is held to
+ * a float64 transcription of rlax's scan (tests/ppo_rollout_oracle.py).
+ *
+ * One kernel (one workgroup: r, d, v staged in LDS, the scan on one lane, then all threads
+ * write the rows) and at most two device-to-device copies of obs rows (the ring wraps at most
+ * once), all on `stream`; the call never synchronises with the host.  IMPALA_E_INVALID before
+ * any launch unless 2 <= L <= 1025, K <= capacity, 0 <= cursor < capacity, gamma and lambda in
+ * [0, 1], 1 <= num_actions <= 15 and no pointer is null. */
+int impala_ppo_extend_rollout(const impala_ppo_ring* ring, int64_t cursor, const uint8_t* obs,
+                              const int64_t* actions, const float* rewards, const uint8_t* done,
+                              const float* logits, const float* values, int64_t L, float gamma,
+                              float lambda, void* stream);
 
 /* Host staging ring (SURVEY.md §8(b) impala_stage; replaces the 5·B pageable `.to(device)`
  * copies of learning.py:121-123).  The handle owns `nslots` device batch slots of B*T frames
