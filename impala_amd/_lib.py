@@ -83,7 +83,7 @@ DQN_EXPORTS = (
     "dqn_train_step", "dqn_loss_head",
     "dqn_replay_block", "dqn_replay_create", "dqn_replay_destroy", "dqn_replay_bind",
     "dqn_replay_state", "dqn_replay_extend", "dqn_replay_extend_rollout", "dqn_replay_sample",
-    "dqn_replay_update", "dqn_train_step_replay", "dqn_replay_weights",
+    "dqn_replay_update", "dqn_train_step_replay", "dqn_train_step_replay_rows", "dqn_replay_weights",
 )
 DQN_ABI_VERSION = 2
 DQN_REPLAY_BLOCK = 512  # rows per block sum of the replay's two-level sampling
@@ -283,6 +283,7 @@ def _declare(lib):
     lib.dqn_replay_sample.argtypes = [_P, C.c_uint64, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]
     lib.dqn_replay_update.argtypes = [_P, _P, _P, C.c_int64, _P]
     lib.dqn_train_step_replay.argtypes = [_P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]
+    lib.dqn_train_step_replay_rows.argtypes = [_P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]
     lib.dqn_replay_weights.argtypes = [_P, _P, _P, _P]
     for name in DQN_EXPORTS:
         getattr(lib, name).restype = (C.c_char_p if name == "dqn_last_error" else

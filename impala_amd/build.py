@@ -1,6 +1,6 @@
 """Build the HIP extension in-tree: ``python -m impala_amd.build``.
 
-Compiles ``impala_amd/csrc/{impala,sac,dqn_replay,ppo_replay}.hip`` for gfx950 into ``impala_amd/libimpala_hip.so`` with
+Compiles ``impala_amd/csrc/{impala,sac,dqn_replay,ppo_replay,dqn_inplace}.hip`` for gfx950 into ``impala_amd/libimpala_hip.so`` with
 hipcc (cross-compiles without a GPU).  The .so is git-ignored and travels with the tree.
 """
 from __future__ import annotations
@@ -25,9 +25,11 @@ def hip_units():
     """The translation units linked into the one library (impala.hip: IMPALA / PPO learner and,
     through csrc/dqn.h on the same launchers, the Ape-X DQN learner; sac.hip: SAC learner;
     dqn_replay.hip: the kernels of the DQN learner's device-side replay, kept out of impala.hip's
-    code object; ppo_replay.hip: the PPO actor's lambda-return ingest kernel, kept out likewise)."""
+    code object; ppo_replay.hip: the PPO actor's lambda-return ingest kernel, kept out likewise;
+    dqn_inplace.hip: the DQN step's three batch-reading kernels instantiated for a replay ring read in
+    place, kept out likewise)."""
     return [os.path.join(SRC_DIR, f)
-            for f in ("impala.hip", "sac.hip", "dqn_replay.hip", "ppo_replay.hip")]
+            for f in ("impala.hip", "sac.hip", "dqn_replay.hip", "ppo_replay.hip", "dqn_inplace.hip")]
 
 
 # Per-unit flags.  impala.hip's kernels start on 1 KB boundaries of the code object (the
@@ -36,8 +38,9 @@ def hip_units():
 # before them is added or removed.  The kernels' own machine code is unchanged
 # (profiles/onepath: ab.txt, isa_cmp.txt).
 _ALIGN_1K = ["-Xarch_device", "-falign-functions=1024"]
-# (ppo_replay.hip holds a learner step's kernel too: the PPO head that reads a ring in place)
-UNIT_FLAGS = {"impala.hip": _ALIGN_1K, "ppo_replay.hip": _ALIGN_1K}
+# (ppo_replay.hip and dqn_inplace.hip hold learner-step kernels too: the PPO head and the DQN
+# step's kernels that read a ring in place)
+UNIT_FLAGS = {"impala.hip": _ALIGN_1K, "ppo_replay.hip": _ALIGN_1K, "dqn_inplace.hip": _ALIGN_1K}
 
 
 def needs_build(out: str = OUT) -> bool:

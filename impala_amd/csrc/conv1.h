@@ -76,6 +76,31 @@ struct ObsRows {
     return (size_t)rows[b] * (size_t)T + (f - (size_t)b * (size_t)T);
   }
 };
+// ObsKeys (dqn_train_step_replay_rows): flat transitions of a replay ring read in place through
+// the keys the replay drew on the device -- keys[f] is the ring row of transition f, f < N.  A
+// key in front of every prefetched frame would be a dependent global load, an L2 round trip in
+// the frame pipeline, so the per-frame kernels read through the workgroup's view instead
+// (obs_wg): every wave loads the keys of the workgroup's frames once, lane l the key of frame
+// min(f0 + l, N - 1) -- one load, indices clamped to real transitions -- and map() is a
+// v_readlane at the wave-uniform f - f0.  That holds <= 64 frames per workgroup and rows below
+// 2^31 (the host checks both).  The dueling head, one lane per transition, calls ObsKeys::map
+// itself, once, with its clamped transition.
+struct ObsKeys {
+  const long long* keys;
+  DEV size_t map(size_t f) const { return (size_t)keys[f]; }
+};
+constexpr int kObsKeysFpwMax = 64;
+struct ObsKeysWg {
+  int f0, key;
+  DEV size_t map(size_t f) const {
+    return (size_t)(uint32_t)__builtin_amdgcn_readlane(key, (int)f - f0);
+  }
+};
+// the map as a workgroup on frames f0 .. reads it: the map itself, or ObsKeys' loaded view
+template <class O> DEV const O& obs_wg(const O& rm, int, int) { return rm; }
+DEV ObsKeysWg obs_wg(const ObsKeys& rm, int f0, int N) {
+  return ObsKeysWg{f0, (int)rm.keys[min(f0 + ((int)threadIdx.x & 63), N - 1)]};
+}
 
 template <typename T, int LDI>
 DEV void c1_stash_frame(T* img, int tid, const uint4 v[3]) {
@@ -730,7 +755,8 @@ __global__ __launch_bounds__(c12f_threads<T>()) void conv12_fwd_s2d(
   // constant 100 MHz clock as its first workgroup starts (one vector store; nullptr = off)
   if (step_stamp != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
     *step_stamp = __builtin_amdgcn_s_memrealtime();
-  conv12_fwd_body<T, O>(x, w1, b1, w2, b2, act1, mask, act2, N, fpw, c3, (int)blockIdx.x, smem, rm);
+  conv12_fwd_body<T>(x, w1, b1, w2, b2, act1, mask, act2, N, fpw, c3, (int)blockIdx.x, smem,
+                     obs_wg(rm, (int)blockIdx.x * fpw, N));
 }
 
 // ---------------------------------------------------------------------------------------

@@ -47,6 +47,9 @@ int launch_dqn_head(impala_learner* h, const impala_batch* b, hipStream_t st) {
   ha.N = h->N; ha.A = h->A; ha.beta = h->dqn_beta;
   ha.dz = h->dz; ha.partials = h->loss_part; ha.slab_h = h->s_h; ha.slab_bh = h->s_bh;
   ha.prio = h->dqn_prio;
+  if (h->keys_on)  // act / tgt are a replay ring read in place (instantiated in dqn_inplace.hip)
+    return klaunch(h, K_HEAD_STEP, "head_step", dqn_inplace_dev::head_keys_kernel<T>(),
+                   dim3(h->n_loss_wg, DQN_SPLIT), dim3(256), st, ha, h->obs_keys);
   return klaunch(h, K_HEAD_STEP, "head_step", dqn_head_step_kernel<T>, dim3(h->n_loss_wg, DQN_SPLIT),
                  dim3(256), st, ha);
 }

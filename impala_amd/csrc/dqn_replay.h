@@ -1,7 +1,9 @@
 // Host side of the device-side prioritized replay of the Ape-X DQN learner (include/dqn_hip.h,
 // dqn_replay_*).  Included at the end of impala.hip after dqn.h: dqn_train_step_replay enqueues
 // the step exactly as dqn_train_step does, and the batch gather is gather_rows_kernel with its
-// device index.  The replay's own kernels live in csrc/dqn_replay.hip (a translation unit of its
+// device index; dqn_train_step_replay_rows skips the gather and switches the core handle's key
+// map on (ObsKeys, conv1.h), so the step reads the sampled ring rows in place through the kernels
+// of csrc/dqn_inplace.hip.  The replay's own kernels live in csrc/dqn_replay.hip (a translation unit of its
 // own, so impala.hip's code object does not change with them) behind csrc/dqn_replay_launch.h;
 // the ring's bookkeeping and the argument checks are csrc/dqn_replay_host.h.
 #pragma once
@@ -29,6 +31,12 @@ struct dqn_replay {
   uint8_t* g_obs = nullptr;
   int64_t *g_act = nullptr, *g_keys = nullptr;
   float *g_tgt = nullptr, *g_prob = nullptr, *g_prio = nullptr;
+  // library-owned per-transition scratch of one batch read in place (dqn_train_step_replay_rows):
+  // keys, probabilities, priorities -- no obs rows
+  char* sbuf = nullptr;
+  int s_rows = 0;
+  int64_t* s_keys = nullptr;
+  float *s_prob = nullptr, *s_prio = nullptr;
 };
 
 namespace {
@@ -118,6 +126,21 @@ int replay_ensure_gather(dqn_replay* r, int n) {
   return 0;
 }
 
+int replay_ensure_scratch(dqn_replay* r, int n) {
+  if (r->s_rows >= n) return 0;
+  if (r->sbuf) CK(hipFree(r->sbuf));  // (synchronises: no launch still reads it)
+  r->sbuf = nullptr;
+  r->s_rows = 0;
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_prob = al((size_t)n * 8), o_prio = o_prob + al((size_t)n * 4);
+  CK(hipMalloc((void**)&r->sbuf, o_prio + al((size_t)n * 4)));
+  r->s_keys = (int64_t*)r->sbuf;
+  r->s_prob = (float*)(r->sbuf + o_prob);
+  r->s_prio = (float*)(r->sbuf + o_prio);
+  r->s_rows = n;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -161,6 +184,7 @@ int dqn_replay_destroy(dqn_replay* r) {
   (void)hipSetDevice(r->device);
   (void)hipDeviceSynchronize();
   if (r->gbuf) (void)hipFree(r->gbuf);
+  if (r->sbuf) (void)hipFree(r->sbuf);
   if (r->state) (void)hipFree(r->state);
   delete r;
   return 0;
@@ -283,6 +307,44 @@ int dqn_train_step_replay(dqn_learner* h, dqn_replay* r, uint64_t seed, uint64_t
   const impala_batch ib = dqn_core_batch(&b);
   if (int e = enqueue_grads(c, &ib, st)) return e;
   if (int e = enqueue_update(c, st)) return e;
+  return replay_enqueue_update(r, keys, prio, N, st);
+}
+
+int dqn_train_step_replay_rows(dqn_learner* h, dqn_replay* r, uint64_t seed, uint64_t counter,
+                               int64_t* keys_out, float* priorities_out, void* stream) {
+  if (int e = dqn_check(h, true, false)) return e;
+  if (int e = replay_check(r, true)) return e;
+  impala_learner* c = h->core;
+  if (r->device != c->device)
+    return fail(IMPALA_E_INVALID, "dqn_train_step_replay_rows: the replay and the learner are on different devices");
+  if (r->ring.size < 1) return fail(IMPALA_E_STATE, "dqn_train_step_replay_rows: the replay is empty (size 0)");
+  // only the default launches read the batch through the key map: the fused forward
+  // (conv12_fwd_s2d), the dueling head and the fused per-frame backward (lnc3_conv12_bwd), whose
+  // workgroups hold their frames' keys one per lane, as 32-bit rows (conv1.h, ObsKeysWg)
+  const int N = c->N;
+  const int fwd_fpw = c->c12f_fpw > 0 ? c->c12f_fpw : std::max(1, cdiv(N, c->n_cu));
+  if (!c->lc12 || c->ln_fpw != c->c1_fpw || fwd_fpw > kObsKeysFpwMax || c->ln_fpw > kObsKeysFpwMax ||
+      r->ring.cap > (int64_t)INT32_MAX)
+    return fail(IMPALA_E_UNSUPPORTED, "dqn_train_step_replay_rows: not on the default kernel path");
+  CK(hipSetDevice(c->device));
+  if (int e = replay_ensure_scratch(r, N)) return e;
+  hipStream_t st = (hipStream_t)stream;
+  // the caller's arrays, where given, take the keys and the new priorities directly (no copies)
+  int64_t* keys = keys_out ? keys_out : r->s_keys;
+  float* prio = priorities_out ? priorities_out : r->s_prio;
+  if (int e = replay_enqueue_draws(r, seed, counter, N, keys, r->s_prob, st)) return e;
+  dqn_batch b{};  // the bound ring is the batch; transition f is its row keys[f]
+  b.obs = r->obs; b.actions = r->actions; b.targets = r->targets; b.probabilities = r->s_prob;
+  b.priorities = prio;
+  c->dqn_prio = b.priorities;
+  const impala_batch ib = dqn_core_batch(&b);
+  static_assert(sizeof(long long) == sizeof(int64_t), "ObsKeys reads the int64 keys");
+  c->obs_keys.keys = reinterpret_cast<const long long*>(keys);
+  c->keys_on = true;
+  int e = enqueue_grads(c, &ib, st);
+  if (e == 0) e = enqueue_update(c, st);
+  c->keys_on = false;
+  if (e) return e;
   return replay_enqueue_update(r, keys, prio, N, st);
 }
 

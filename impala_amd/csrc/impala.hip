@@ -25,6 +25,7 @@
 
 #include "../../include/impala_hip.h"
 #include "dqn_head.h"
+#include "dqn_inplace_launch.h"
 #include "head.h"
 #include "hostpool.h"
 #include "kernels.h"
@@ -131,6 +132,10 @@ struct impala_learner {
   // replay ring through obs_rows (conv12_fwd_s2d, head_step_kernel, lnc3_conv12_bwd)
   bool rows_on = false;
   ObsRows obs_rows{};
+  // dqn_train_step_replay_rows: likewise through obs_keys, the keys the replay drew on the device
+  // (the same three launches, instantiated in dqn_inplace.hip)
+  bool keys_on = false;
+  ObsKeys obs_keys{};
   // library-owned
   char* ws = nullptr;
   size_t ws_bytes = 0;
@@ -265,7 +270,13 @@ int launch_forward(impala_learner* h, const uint8_t* obs, int n, hipStream_t st,
                    vv + Vecs::b1, sw + sh.w2, vv + Vecs::b2, (T*)h->act1, h->mask1,
                    (T*)h->act2, n, fpw, c3, with_heads ? nullptr : step_stamp(h), rm);
   };
-  if (int r = h->rows_on && !with_heads ? fwd(h->obs_rows) : fwd(ObsDirect{})) return r;
+  if (h->keys_on && !with_heads) {  // (instantiated in dqn_inplace.hip)
+    if (int r = klaunch(h, conv3_done ? K_CONV123_FWD : K_CONV12_FWD, "conv12_fwd",
+                        dqn_inplace_dev::fwd_keys_kernel<T>(), dim3(cdiv(n, fpw)), dim3(c12f_threads<T>()), st,
+                        obs, sw + sh.w1, vv + Vecs::b1, sw + sh.w2, vv + Vecs::b2, (T*)h->act1, h->mask1,
+                        (T*)h->act2, n, fpw, c3, step_stamp(h), h->obs_keys))
+      return r;
+  } else if (int r = h->rows_on && !with_heads ? fwd(h->obs_rows) : fwd(ObsDirect{})) return r;
   if (!conv3_done) {  // more frames per workgroup than the tail takes, or IMPALA_C3_TAIL=0
     Conv3LnFwd<T> op{};
     op.C = n * P3; op.w = sw + sh.w3; op.b = vv + Vecs::b3; op.x = (const T*)h->act2;
@@ -416,7 +427,15 @@ int launch_backward(impala_learner* h, const impala_batch* b, hipStream_t st, co
                        sw + sh.w2, sw + sh.w2t, (const uint32_t*)h->mask1, h->s_w1, h->s_b1, N,
                        h->ln_fpw, rm);
       };
-      if (int r = h->rows_on ? bwd(h->obs_rows) : bwd(ObsDirect{})) return r;
+      if (h->keys_on) {  // (instantiated in dqn_inplace.hip)
+        if (int r = klaunch(h, K_LNC12_BWD, "ln_conv3_conv2_dgrad_conv1_wgrad",
+                            dqn_inplace_dev::bwd_keys_kernel<T>(), dim3(h->n_ln_wg), dim3(lnc3_threads<T>()), st,
+                            (const float*)h->dy, (const T*)h->act3, (const float*)h->lnstat,
+                            (const float*)(h->vecs + Vecs::lng), sw + sh.w3, sw + sh.w3t, (const T*)h->act2,
+                            (T*)h->dact3, (T*)h->dact2, h->s_ln, b->obs, sw + sh.w2, sw + sh.w2t,
+                            (const uint32_t*)h->mask1, h->s_w1, h->s_b1, N, h->ln_fpw, h->obs_keys))
+          return r;
+      } else if (int r = h->rows_on ? bwd(h->obs_rows) : bwd(ObsDirect{})) return r;
     } else {  // LayerNorm backward + conv3 dgrad per frame
       if (int r = klaunch(h, K_LNC3_BWD, "ln_bwd_conv3_dgrad", lnc3_bwd<T>, dim3(h->n_ln_wg),
                           dim3(lnc3_threads<T>()), st, (const float*)h->dy, (const T*)h->act3,

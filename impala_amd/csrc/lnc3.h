@@ -473,6 +473,8 @@ __global__ __launch_bounds__(lnc3_threads<T>()) void lnc3_conv12_bwd(
   static_assert(lnc3_threads<T>() == 256 * C12_GROUPS, "one block shape for both bodies");
   constexpr int B1 = Lnc3Lds<T>::BYTES, B2 = C12BLds<T>::BYTES;
   __shared__ __attribute__((aligned(16))) char lds[B1 > B2 ? B1 : B2];
+  // (ObsKeys: the workgroup's keys load here, a whole LayerNorm body ahead of their first use)
+  const auto& wm = obs_wg(rm, (int)blockIdx.x * fpw, N);
   if constexpr (sizeof(T) == 4) {
     // fp32: each 4-wave group runs its role of both bodies as one code path, so group A's W2
     // fragments (loaded during the LayerNorm frames) and group B's W3 fragments / weight-gradient
@@ -490,15 +492,15 @@ __global__ __launch_bounds__(lnc3_threads<T>()) void lnc3_conv12_bwd(
       lnc3_body_f32r<0>(dy, a3, stats, gam, w3f, a2, d3, d2, ln_slab, N, fpw, wg, lds,
                         [&](int k) { c12_load_w2(w2f, wb, cls, lane, k, k + 1); });
       __syncthreads();  // this workgroup's dact2 stores are visible to all its waves; LDS is reused
-      conv12_bwd_body_f32<0, O>(x, w2f, d2, mask1, c1_slab, c1_slab_bias, N, fpw, wg, lds, wb, false, rm);
+      conv12_bwd_body_f32<0>(x, w2f, d2, mask1, c1_slab, c1_slab_bias, N, fpw, wg, lds, wb, false, wm);
     } else {
       lnc3_body_f32r<1>(dy, a3, stats, gam, w3f, a2, d3, d2, ln_slab, N, fpw, wg, lds, [](int) {});
       __syncthreads();
-      conv12_bwd_body_f32<1, O>(x, w2f, d2, mask1, c1_slab, c1_slab_bias, N, fpw, wg, lds, wb, false, rm);
+      conv12_bwd_body_f32<1>(x, w2f, d2, mask1, c1_slab, c1_slab_bias, N, fpw, wg, lds, wb, false, wm);
     }
   } else {
     lnc3_body<T>(dy, act3, stats, gam, w3, w3t, act2, dact3, dact2, ln_slab, N, fpw, (int)blockIdx.x, lds);
     __syncthreads();  // this workgroup's dact2 stores are visible to all its waves; LDS is reused
-    conv12_bwd_body<T, O>(x, w2, w2t, dact2, mask1, c1_slab, c1_slab_bias, N, fpw, (int)blockIdx.x, lds, rm);
+    conv12_bwd_body<T>(x, w2, w2t, dact2, mask1, c1_slab, c1_slab_bias, N, fpw, (int)blockIdx.x, lds, wm);
   }
 }

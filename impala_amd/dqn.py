@@ -6,8 +6,10 @@ builds them), ``NativePrioritizedReplay`` (the same ring on the library's ``dqn_
 
 The network is IMPALA's trunk with a 512-wide projection and a dueling head; the step is one
 ``dqn_train_step`` call (include/dqn_hip.h) or, over a ``NativePrioritizedReplay``, one
-``dqn_train_step_replay`` call: sample, step and priority update.  The compute path is the HIP
-library only.
+``dqn_train_step_replay`` call: sample, step and priority update
+(``dqn_train_step_replay_rows`` with ``in_place=True``: the step reads the sampled ring rows where
+they lie).  ``ApexActor`` (agents/dqn/learning.py:17-65) feeds that replay one rollout at a time.
+The compute path is the HIP library only.
 """
 from __future__ import annotations
 
@@ -21,7 +23,7 @@ import torch
 
 from impala_amd import _lib
 from impala_amd._lib import check, lib
-from impala_amd.core import Builder, Learner
+from impala_amd.core import Actor, Builder, Learner
 from impala_amd.flat import FlatModule, spec_count, trunk_init_flat
 from impala_amd.learner import ImpalaAdam
 from impala_amd.model import OBS_SHAPE
@@ -30,6 +32,8 @@ HIDDEN = 512
 _ERR = "dqn_last_error"  # the DQN ABI reports through its own accessor (_lib.check)
 # calls of dqn_train_step_replay made through DqnEngine.train_step_replay (this process)
 REPLAY_STEP_CALLS = 0
+# calls of dqn_train_step_replay_rows made through DqnEngine.train_step_replay_rows (this process)
+REPLAY_ROWS_STEP_CALLS = 0
 
 
 def net_specs(num_actions: int = 15) -> List[Tuple[str, Tuple[int, ...]]]:
@@ -189,6 +193,22 @@ class DqnEngine(_lib.NativeHandle):
         check(lib().dqn_train_step_replay(self._h, replay._h, int(seed), int(counter),
                                           _lib.ptr(keys), _lib.ptr(prio),
                                           _lib.stream_ptr(None)), "dqn_train_step_replay", _ERR)
+        return keys, prio
+
+    def train_step_replay_rows(self, replay: "NativePrioritizedReplay", seed: int, counter: int):
+        """``train_step_replay`` without the batch copy: one ``dqn_train_step_replay_rows`` call,
+        the step reading the sampled rows of ``replay``'s ring in place.  Same outputs, bit for
+        bit.  Until the current stream reaches the call's end, do not write ``replay``'s rows
+        from another stream.  Raises ``_lib.Unsupported`` off the default kernel path."""
+        global REPLAY_ROWS_STEP_CALLS
+        self._fresh()
+        keys = torch.empty(self.N, dtype=torch.int64, device=self.device)
+        prio = torch.empty(self.N, device=self.device)
+        REPLAY_ROWS_STEP_CALLS += 1
+        check(lib().dqn_train_step_replay_rows(self._h, replay._h, int(seed), int(counter),
+                                               _lib.ptr(keys), _lib.ptr(prio),
+                                               _lib.stream_ptr(None)),
+              "dqn_train_step_replay_rows", _ERR)
         return keys, prio
 
 
@@ -405,11 +425,14 @@ class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
     ``sample`` draws by the header's contract from ``(seed, counter)``; the counter advances once
     per call (``reset(seed)`` rewinds it), so a seeded replay repeats its draws.
     ``extend_rollout`` is the actor's ``_async_make_replay`` (agents/dqn/learning.py:56-65).
+    ``in_place=True`` asks ``ApexLearner`` to step on the sampled rows where they lie
+    (``dqn_train_step_replay_rows``) instead of on a gathered copy.
     """
     _destroy, _last_error = "dqn_replay_destroy", _ERR
 
     def __init__(self, capacity: int, priority_exponent: float = 0.6, device="cuda",
-                 seed: Optional[int] = None, obs_shape=OBS_SHAPE):
+                 seed: Optional[int] = None, obs_shape=OBS_SHAPE, in_place: bool = False):
+        self.in_place = bool(in_place)
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("NativePrioritizedReplay lives on the HIP path only (cuda device)")
@@ -615,8 +638,15 @@ class ApexLearner(Learner):
         e = self._engine
         m = torch.empty(_lib.DQN_NUM_METRICS, dtype=torch.float32, device=e.device)
         e.bind_metrics(m)
-        seed, counter = self._replay_buffer.next_draw()
-        self.last_keys, self.last_priorities = e.train_step_replay(self._replay_buffer, seed, counter)
+        rb = self._replay_buffer
+        seed, counter = rb.next_draw()
+        out = None
+        if rb.in_place:
+            try:
+                out = e.train_step_replay_rows(rb, seed, counter)
+            except _lib.Unsupported:  # refused before any launch: the gather path, from now on
+                rb.in_place = False
+        self.last_keys, self.last_priorities = out or e.train_step_replay(rb, seed, counter)
         v = m.unbind(0)
         out = {name: v[i] for name, i in _lib.DQN_METRIC_SLOTS}
         out["debug/priority_update_time"] = 0
@@ -641,6 +671,82 @@ class ApexLearner(Learner):
         out = {name: v[i] for name, i in _lib.DQN_METRIC_SLOTS}
         out["debug/priority_update_time"] = priority_update_time
         return out
+
+
+class ApexActor(Actor):
+    """``ApexActor`` (agents/dqn/learning.py:17-65) for in-process actors: it collects
+    ``(obs, action, reward, done, q_pi, q_star)`` per step and hands every ``rollout_length`` steps
+    to the replay's ``extend_rollout``, whose kernel computes the n-step targets and the initial
+    priorities of the rollout's ``rollout_length - 1`` transitions.  Each rollout stands alone."""
+
+    def __init__(self, model, replay_buffer=None, eps: float = 0.4, n_step: int = 3,
+                 rollout_length: int = 100, gamma: float = 0.99):
+        self._model = model
+        self._replay_buffer = replay_buffer
+        self._eps = torch.tensor((eps,), dtype=torch.float32)
+        self._n_step = n_step
+        self._rollout_length = rollout_length
+        self._gamma = gamma
+        self._trajectory = []
+        self._last_transition = None
+
+    def act(self, timestep):  # learning.py:31-33
+        obs = timestep.observation if hasattr(timestep, "observation") else timestep[0]
+        action, q, v = self._model.act(obs, self._eps)
+        return action, {"q": q, "v": v}
+
+    async def async_act(self, timestep):
+        return self.act(timestep)
+
+    def observe_init(self, timestep) -> None:
+        if self._replay_buffer is None:
+            return
+        self._last_transition = timestep
+
+    async def async_observe_init(self, timestep) -> None:
+        self.observe_init(timestep)
+
+    def observe(self, action, next_timestep) -> None:  # learning.py:40-48
+        if self._replay_buffer is None:
+            return
+        lt = self._last_transition
+        obs = lt.observation if hasattr(lt, "observation") else lt[0]
+        act, info = action
+        reward, done = next_timestep[1], next_timestep[2]
+        f32 = lambda x: torch.as_tensor(x, dtype=torch.float32).reshape(())
+        self._trajectory.append((torch.as_tensor(obs).reshape(OBS_SHAPE),
+                                 torch.as_tensor(act).reshape(()), f32(reward),
+                                 torch.as_tensor(done).reshape(()), f32(info["q"]), f32(info["v"])))
+        self._last_transition = next_timestep
+        if len(self._trajectory) == self._rollout_length:
+            self.update()
+
+    async def async_observe(self, action, next_timestep) -> None:
+        self.observe(action, next_timestep)
+
+    def update(self) -> None:  # learning.py:50-65
+        """The stacked steps into the replay (a rollout of L steps makes L - 1 transitions, so
+        fewer than 2 steps make none and stay pending)."""
+        if self._replay_buffer is None or len(self._trajectory) < 2:
+            return
+        s, a, r, d, q_pi, q_star = (torch.stack(x) for x in zip(*self._trajectory))
+        self._trajectory = []
+        self._replay_buffer.extend_rollout(s, a.to(torch.int64), r, d, q_pi, q_star, self._n_step,
+                                           self._gamma)
+
+    async def async_update(self) -> None:
+        self.update()
+
+
+class ApexActorFactory:
+    """Actor index -> an ``ApexActor`` exploring at ``eps_func(index)`` (the reference's
+    ApexDQNAgentFactory)."""
+
+    def __init__(self, model, eps_func, rb=None, **kwargs):
+        self._model, self._eps_func, self._rb, self._kwargs = model, eps_func, rb, kwargs
+
+    def __call__(self, index: int) -> Actor:
+        return ApexActor(self._model, self._rb, eps=self._eps_func(index), **self._kwargs)
 
 
 class ConstantEpsFunc:
@@ -669,21 +775,30 @@ class FlexibleEpsFunc:
 class ApexDQNBuilder(Builder):
     """agents/dqn/builder.py:76-120 on the HIP learner."""
 
-    def make_replay(self, native: bool = False):  # builder.py:82-89
-        """``native=True``: the ring on the library's ``dqn_replay`` (NativePrioritizedReplay)."""
-        cls = NativePrioritizedReplay if native else PrioritizedReplay
-        return cls(self.cfg.agent.replay_buffer_size,
-                   priority_exponent=float(self.cfg.agent.priority_exponent),
-                   device=self.cfg.distributed.train_device,
-                   seed=self.cfg.training.seed)
+    def make_replay(self, native: bool = False, in_place: bool = False):  # builder.py:82-89
+        """``native=True``: the ring on the library's ``dqn_replay`` (NativePrioritizedReplay);
+        ``in_place=True`` (native only): the learner steps on the sampled rows where they lie."""
+        if in_place and not native:
+            raise ValueError("in_place needs the native replay (native=True)")
+        kw = dict(priority_exponent=float(self.cfg.agent.priority_exponent),
+                  device=self.cfg.distributed.train_device, seed=self.cfg.training.seed)
+        if native:
+            return NativePrioritizedReplay(self.cfg.agent.replay_buffer_size, in_place=in_place, **kw)
+        return PrioritizedReplay(self.cfg.agent.replay_buffer_size, **kw)
 
     def make_actor(self, model, rb=None, deterministic: bool = False):  # builder.py:91-97
-        # ApexActor's n-step targets and initial priorities are
-        # NativePrioritizedReplay.extend_rollout (dqn_replay_extend_rollout); the env loop around
-        # them stays out of scope here (SURVEY.md §2 rows 12-14)
-        raise NotImplementedError(
-            "Ape-X actors are not part of the MI355X learner path: feed rollouts to "
-            "NativePrioritizedReplay.extend_rollout (model.act gives q_pi / q_star)")
+        if deterministic:
+            eps_func = ConstantEpsFunc(self.cfg.agent.eval_eps)
+        else:
+            eps_func = FlexibleEpsFunc(self.cfg.agent.train_eps, self.cfg.training.num_rollouts)
+        if rb is not None and not hasattr(rb, "extend_rollout"):
+            # ApexActor's n-step targets and initial priorities are the native replay's ingest
+            # (dqn_replay_extend_rollout); the plain PrioritizedReplay has no such entry
+            raise NotImplementedError(
+                "ApexActor hands whole rollouts to the replay's extend_rollout, the n-step ingest "
+                "of NativePrioritizedReplay (make_replay(native=True)); this replay has none")
+        return ApexActorFactory(model, eps_func, rb, n_step=int(self.cfg.agent.n_step),
+                                rollout_length=int(self.cfg.agent.rollout_length))
 
     def learner_kwargs(self) -> dict:
         """make_learner's constructor arguments (builder.py:99-110): Adam from

@@ -18,6 +18,7 @@
  *                    n-step targets and initial priorities of one rollout, appended to the ring
  *   dqn_train_step_replay      agents/dqn/learning.py:139-147,159-182  sample, step and priority
  *                    update as one call
+ *   dqn_train_step_replay_rows  the same, the step reading the sampled ring rows in place
  *
  * Network: AtariBody -> LayerNorm(1024) -> Linear(1024, 512) -> GELU -> advantage head
  * Linear(512, A) and value head Linear(512, 1); q = v + adv - mean_A(adv).  The trunk up to the
@@ -210,6 +211,21 @@ int dqn_replay_update(dqn_replay* r, const int64_t* keys, const float* prioritie
  * there directly. */
 int dqn_train_step_replay(dqn_learner* h, dqn_replay* r, uint64_t seed, uint64_t counter,
                           int64_t* keys_out, float* priorities_out, void* stream);
+/* dqn_train_step_replay without the gather: the same draws, then the step reads the sampled ring
+ * rows in place -- the bound obs / actions / targets are its batch, transition f is ring row
+ * keys[f] -- then dqn_replay_update.  Same arguments, checks and order of work, the same bits in
+ * every output; no obs gather buffer is allocated (the first call allocates batch_size keys,
+ * probabilities and priorities of scratch).  Everything is enqueued on `stream`, nothing waits on
+ * the host.
+ * Ownership: between this call and `stream` reaching its end the caller must not write the ring
+ * rows (obs, actions, targets): the step's kernels read them after the call returns.  An extend
+ * enqueued later on the same stream is ordered by the stream.
+ * Only the default kernel path reads through the keys: a handle created under a switch that
+ * leaves it (IMPALA_LC12=0, frames-per-workgroup overrides that differ or exceed 64) or a ring of
+ * more than 2^31 - 1 rows gets IMPALA_E_UNSUPPORTED before any launch; dqn_train_step_replay
+ * serves those. */
+int dqn_train_step_replay_rows(dqn_learner* h, dqn_replay* r, uint64_t seed, uint64_t counter,
+                               int64_t* keys_out, float* priorities_out, void* stream);
 /* Test / inspection entry: copies weights [capacity] f64 and (optional) the running maximum f32
  * [1] into caller-owned device arrays. */
 int dqn_replay_weights(dqn_replay* r, double* weights_out, float* max_priority_out, void* stream);

@@ -7,11 +7,15 @@ after --warmup, for
   (a) PrioritizedReplay.sample + DqnEngine.train_step + update  (the torch replay path)
   (b) dqn_train_step_replay                                      (one call)
   (c) dqn_train_step alone on a fixed batch
-in --runs alternating runs a, b, c, a, b, c, ...  Prints one JSON line per configuration with each
-run's figures, the means, the replay's cost (b) - (c) beside (a) - (c), and whether (a) - (b)
-exceeds three times the larger run-to-run spread (the method of README's wgloop note).
+  (d) dqn_train_step_replay_rows                                 (one call, the ring read in place)
+in --runs alternating runs a, b, c, d, a, b, c, d, ...  Prints one JSON line per configuration with
+each run's figures, the means, the replay's cost (b) - (c) and (d) - (c) beside (a) - (c), and
+whether (a) - (b) and (b) - (d) exceed three times the larger run-to-run spread of the two (the
+method of README's wgloop note).  (b) and (d) share the native ring.  Per ring it also times one
+extend_rollout of --rollout steps (device inputs, events around --steps calls).
 
-usage: python tools/dqn_replay_time.py [--steps 200] [--warmup 20] [--runs 4] [--out FILE]"""
+usage: python tools/dqn_replay_time.py [--steps 200] [--warmup 20] [--runs 4] [--paths abcd]
+                                       [--out FILE]"""
 import argparse
 import json
 import os
@@ -65,6 +69,8 @@ def main():
     ap.add_argument("--runs", type=int, default=4)
     ap.add_argument("--caps", type=int, nargs="+", default=[100_000, 1_000_000])
     ap.add_argument("--dtypes", nargs="+", default=["fp32", "bf16"])
+    ap.add_argument("--paths", default="abcd", help="which of the paths a, b, c, d to run")
+    ap.add_argument("--rollout", type=int, default=100, help="L of the timed extend_rollout (0: skip)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -76,14 +82,26 @@ def main():
         # the plain ring's rows, so both replays hold the same transitions
         native.extend((plain.s, plain.a, plain.target), priorities=plain.priorities)
         torch.cuda.synchronize()
+        if args.rollout >= 2:
+            L = args.rollout
+            g = torch.Generator(device=dev).manual_seed(3)
+            ro = (torch.randint(0, 256, (L, 3, 64, 64), dtype=torch.uint8, device=dev, generator=g),
+                  torch.randint(0, A, (L,), device=dev, generator=g), torch.randn(L, device=dev, generator=g),
+                  torch.zeros(L, dtype=torch.uint8, device=dev), torch.randn(L, device=dev, generator=g),
+                  torch.randn(L, device=dev, generator=g))
+            wall, ev = timed(lambda: native.extend_rollout(*ro, n_step=3, gamma=0.99), args.steps, args.warmup)
+            line = json.dumps({"capacity": cap, "extend_rollout_L": L, "calls": args.steps,
+                               "wall_ms": round(wall, 5), "event_ms": round(ev, 5)})
+            print(line, flush=True)
+            lines.append(line)
         for dtype in args.dtypes:
             engines = []
-            for _ in range(3):
+            for _ in range(4):
                 m = AtariDQNModel((3, 64, 64), A, device=dev, dtype=dtype, seed=0)
                 e = DqnEngine(m, batch_size=N)
                 m._train_engine = e
                 engines.append(e)
-            ea, eb, ec = engines
+            ea, eb, ec, ed = engines
             keys, fixed, probs = plain.sample(N)
             fixed = tuple(x.clone() for x in fixed)
             probs = probs.clone()
@@ -100,23 +118,39 @@ def main():
             def step_c():
                 ec.train_step(*fixed, probs)
 
-            runs = {"a": [], "b": [], "c": []}
+            def step_d():
+                counter[0] += 1
+                ed.train_step_replay_rows(native, 1, counter[0])
+
+            steps = [(k, f) for k, f in (("a", step_a), ("b", step_b), ("c", step_c), ("d", step_d))
+                     if k in args.paths]
+            runs = {k: [] for k, _ in steps}
             for _ in range(args.runs):
-                for name, fn in (("a", step_a), ("b", step_b), ("c", step_c)):
+                for name, fn in steps:
                     runs[name].append(timed(fn, args.steps, args.warmup))
             out = {"capacity": cap, "dtype": dtype, "N": N, "steps": args.steps, "warmup": args.warmup}
             for kind, col in (("wall_ms", 0), ("event_ms", 1)):
                 v = {k: [round(r[col], 5) for r in rs] for k, rs in runs.items()}
                 mean = {k: float(np.mean(x)) for k, x in v.items()}
-                spread = max(max(x) - min(x) for x in (v["a"], v["b"]))
-                out[kind] = {
-                    "runs": v, "mean": {k: round(x, 5) for k, x in mean.items()},
-                    "replay_cost_b_minus_c": round(mean["b"] - mean["c"], 5),
-                    "torch_replay_cost_a_minus_c": round(mean["a"] - mean["c"], 5),
-                    "a_minus_b": round(mean["a"] - mean["b"], 5),
-                    "larger_spread_of_a_b": round(spread, 5),
-                    "b_below_a_by_more_than_3_spreads": bool(mean["a"] - mean["b"] > 3 * spread),
-                }
+                sp = {k: max(x) - min(x) for k, x in v.items()}
+                o = {"runs": v, "mean": {k: round(x, 5) for k, x in mean.items()},
+                     "spread": {k: round(x, 5) for k, x in sp.items()}}
+
+                def gap(hi, lo):  # is `lo` below `hi` by more than three times the larger spread
+                    if hi in mean and lo in mean:
+                        s3 = max(sp[hi], sp[lo])
+                        o[f"{hi}_minus_{lo}"] = round(mean[hi] - mean[lo], 5)
+                        o[f"larger_spread_of_{hi}_{lo}"] = round(s3, 5)
+                        o[f"{lo}_below_{hi}_by_more_than_3_spreads"] = bool(mean[hi] - mean[lo] > 3 * s3)
+                        o[f"{hi}_below_{lo}_by_more_than_3_spreads"] = bool(mean[lo] - mean[hi] > 3 * s3)
+
+                for k, name in (("b", "replay_cost_b_minus_c"), ("d", "in_place_cost_d_minus_c"),
+                                ("a", "torch_replay_cost_a_minus_c")):
+                    if k in mean and "c" in mean:
+                        o[name] = round(mean[k] - mean["c"], 5)
+                gap("a", "b")
+                gap("b", "d")
+                out[kind] = o
             line = json.dumps(out)
             print(line, flush=True)
             lines.append(line)
