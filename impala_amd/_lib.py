@@ -65,7 +65,7 @@ EXPORTS = (
     "impala_slot_batch",
     "impala_slot_release", "impala_act", "impala_set_debug_vtrace",
     "impala_timer_read_kernel", "impala_dp_unique_id", "impala_dp_init", "impala_dp_train_step",
-    "impala_dp_nranks", "impala_step_clock", "impala_step_clock_end",
+    "impala_dp_nranks", "impala_step_clock", "impala_step_clock_end", "impala_debug_read",
 )
 # every symbol declared in include/sac_hip.h
 SAC_EXPORTS = (
@@ -186,6 +186,7 @@ def _declare(lib):
     lib.impala_refresh_weights.argtypes = [_P, _P]
     lib.impala_set_step.argtypes = [_P, C.c_int64, _P]
     lib.impala_set_debug_vtrace.argtypes = [_P, _P]
+    lib.impala_debug_read.argtypes = [_P, C.c_int, _P, C.c_size_t, _P]
     lib.impala_set_metrics.argtypes = [_P, _P]
     lib.impala_set_metrics_host.argtypes = [_P, _P]
     lib.impala_train_step_rows.argtypes = [_P, C.POINTER(ImpalaBatch), _P, C.c_int, C.c_int64, _P]

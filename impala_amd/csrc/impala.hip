@@ -904,6 +904,41 @@ int impala_set_debug_vtrace(impala_learner* h, float* out) {
   return 0;
 }
 
+int impala_debug_read(impala_learner* h, int which, void* dst, size_t bytes, void* stream) {
+  using namespace net;
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  if (!dst) return fail(IMPALA_E_INVALID, "null destination");
+  const size_t N = (size_t)h->N, es = h->bf16 ? 2 : 4, hid = (size_t)h->hid;
+  const void* src = nullptr;
+  size_t size = 0;
+  switch (which) {  // the sizes of the workspace carve-up in create_learner
+    case IMPALA_DBG_ACT1: src = h->act1; size = N * P1 * OC1 * es; break;
+    case IMPALA_DBG_ACT2: src = h->act2; size = N * P2 * OC2 * es; break;
+    case IMPALA_DBG_ACT3: src = h->act3; size = N * FLAT * es; break;
+    case IMPALA_DBG_Y: src = h->y; size = N * FLAT * es; break;  // (dense: the row pitch is dropped)
+    case IMPALA_DBG_H: src = h->h; size = N * hid * es; break;
+    case IMPALA_DBG_DZ: src = h->dz; size = N * hid * es; break;
+    case IMPALA_DBG_DACT3: src = h->dact3; size = N * FLAT * es; break;
+    case IMPALA_DBG_DACT2: src = h->dact2; size = N * P2 * OC2 * es; break;
+    case IMPALA_DBG_MASK1: src = h->mask1; size = N * P1 * 4; break;
+    case IMPALA_DBG_LNSTAT: src = h->lnstat; size = N * 2 * 4; break;
+    case IMPALA_DBG_ZG: src = h->zg; size = N * hid * 4; break;
+    case IMPALA_DBG_HEADS: src = h->heads; size = N * HEADS * 4; break;
+    case IMPALA_DBG_DY: src = h->dy; size = N * FLAT * 4; break;
+    default: return fail(IMPALA_E_INVALID, "unknown debug tensor");
+  }
+  if (bytes == 0 || bytes > size) return fail(IMPALA_E_INVALID, "bytes must be in (0, the tensor's size]");
+  CK(hipSetDevice(h->device));
+  if (which == IMPALA_DBG_Y && YLD != FLAT) {  // rows of FLAT elements at a pitch of YLD
+    const size_t row = FLAT * es;
+    if (bytes % row) return fail(IMPALA_E_INVALID, "y is read in whole rows");
+    CK(hipMemcpy2DAsync(dst, row, src, YLD * es, row, bytes / row, hipMemcpyDefault, (hipStream_t)stream));
+    return 0;
+  }
+  CK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, (hipStream_t)stream));
+  return 0;
+}
+
 int impala_refresh_weights(impala_learner* h, void* stream) {
   if (int r = check_bound(h, false)) return r;
   CK(hipSetDevice(h->device));

@@ -142,6 +142,44 @@ class Engine(_lib.NativeHandle):
                 "q": buf[2 * BL:3 * BL].view(B, L), "rho": buf[3 * BL:3 * BL + B * T].view(B, T),
                 "v": buf[3 * BL + B * T:].view(B, T)}
 
+    # name -> (IMPALA_DBG_* id, element kind, shape of one frame); kind "T" is the compute type
+    DEBUG_TENSORS = {
+        "act1": (0, "T", (15, 15, 32)), "act2": (1, "T", (6, 6, 64)), "act3": (2, "T", (1024,)),
+        "y": (3, "T", (1024,)), "h": (4, "T", (256,)), "dz": (5, "T", (256,)),
+        "dact3": (6, "T", (1024,)), "dact2": (7, "T", (6, 6, 64)), "mask1": (8, "u32", (225,)),
+        "lnstat": (9, "f32", (2,)), "zg": (10, "f32", (256,)), "heads": (11, "f32", (16,)),
+        "dy": (12, "f32", (1024,)),
+    }
+
+    def debug_tensor(self, name: str, frames: Optional[int] = None, stream=None):
+        """Read-only export of a workspace tensor as the last forward / step left it
+        (impala_debug_read; a host sync): a numpy array [frames, ...] in the layout of DESIGN §3
+        -- act1 [n,15,15,32], act2 / dact2 [n,6,6,64] channels-last; act3 / y / dact3 / dy
+        [n,1024] with feature index p*64+c (y without its row pitch); h / dz / zg [n,256];
+        mask1 uint32 [n,225] (bit c = channel c of act1 > 0); lnstat [n,2] (mean, rstd); heads
+        [n,16] (logits 0..A-1, the value at 15).  Tensors of the compute type come back as
+        float32 (exact for bf16).  ``frames``: the leading frames to read (default all B*T)."""
+        if name not in self.DEBUG_TENSORS:
+            raise ValueError(f"unknown debug tensor {name!r}: one of {sorted(self.DEBUG_TENSORS)}")
+        which, kind, shape = self.DEBUG_TENSORS[name]
+        n = self.frames if frames is None else int(frames)
+        if not 1 <= n <= self.frames:
+            raise ValueError(f"frames must be in [1, {self.frames}]")
+        bf16 = DTYPES[self.dtype] == _lib.IMPALA_DTYPE_BF16
+        dt = {"T": torch.bfloat16 if bf16 else torch.float32, "f32": torch.float32,
+              "u32": torch.int32}[kind]
+        buf = torch.empty((n,) + shape, dtype=dt, device=self.device)
+        check(_lib.lib().impala_debug_read(self._h, which, ptr(buf), buf.numel() * buf.element_size(),
+                                           stream_ptr(stream)), "impala_debug_read")
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        else:
+            stream.synchronize()
+        if kind == "u32":
+            import numpy as np
+            return buf.cpu().numpy().view(np.uint32)
+        return buf.float().cpu().numpy()
+
     # ------------------------------------------------------------------ compute
     def forward(self, obs: torch.Tensor, stream=None):
         """obs u8 [N,3,64,64] (any N; chunked by the handle capacity) -> logits [N,A], v [N,1]."""

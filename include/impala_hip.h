@@ -167,6 +167,33 @@ int impala_set_step(impala_learner* h, int64_t step, void* stream);
  * (3*B*(T-1) + 2*B*T floats, device memory).  NULL disables it. */
 int impala_set_debug_vtrace(impala_learner* h, float* out);
 
+/* Read-only debug export of one workspace tensor of the handle, as the last forward / step left
+ * it: an asynchronous device-to-device (or device-to-host) copy of the first `bytes` bytes of
+ * tensor `which` to `dst`, enqueued on `stream` after the work already there.  No kernel runs
+ * and nothing of the handle changes.  E = 4 bytes on fp32 handles, 2 (bf16) otherwise; N = B*T:
+ *   ACT1  E [N][15][15][32]   ACT2, DACT2  E [N][6][6][64]      (channels-last)
+ *   ACT3, Y, DACT3  E [N][1024], feature p*64 + c                H, DZ  E [N][256]
+ *   MASK1 u32 [N][225] (bit c = act1 channel c > 0)             LNSTAT f32 [N][2] (mean, rstd)
+ *   ZG f32 [N][256] gelu'(FC pre-activation)    HEADS f32 [N][16] (logits 0..A-1, value at 15)
+ *   DY f32 [N][1024]
+ * (the projection width of a handle made by dqn_create is 512 instead of 256).  `bytes` must be
+ * in (0, the tensor's size]. */
+#define IMPALA_DBG_ACT1 0
+#define IMPALA_DBG_ACT2 1
+#define IMPALA_DBG_ACT3 2
+#define IMPALA_DBG_Y 3
+#define IMPALA_DBG_H 4
+#define IMPALA_DBG_DZ 5
+#define IMPALA_DBG_DACT3 6
+#define IMPALA_DBG_DACT2 7
+#define IMPALA_DBG_MASK1 8
+#define IMPALA_DBG_LNSTAT 9
+#define IMPALA_DBG_ZG 10
+#define IMPALA_DBG_HEADS 11
+#define IMPALA_DBG_DY 12
+#define IMPALA_DBG_COUNT 13
+int impala_debug_read(impala_learner* h, int which, void* dst, size_t bytes, void* stream);
+
 /* Policy/value forward of n frames (n <= B*T): logits [n][A], values [n]. */
 int impala_forward(impala_learner* h, const uint8_t* obs, int n, float* logits, float* values,
                    void* stream);

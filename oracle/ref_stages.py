@@ -1,0 +1,339 @@
+"""ORACLE -- test infrastructure only.  References of the learner step's stages, one function
+each, for teacher-forced checks of the bf16 (and fp32) kernels.
+
+Every function takes the tensors its kernel stage READS (in the layouts ``Engine.debug_tensor``
+exports, DESIGN §3: activations channels-last, the 1024 features in p*64+c order) and returns
+what the stage WRITES, before any rounding to bf16, evaluated in ``dtype`` (float64 for the
+reference, float32 for the CPU stand-in of the kernels).  What each stage reads, from the
+kernels:
+
+  conv1      relu(conv(w1, image bytes) * (1/255) + b1): the bytes are exact in bf16, the scale
+             and the bias are applied to the fp32 accumulator (conv1.h c1_epi).  mask1 bit c =
+             channel c > 0.
+  conv2      relu(conv(w2, act1) + b2) on the rounded act1.
+  conv3+LN   v = relu(conv(w3, act2) + b3) unrounded in fp32; mean / rstd and y = LN(v) come
+             from that unrounded v, act3 is v rounded (lnorm.h ln_frame_epilogue).
+  fc         z = wfc y + bfc; zg = gelu'(z) stays fp32, h = gelu(z) is rounded; z is not kept.
+  heads      heads = wh h + bh, fp32 [N][16].
+  head bwd   dH (d loss / d heads, from the fp32 heads) is rounded in LDS (head.h phase 2c);
+             dz = zg * (q(dH) wh); d wh = q(dH)^T h; d bh = sum q(dH).
+  fc bwd     dy = dz wfc (fp32); d wfc = dz^T y; d bfc = sum dz -- the rounded dz (the weight-
+             gradient GEMM sums the rows it reads, gemm.h gemm_wg_body).
+  LN bwd     xh = (act3 - mean) * rstd from the ROUNDED act3 and the fp32 stats; d gamma = sum
+             dy xh, d beta = sum dy; dact3 = [act3 > 0] rstd (dy gamma - S1 - xh S2) (lnc3.h).
+  conv3 bwd  dact2 = [act2 > 0] col2im(q(dact3) w3); d w3 from (q(dact3), act2); d b3 = sum
+             q(dact3).
+  conv2 bwd  d w2 from (q(dact2), act1); d b2 = sum q(dact2); dY1 = [mask1] col2im(q(dact2) w2),
+             which never reaches HBM.
+  conv1 bwd  d b1 = sum of the UNROUNDED fp32 dY1 (conv1.h: bsum adds v before the bf16 store);
+             d w1 = q(dY1)^T image bytes * (1/255).
+
+In the bf16 mode every weight is RNE_bf16(master fp32) (kernels.h pack_params, ``(T)p``); biases,
+LayerNorm gamma / beta and the statistics stay fp32.  ``quant=False`` switches every rounding off
+(the fp32 mode, and the chain identity against ref_cpu).
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from oracle import ref_cpu
+
+BLOCKS = ("w1", "b1", "w2", "b2", "w3", "b3", "lng", "lnb", "wfc", "bfc", "wa", "ba", "wc", "bc")
+T_TENSORS = ("act1", "act2", "act3", "y", "h", "dz", "dact3", "dact2")  # compute type
+F32_TENSORS = ("lnstat", "zg", "heads", "dy")
+FORWARD_TENSORS = ("act1", "act2", "act3", "lnstat", "y", "zg", "h", "heads")
+LN_EPS = 1e-5
+VCOL = 15
+# export feature j = p*64 + c  ->  canonical (NCHW flatten) feature c*16 + p
+_PERM = torch.tensor([(j & 63) * 16 + (j >> 6) for j in range(1024)])
+
+
+def rne_bf16(x: torch.Tensor) -> torch.Tensor:
+    """Round to the nearest bf16 (ties to even), returned in x's dtype.  float64 is rounded
+    directly (not through float32: a double rounding could land on the other side of a tie)."""
+    if x.dtype == torch.float32:
+        return x.bfloat16().float()
+    _, e = torch.frexp(x)
+    ulp = torch.ldexp(torch.ones_like(x), (e - 1).clamp_min(-126) - 7)
+    return torch.round(x / ulp) * ulp
+
+
+def ulp_bf16(r: np.ndarray) -> np.ndarray:
+    """2^(floor(log2 |r|) - 7): the spacing of bf16 at r (0 at r = 0)."""
+    r = np.asarray(r, np.float64)
+    _, e = np.frexp(r)
+    return np.where(r == 0, 0.0, np.ldexp(1.0, np.maximum(e - 1, -126) - 7))
+
+
+def block_shapes(A: int):
+    return [(n, (A,) + s[1:] if k.startswith("model.actor") else s)
+            for n, (k, s) in zip(BLOCKS, ref_cpu.PARAM_SPECS)]
+
+
+def split_flat(flat, A: int) -> Dict[str, np.ndarray]:
+    """A flat parameter / gradient vector -> its 14 canonical blocks."""
+    out, off = {}, 0
+    for n, s in block_shapes(A):
+        k = int(np.prod(s))
+        out[n] = np.asarray(flat[off:off + k]).reshape(s)
+        off += k
+    assert off == len(flat)
+    return out
+
+
+class Weights:
+    """The weights as the kernels see them: conv / FC / head weights rounded to bf16 when
+    ``quant``, the vectors fp32; the 1024-feature axes in the export order p*64+c; the heads as
+    one [16][256] matrix (rows 0..A-1 actor, row 15 critic)."""
+
+    def __init__(self, flat, A: int, quant: bool, dtype=torch.float64):
+        src = np.asarray(flat, np.float32 if quant else np.float64)  # (the master weights are fp32)
+        b = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dtype)
+             for k, v in split_flat(src, A).items()}
+        q = rne_bf16 if quant else (lambda t: t)
+        self.A = A
+        self.w1, self.w2, self.w3 = q(b["w1"]), q(b["w2"]), q(b["w3"])
+        self.b1, self.b2, self.b3 = b["b1"], b["b2"], b["b3"]
+        self.lng, self.lnb = b["lng"][_PERM], b["lnb"][_PERM]
+        self.wfc, self.bfc = q(b["wfc"])[:, _PERM], b["bfc"]
+        self.wh = torch.zeros(16, 256, dtype=dtype)
+        self.wh[:A], self.wh[VCOL] = q(b["wa"]), q(b["wc"])[0]
+        self.bh = torch.zeros(16, dtype=dtype)
+        self.bh[:A], self.bh[VCOL] = b["ba"], b["bc"][0]
+
+
+def _nchw(x, H, C):
+    return x.reshape(-1, H, H, C).permute(0, 3, 1, 2)
+
+
+def _nhwc(x):
+    return x.permute(0, 2, 3, 1).contiguous()
+
+
+# ------------------------------------------------------------------------------- forward
+def conv1_fwd(obs_u8, W: Weights):
+    """image bytes [N,3,64,64] -> act1 [N,15,15,32] (unrounded)."""
+    x = F.conv2d(obs_u8.to(W.w1.dtype), W.w1, stride=4) * (1.0 / 255.0) + W.b1.view(1, -1, 1, 1)
+    return _nhwc(x.clamp_min(0))
+
+
+def mask_bits(act1) -> np.ndarray:
+    """act1 [N,15,15,32] -> mask1 uint32 [N,225], bit c = channel c > 0."""
+    b = (np.asarray(act1) > 0).reshape(-1, 225, 32).astype(np.uint64)
+    return (b << np.arange(32, dtype=np.uint64)).sum(-1).astype(np.uint32)
+
+
+def conv2_fwd(act1, W: Weights):
+    """act1 [N,15,15,32] -> act2 [N,6,6,64] (unrounded)."""
+    x = F.conv2d(_nchw(act1, 15, 32), W.w2, stride=2) + W.b2.view(1, -1, 1, 1)
+    return _nhwc(x.clamp_min(0))
+
+
+def conv3_ln_fwd(act2, W: Weights):
+    """act2 [N,6,6,64] -> (act3 [N,1024] unrounded, lnstat [N,2] = (mean, rstd), y [N,1024])."""
+    x = F.conv2d(_nchw(act2, 6, 64), W.w3) + W.b3.view(1, -1, 1, 1)
+    v = _nhwc(x.clamp_min(0)).reshape(-1, 1024)
+    mean = v.mean(1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(((v - mean) ** 2).mean(1, keepdim=True) + LN_EPS)
+    y = (v - mean) * rstd * W.lng + W.lnb
+    return v, torch.cat([mean, rstd], 1), y
+
+
+def fc_fwd(y, W: Weights):
+    """y [N,1024] -> (zg = gelu'(z) [N,256], h = gelu(z) unrounded); exact (erf) GELU."""
+    z = y @ W.wfc.T + W.bfc
+    cdf = 0.5 * (1.0 + torch.erf(z / math.sqrt(2.0)))
+    return cdf + z * torch.exp(-0.5 * z * z) / math.sqrt(2.0 * math.pi), z * cdf
+
+
+def heads_fwd(h, W: Weights):
+    """h [N,256] -> heads [N,16] (logits 0..A-1, value at 15, the rest 0)."""
+    return h @ W.wh.T + W.bh
+
+
+# ------------------------------------------------------------------------------- loss head
+def impala_head(heads, batch, A: int, dtype=torch.float64, entropy_coeff: float = 0.01):
+    """The V-trace loss on the exported heads [B*T,16] -> (dH [N,16] unrounded, metrics dict
+    with loss / entropy / td / pg / kl / ratio and pg_abs = mean |log pi(a) adv|, the scale of
+    train/pg's normwise bound)."""
+    _, act, rew, disc, mu = batch
+    B, T = act.shape
+    hd = np.asarray(heads, np.float64).reshape(B, T, 16)
+    o = ref_cpu.loss_from_outputs(hd[..., :A], hd[..., VCOL], act, rew, disc, mu,
+                                  entropy_coeff=entropy_coeff, dtype=dtype)
+    dH = torch.zeros(B, T, 16, dtype=dtype)
+    dH[..., :A] = torch.from_numpy(o["dlogits"]).to(dtype)
+    dH[..., VCOL] = torch.from_numpy(o["dvalues"]).to(dtype)
+    lg = torch.from_numpy(hd[..., :A])
+    logpa = torch.log_softmax(lg, -1).gather(-1, torch.from_numpy(np.asarray(act))[..., None])[..., 0]
+    met = {k: o[k] for k in ("loss", "entropy", "td", "pg", "kl", "ratio")}
+    met["pg_abs"] = float((logpa[:, :-1] * torch.from_numpy(np.asarray(o["adv"], np.float64))).abs().mean())
+    return dH.reshape(B * T, 16), met
+
+
+def ppo_head(heads, batch, A: int, dtype=torch.float64, entropy_coeff: float = 0.01,
+             clip_coeff: float = 0.1):
+    """ref_cpu.ppo_loss (the code behind ppo_loss_from_outputs) on the exported heads [N,16], in
+    ``dtype`` -> (dH [N,16] unrounded, metrics dict)."""
+    _, act, tgt, mu = batch
+    hd = torch.from_numpy(np.asarray(heads, np.float64)).to(dtype)
+    lg = hd[:, :A].clone().requires_grad_(True)
+    v = hd[:, VCOL:VCOL + 1].clone().requires_grad_(True)
+    b = (None, torch.from_numpy(np.asarray(act, np.int64)),
+         torch.from_numpy(np.asarray(tgt)).to(dtype), torch.from_numpy(np.asarray(mu)).to(dtype))
+    loss, met = ref_cpu.ppo_loss(ref_cpu._Outputs(lg, v), b, entropy_cost=entropy_coeff,
+                                 clip_coeff=clip_coeff)
+    loss.backward()
+    dH = torch.zeros(hd.shape[0], 16, dtype=dtype)
+    dH[:, :A], dH[:, VCOL] = lg.grad, v.grad[:, 0]
+    return dH, {k.split("/")[1]: float(x) for k, x in met.items()}
+
+
+# ------------------------------------------------------------------------------- backward
+def head_bwd(qdH, zg, h, W: Weights):
+    """q(dH) [N,16], zg, h [N,256] -> (dz unrounded, d wh [16,256], d bh [16])."""
+    return zg * (qdH @ W.wh), qdH.T @ h, qdH.sum(0)
+
+
+def fc_bwd(dz, y, W: Weights):
+    """dz [N,256] (rounded), y [N,1024] -> (dy [N,1024], d wfc [256,1024] export order, d bfc)."""
+    return dz @ W.wfc, dz.T @ y, dz.sum(0)
+
+
+def ln_bwd(dy, act3, lnstat, W: Weights, xh=None):
+    """dy fp32, act3 (rounded), lnstat -> (dact3 unrounded, d gamma, d beta) (export order).
+    ``xh``: a normalised input to use instead of the kernel's (act3 - mean) * rstd."""
+    mean, rstd = lnstat[:, :1], lnstat[:, 1:]
+    if xh is None:
+        xh = (act3 - mean) * rstd
+    gd = dy * W.lng
+    s1, s2 = gd.mean(1, keepdim=True), (gd * xh).mean(1, keepdim=True)
+    dact3 = torch.where(act3 > 0, rstd * (gd - s1 - xh * s2), torch.zeros_like(dy))
+    return dact3, (dy * xh).sum(0), dy.sum(0)
+
+
+def conv3_bwd(dact3, act2, W: Weights, w3=None):
+    """dact3 [N,1024] (rounded), act2 -> (dact2 unrounded, d w3 [64,64,3,3], d b3).
+    ``w3``: a weight to use in the dgrad instead of W.w3."""
+    g = _nchw(dact3, 4, 64).contiguous()
+    x = _nchw(act2, 6, 64).contiguous()
+    dx = torch.nn.grad.conv2d_input(x.shape, W.w3 if w3 is None else w3, g)
+    dact2 = torch.where(x > 0, dx, torch.zeros_like(dx))
+    return _nhwc(dact2), torch.nn.grad.conv2d_weight(x, W.w3.shape, g), g.sum((0, 2, 3))
+
+
+def conv2_bwd(dact2, act1, W: Weights):
+    """dact2 [N,6,6,64] (rounded), act1 (its sign = mask1) -> (dY1 [N,15,15,32] unrounded,
+    d w2 [64,32,4,4], d b2)."""
+    g = _nchw(dact2, 6, 64).contiguous()
+    x = _nchw(act1, 15, 32).contiguous()
+    dx = torch.nn.grad.conv2d_input(x.shape, W.w2, g, stride=2)
+    dY1 = torch.where(x > 0, dx, torch.zeros_like(dx))
+    return _nhwc(dY1), torch.nn.grad.conv2d_weight(x, W.w2.shape, g, stride=2), g.sum((0, 2, 3))
+
+
+def conv1_bwd(dY1, qdY1, obs_u8, W: Weights):
+    """dY1 unrounded (the bias sum), q(dY1) (the weight gradient), image bytes ->
+    (d w1 [32,3,8,8], d b1)."""
+    x = obs_u8.to(W.w1.dtype)
+    dw = torch.nn.grad.conv2d_weight(x, W.w1.shape, _nchw(qdY1, 15, 32).contiguous(), stride=4)
+    return dw * (1.0 / 255.0), dY1.sum((0, 1, 2))
+
+
+def _canon_grads(g: Dict[str, torch.Tensor], A: int) -> Dict[str, np.ndarray]:
+    """Stage gradients (export order) -> the 14 canonical blocks."""
+    inv = torch.empty_like(_PERM)
+    inv[_PERM] = torch.arange(1024)
+    out = {k: g[k] for k in ("w1", "b1", "w2", "b2", "w3", "b3", "bfc")}
+    out["lng"], out["lnb"], out["wfc"] = g["lng"][inv], g["lnb"][inv], g["wfc"][:, inv]
+    out["wa"], out["ba"] = g["wh"][:A], g["bh"][:A]
+    out["wc"], out["bc"] = g["wh"][VCOL:VCOL + 1], g["bh"][VCOL:VCOL + 1]
+    return {k: out[k].double().numpy() for k in BLOCKS}
+
+
+def run(flat, batch, A: int, given: Optional[dict] = None, quant: bool = True,
+        dtype=torch.float64, algo: str = "impala", forward_only: bool = False) -> dict:
+    """Every stage of one step.  ``given`` = the tensors of a real step (teacher forcing: each
+    stage reads ITS inputs from there, so the outputs are references for that step's tensors);
+    None chains the stages on their own outputs, rounded to bf16 where the kernels round when
+    ``quant`` (dtype float32: the CPU stand-in of the bf16 kernels; quant False, float64: the
+    network itself).  -> {"t": name -> tensor before rounding (numpy float64), "grads": the 14
+    canonical blocks, "met": metrics, "mask1": uint32}.  ``given`` may also carry "dY1" (an
+    unrounded conv2 input gradient to round and use instead of the run's own)."""
+    W = Weights(flat, A, quant, dtype)
+    q = rne_bf16 if quant else (lambda t: t)
+    t: Dict[str, torch.Tensor] = {}
+
+    def inp(name):  # the tensor a stage reads
+        if given is not None:
+            return torch.from_numpy(np.ascontiguousarray(given[name], dtype=np.float64)).to(dtype)
+        return q(t[name]) if name in T_TENSORS or name in ("dH", "dY1") else t[name]
+
+    obs = torch.from_numpy(np.ascontiguousarray(batch[0])).reshape(-1, 3, 64, 64)
+    with torch.no_grad():
+        t["act1"] = conv1_fwd(obs, W)
+        t["act2"] = conv2_fwd(inp("act1"), W)
+        t["act3"], t["lnstat"], t["y"] = conv3_ln_fwd(inp("act2"), W)
+        t["zg"], t["h"] = fc_fwd(inp("y"), W)
+        t["heads"] = heads_fwd(inp("h"), W)
+    out = {"mask1": mask_bits(inp("act1").numpy())}
+    if not forward_only:
+        head = impala_head if algo == "impala" else ppo_head
+        t["dH"], out["met"] = head(inp("heads").double().numpy(), batch, A, dtype=dtype)
+        with torch.no_grad():
+            qdH = q(t["dH"])  # (never exported: always the run's own)
+            g = {}
+            t["dz"], g["wh"], g["bh"] = head_bwd(qdH, inp("zg"), inp("h"), W)
+            t["dy"], g["wfc"], g["bfc"] = fc_bwd(inp("dz"), inp("y"), W)
+            t["dact3"], g["lng"], g["lnb"] = ln_bwd(inp("dy"), inp("act3"), inp("lnstat"), W)
+            t["dact2"], g["w3"], g["b3"] = conv3_bwd(inp("dact3"), inp("act2"), W)
+            t["dY1"], g["w2"], g["b2"] = conv2_bwd(inp("dact2"), inp("act1"), W)
+            qdY1 = q(t["dY1"])
+            if given is not None and "dY1" in given:
+                qdY1 = q(torch.from_numpy(np.asarray(given["dY1"], np.float64)).to(dtype))
+            g["w1"], g["b1"] = conv1_bwd(t["dY1"], qdY1, obs, W)
+        out["grads"] = _canon_grads(g, A)
+    out["t"] = {k: v.double().numpy() for k, v in t.items()}
+    return out
+
+
+def stand_in_tensors(run_out: dict, quant: bool = True) -> dict:
+    """What the kernels would export after a chained run: the workspace tensors alone (dH and
+    dY1 never leave LDS), those of the compute type rounded."""
+    return {k: (rne_bf16(torch.from_numpy(v).float()).double().numpy()
+                if quant and k in T_TENSORS else v)
+            for k, v in run_out["t"].items() if k in T_TENSORS + F32_TENSORS}
+
+
+# ------------------------------------------------------------------------------- figures
+def f32_figures(got, r):
+    """-> worst |got - r| / (|r| + rms r) (the normwise measure of test_gpu_parity_full.py)."""
+    got, r = np.asarray(got, np.float64), np.asarray(r, np.float64)
+    rms = float(np.sqrt(np.mean(r * r)))
+    return float(np.max(np.abs(got - r) / (np.abs(r) + rms + 1e-300)))
+
+
+def bf16_figures(got, r):
+    """got: a bf16 tensor (as float), r: its float64 reference before rounding ->
+    (worst |got - r| / (ulp(r) + 1e-5 (|r| + rms r)), share of elements with got != RNE_bf16(r),
+    worst |got - r| in ulp(r) over the mismatching elements)."""
+    got, r = np.asarray(got, np.float64), np.asarray(r, np.float64)
+    rms = float(np.sqrt(np.mean(r * r)))
+    d = np.abs(got - r)
+    tol = ulp_bf16(r) + 1e-5 * (np.abs(r) + rms)
+    worst = float(np.max(d / (tol + 1e-300)))
+    want = rne_bf16(torch.from_numpy(np.ascontiguousarray(r))).numpy()
+    miss = got != want
+    u = ulp_bf16(r)
+    wu = float(np.max(d[miss] / np.maximum(u[miss], 1e-300))) if miss.any() else 0.0
+    return worst, float(np.mean(miss)), wu
+
+
+def rel_l2(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))

@@ -89,6 +89,8 @@ def test_kernel_entry_points_validate_before_launch():
     # device step clock: a null handle is refused before any HIP call
     assert lib.impala_step_clock(None, None, 3) == 1001
     assert lib.impala_step_clock_end(None, None, None) == 1001
+    # workspace export: likewise
+    assert lib.impala_debug_read(None, 0, None, 4, None) == 1001
 
 
 def test_headers_compile_as_c99(tmp_path):
