@@ -85,6 +85,15 @@ DQN_EXPORTS = (
     "dqn_replay_state", "dqn_replay_extend", "dqn_replay_extend_rollout", "dqn_replay_sample",
     "dqn_replay_update", "dqn_train_step_replay", "dqn_train_step_replay_rows", "dqn_replay_weights",
 )
+# every symbol declared in include/iqn_hip.h
+IQN_EXPORTS = (
+    "iqn_abi_version", "iqn_last_error", "iqn_config_default", "iqn_param_count", "iqn_create",
+    "iqn_destroy", "iqn_bind_params", "iqn_sync_target", "iqn_refresh_weights", "iqn_forward",
+    "iqn_act", "iqn_nstep_targets", "iqn_loss_head",
+)
+IQN_ABI_VERSION = 1
+IQN_MAX_TAU = 32
+IQN_MAX_ROWS = 16384
 DQN_ABI_VERSION = 2
 DQN_REPLAY_BLOCK = 512  # rows per block sum of the replay's two-level sampling
 DQN_MAX_BATCH = 4096
@@ -156,6 +165,11 @@ class DqnConfig(C.Structure):
                 ("lr", C.c_float), ("adam_beta1", C.c_float), ("adam_beta2", C.c_float),
                 ("adam_eps", C.c_float), ("max_grad_norm", C.c_float),
                 ("importance_sampling_exponent", C.c_float)]
+
+
+class IqnConfig(C.Structure):
+    _fields_ = [("batch_size", C.c_int), ("num_actions", C.c_int), ("n_tau", C.c_int),
+                ("dtype", C.c_int)]
 
 
 class DqnBatch(C.Structure):
@@ -286,6 +300,23 @@ def _declare(lib):
     lib.dqn_train_step_replay.argtypes = [_P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]
     lib.dqn_train_step_replay_rows.argtypes = [_P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]
     lib.dqn_replay_weights.argtypes = [_P, _P, _P, _P]
+    lib.iqn_config_default.argtypes = [C.POINTER(IqnConfig)]
+    lib.iqn_param_count.argtypes = [C.c_int]
+    lib.iqn_create.argtypes = [C.POINTER(IqnConfig), C.c_int, C.POINTER(_P)]
+    lib.iqn_destroy.argtypes = [_P]
+    lib.iqn_bind_params.argtypes = [_P, _P, _P, _P]
+    lib.iqn_sync_target.argtypes = [_P, _P]
+    lib.iqn_refresh_weights.argtypes = [_P, _P]
+    lib.iqn_forward.argtypes = [_P, _P, C.c_int, C.c_int, _P, C.c_uint64, C.c_uint64, _P, _P, _P]
+    lib.iqn_act.argtypes = [_P, _P, C.c_int, _P, C.c_float, C.c_uint64, C.c_uint64, _P, _P, _P, _P,
+                            _P, _P, _P]
+    lib.iqn_nstep_targets.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_float, _P,
+                                      _P, _P]
+    lib.iqn_loss_head.argtypes = [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_float, C.c_float, _P, _P, _P, _P, _P]
+    for name in IQN_EXPORTS:
+        getattr(lib, name).restype = (C.c_char_p if name == "iqn_last_error" else
+                                      C.c_size_t if name == "iqn_param_count" else C.c_int)
     for name in DQN_EXPORTS:
         getattr(lib, name).restype = (C.c_char_p if name == "dqn_last_error" else
                                       C.c_size_t if name == "dqn_param_count" else C.c_int)

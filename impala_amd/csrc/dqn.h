@@ -64,7 +64,8 @@ struct TargetView {
   impala_learner* c;
   float *params, *vecs, *heads;
   void* shadow;
-  explicit TargetView(dqn_learner* h) : c(h->core), params(c->params), vecs(c->vecs), heads(c->heads), shadow(c->shadow) {
+  template <class H>  // dqn_learner, iqn_learner (iqn.h)
+  explicit TargetView(H* h) : c(h->core), params(c->params), vecs(c->vecs), heads(c->heads), shadow(c->shadow) {
     c->params = h->target_params; c->vecs = h->t_vecs; c->heads = h->t_heads; c->shadow = h->t_shadow;
   }
   ~TargetView() { c->params = params; c->vecs = vecs; c->heads = heads; c->shadow = shadow; }

@@ -161,6 +161,9 @@ struct impala_learner {
   // DQN handles (dqn.h): the step's priorities output and the importance-sampling exponent
   float* dqn_prio = nullptr;
   float dqn_beta = 0.4f;
+  // IQN handles (iqn.h): launch_forward stops after the conv trunk (act3); the quantile head runs
+  // on the handle's own rows
+  bool trunk_only = false;
   // live launch timer (impala_timer_*): per kernel id, event pairs handed to
   // hipExtLaunchKernel, which stamps the kernel's own start / end (as rocprofv3 does)
   struct KTimer {
@@ -287,6 +290,8 @@ int launch_forward(impala_learner* h, const uint8_t* obs, int n, hipStream_t st,
                         dim3(persist_grid(h, cdiv((long)n * P3, 64))), dim3(256), st, op, 1))
       return r;
   }
+  // (the conv tail's own y and LayerNorm statistics are computed and unused)
+  if (h->trunk_only) return 0;
   {
     FcFwd<T, HID> op{n, sw + sh.wfc, vv + Vecs::bfc, (const T*)h->y, h->zg, (T*)h->h};
     using C = FcFwdCfg<T>;
@@ -1600,3 +1605,4 @@ int impala_ppo_loss_head(const float* logits, const float* values, const int64_t
 // the Ape-X DQN entry points (include/dqn_hip.h) on the launchers above
 #include "dqn.h"
 #include "dqn_replay.h"
+#include "iqn.h"

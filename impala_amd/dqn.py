@@ -297,13 +297,14 @@ class AtariDQNModel(FlatModule):
                                                 dtype=self.compute_dtype))
 
 
-def _replay_columns(items):
-    """``(s [n,3,64,64], a [n], target [n])`` from either form ``PrioritizedReplay.extend`` takes."""
+def _replay_columns(items, width: int = 1):
+    """``(s [n,3,64,64], a [n], target [n])`` from either form ``PrioritizedReplay.extend`` takes
+    (``target [n, width]`` for a ring of ``width`` targets per transition)."""
     if isinstance(items, (list,)) and items and isinstance(items[0], (tuple, list)):
         cols = list(zip(*items))
         s = torch.cat([x if x.dim() == 4 else x.unsqueeze(0) for x in cols[0]])
         a = torch.cat([x.reshape(-1) for x in cols[1]])
-        t = torch.cat([x.reshape(-1) for x in cols[2]])
+        t = torch.cat([x.reshape(-1) if width == 1 else x.reshape(-1, width) for x in cols[2]])
         return s, a, t
     return items
 
@@ -316,11 +317,18 @@ class PrioritizedReplay:
     The returned ``probabilities`` are normalised (``p^α / Σ p^α``); whether rlmeta returns these
     or the raw ``p^α`` is not pinned, and the learner's weights ``w / max w`` do not depend on
     that scale.
+
+    ``target_width=W > 1`` makes ``target`` a ``[capacity, W]`` array: one row of W quantile targets
+    per transition (the distributional actor's, impala_amd/iqn.py); ``extend`` then takes
+    ``target [n, W]`` and ``sample`` returns ``target [n, W]``.
     """
 
     def __init__(self, capacity: int, priority_exponent: float = 0.6, device="cuda",
-                 seed: Optional[int] = None, obs_shape=OBS_SHAPE):
+                 seed: Optional[int] = None, obs_shape=OBS_SHAPE, target_width: int = 1):
         self.capacity = int(capacity)
+        self.target_width = int(target_width)
+        if self.target_width < 1:
+            raise ValueError("target_width must be >= 1")
         self.alpha = float(priority_exponent)
         self.device = torch.device(device)
         self._alloc_ring(obs_shape)
@@ -331,7 +339,8 @@ class PrioritizedReplay:
         cap, dev = self.capacity, self.device
         self.s = torch.zeros((cap,) + tuple(obs_shape), dtype=torch.uint8, device=dev)
         self.a = torch.zeros(cap, dtype=torch.int64, device=dev)
-        self.target = torch.zeros(cap, dtype=torch.float32, device=dev)
+        shape = (cap,) if self.target_width == 1 else (cap, self.target_width)
+        self.target = torch.zeros(shape, dtype=torch.float32, device=dev)
         self.priorities = torch.zeros(cap, dtype=torch.float32, device=dev)
 
     def _init_sampler(self) -> None:
@@ -357,7 +366,7 @@ class PrioritizedReplay:
         """items: ``(s [n,3,64,64], a [n], target [n])`` or a list of per-transition triples (each
         with or without a leading dim).  Items without a priority get the current maximum.
         Returns the ring keys written."""
-        s, a, t = _replay_columns(items)
+        s, a, t = _replay_columns(items, self.target_width)
         n = s.shape[0]
         if n > self.capacity:
             raise ValueError("more items than the ring holds")
@@ -365,7 +374,7 @@ class PrioritizedReplay:
         keys = (torch.arange(n, device=self.device) + cursor) % self.capacity
         self.s[keys] = s.to(self.device)
         self.a[keys] = a.reshape(-1).to(self.device, torch.int64)
-        self.target[keys] = t.reshape(-1).to(self.device, torch.float32)
+        self.target[keys] = t.reshape((n,) + self.target.shape[1:]).to(self.device, torch.float32)
         if priorities is None:
             self.priorities[keys] = self._max_priority
         else:
@@ -431,7 +440,11 @@ class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
     _destroy, _last_error = "dqn_replay_destroy", _ERR
 
     def __init__(self, capacity: int, priority_exponent: float = 0.6, device="cuda",
-                 seed: Optional[int] = None, obs_shape=OBS_SHAPE, in_place: bool = False):
+                 seed: Optional[int] = None, obs_shape=OBS_SHAPE, in_place: bool = False,
+                 target_width: int = 1):
+        if target_width != 1:
+            raise NotImplementedError("NativePrioritizedReplay holds scalar targets only "
+                                      "(target_width 1); PrioritizedReplay takes target_width > 1")
         self.in_place = bool(in_place)
         device = torch.device(device)
         if device.type != "cuda":
@@ -690,6 +703,11 @@ class ApexActor(Actor):
         self._trajectory = []
         self._last_transition = None
 
+    @staticmethod
+    def _star(v) -> torch.Tensor:
+        """One step's bootstrap value as it is stacked (a scalar; the distributional actor's: a row)."""
+        return torch.as_tensor(v, dtype=torch.float32).reshape(())
+
     def act(self, timestep):  # learning.py:31-33
         obs = timestep.observation if hasattr(timestep, "observation") else timestep[0]
         action, q, v = self._model.act(obs, self._eps)
@@ -716,7 +734,8 @@ class ApexActor(Actor):
         f32 = lambda x: torch.as_tensor(x, dtype=torch.float32).reshape(())
         self._trajectory.append((torch.as_tensor(obs).reshape(OBS_SHAPE),
                                  torch.as_tensor(act).reshape(()), f32(reward),
-                                 torch.as_tensor(done).reshape(()), f32(info["q"]), f32(info["v"])))
+                                 torch.as_tensor(done).reshape(()), f32(info["q"]),
+                                 self._star(info["v"])))
         self._last_transition = next_timestep
         if len(self._trajectory) == self._rollout_length:
             self.update()

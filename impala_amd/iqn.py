@@ -1,0 +1,371 @@
+"""The distributional (IQN) Ape-X actor path on the HIP library:
+``DistributionalAtariDQN`` (models/distributed_models.py:35-69 over
+models/models.py:90-101 and models/quantile_layers.py:7-54), ``ApexDistributionalActor``
+(agents/dqn/learning.py:68-84), ``ApexDistributionalBuilder`` (agents/dqn/builder.py:124-156)
+and the quantile-regression loss as a standalone head (``iqn_loss_head``).
+
+The network is the dueling DQN's trunk and heads with a quantile embedding multiplied into the
+trunk's features before the LayerNorm: W = ``n_tau_samples`` quantiles per frame, so one call on
+n frames runs the head on n W rows.  Every compute entry is one call of include/iqn_hip.h; the
+compute path is the HIP library only.  The training step through the trunk is not built yet:
+``ApexDistributionalBuilder.make_learner`` raises ``NotImplementedError``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from impala_amd import _lib
+from impala_amd._lib import check, lib
+from impala_amd.core import Actor
+from impala_amd.dqn import (ApexActor, ApexDQNBuilder, ConstantEpsFunc, FlexibleEpsFunc,
+                            PrioritizedReplay)
+from impala_amd.flat import FlatModule, layer_init_truncated, spec_count
+from impala_amd.model import OBS_SHAPE
+
+HIDDEN = 512
+N_COS = 64  # QuantileLayer.n_cos_embedding
+_ERR = "iqn_last_error"
+
+
+def net_specs(num_actions: int = 15) -> List[Tuple[str, Tuple[int, ...]]]:
+    """``parameters()`` names / shapes of one DistributionalAtariNetwork (models/models.py:90-101)."""
+    return [
+        ("body.body.0.weight", (32, 3, 8, 8)), ("body.body.0.bias", (32,)),
+        ("body.body.2.weight", (64, 32, 4, 4)), ("body.body.2.bias", (64,)),
+        ("body.body.4.weight", (64, 64, 3, 3)), ("body.body.4.bias", (64,)),
+        ("q.quantile_layer.output_layer.0.weight", (1024, N_COS)),
+        ("q.quantile_layer.output_layer.0.bias", (1024,)),
+        ("q.project.0.weight", (1024,)), ("q.project.0.bias", (1024,)),
+        ("q.project.1.weight", (HIDDEN, 1024)), ("q.project.1.bias", (HIDDEN,)),
+        ("q.q.weight", (num_actions, HIDDEN)), ("q.q.bias", (num_actions,)),
+        ("q.v.weight", (1, HIDDEN)), ("q.v.bias", (1,)),
+    ]
+
+
+def param_specs(num_actions: int = 15):
+    """DistributionalAtariDQN.parameters(): the online net, then the target net."""
+    s = net_specs(num_actions)
+    return [("online_net." + k, v) for k, v in s] + [("target_net." + k, v) for k, v in s]
+
+
+def param_count(num_actions: int = 15) -> int:
+    """Parameters of one net (the online net alone): iqn_param_count."""
+    return spec_count(net_specs(num_actions))
+
+
+def default_config() -> _lib.IqnConfig:
+    cfg = _lib.IqnConfig()
+    check(lib().iqn_config_default(C.byref(cfg)), "iqn_config_default", _ERR)
+    return cfg
+
+
+def iqn_init_flat(action_dim: int) -> torch.Tensor:
+    """Reference init of one DistributionalAtariNetwork as a flat CPU tensor: the layers are
+    constructed in the reference's order (body, quantile layer, project, q, v), each consuming
+    the global RNG as there (``trunk_init_flat`` with the quantile layer's Linear in its place)."""
+    trunc = layer_init_truncated
+    layers = [trunc(nn.Conv2d(3, 32, 8, stride=4), 3 * 64),
+              trunc(nn.Conv2d(32, 64, 4, stride=2), 32 * 16),
+              trunc(nn.Conv2d(64, 64, 3, stride=1), 64 * 9),
+              trunc(nn.Linear(N_COS, 1024), N_COS),
+              nn.LayerNorm(1024), trunc(nn.Linear(1024, HIDDEN), 1024),
+              trunc(nn.Linear(HIDDEN, action_dim), HIDDEN), trunc(nn.Linear(HIDDEN, 1), HIDDEN)]
+    return torch.cat([t.detach().reshape(-1) for l in layers for t in (l.weight, l.bias)])
+
+
+def iqn_nstep_targets(rewards, done, q_pi, q_star, n_step: int = 3, gamma: float = 0.99):
+    """One rollout of L steps -> (targets [L-1, W], priorities [L-1]) on q_star's device
+    (``iqn_nstep_targets``): rewards [L], done [L], q_pi [L], q_star [L, W]."""
+    q_star = q_star.contiguous().float()
+    if q_star.dim() != 2:
+        raise ValueError("q_star: [L, W]")
+    dev = q_star.device
+    L, W = q_star.shape
+    f32 = lambda x: x.reshape(-1).to(dev, torch.float32).contiguous()
+    r, q_pi = f32(rewards), f32(q_pi)
+    d = done.reshape(-1).to(dev).ne(0).to(torch.uint8).contiguous()
+    if not all(x.numel() == L for x in (r, d, q_pi)):
+        raise ValueError("iqn_nstep_targets: every field has one entry per step")
+    targets = torch.empty(max(L - 1, 0), W, device=dev)
+    prio = torch.empty(max(L - 1, 0), device=dev)
+    check(lib().iqn_nstep_targets(_lib.ptr(r), _lib.ptr(d), _lib.ptr(q_pi), _lib.ptr(q_star), L, W,
+                                  int(n_step), float(gamma), _lib.ptr(targets), _lib.ptr(prio),
+                                  _lib.stream_ptr(None)), "iqn_nstep_targets", _ERR)
+    return targets, prio
+
+
+def iqn_loss_head(adv, v, actions, taus, targets, probabilities=None, huber_param: float = 1.0,
+                  importance_sampling_exponent: float = 0.4) -> Dict[str, torch.Tensor]:
+    """The quantile-regression loss alone on given heads (``iqn_loss_head``): adv [N,Ws,A],
+    v [N,Ws], taus [N,Ws], targets [N,Wt] fp32 on the GPU."""
+    adv = adv.contiguous().float()
+    N, Ws, A = adv.shape
+    dev = adv.device
+    targets = targets.contiguous().float()
+    Wt = targets.shape[1]
+    v, taus = v.reshape(N, Ws).contiguous().float(), taus.reshape(N, Ws).contiguous().float()
+    actions = actions.reshape(-1).contiguous().to(torch.int64)
+    if probabilities is not None:
+        probabilities = probabilities.reshape(-1).contiguous().float()
+    out = dict(dadv=torch.empty_like(adv), dv=torch.empty(N, Ws, device=dev),
+               priorities=torch.empty(N, device=dev), metrics=torch.empty(4, device=dev))
+    check(lib().iqn_loss_head(_lib.ptr(adv), _lib.ptr(v), _lib.ptr(actions), _lib.ptr(taus),
+                              _lib.ptr(targets), _lib.ptr(probabilities), N, Ws, Wt, A,
+                              float(huber_param), float(importance_sampling_exponent),
+                              _lib.ptr(out["dadv"]), _lib.ptr(out["dv"]),
+                              _lib.ptr(out["priorities"]), _lib.ptr(out["metrics"]),
+                              _lib.stream_ptr(None)), "iqn_loss_head", _ERR)
+    return out
+
+
+class IqnEngine(_lib.NativeHandle):
+    """One ``iqn_learner`` handle bound to a ``DistributionalAtariDQN``'s flat buffers."""
+    _destroy, _last_error = "iqn_destroy", _ERR
+
+    def __init__(self, model: "DistributionalAtariDQN", batch_size: int = 128,
+                 dtype: Optional[str] = None):
+        self.model = model
+        self.device = model.flat.device
+        if self.device.type != "cuda":
+            raise RuntimeError("the IQN engine runs on the HIP path only (cuda device)")
+        self.N, self.A, self.W = int(batch_size), model.action_dim, model.n_tau_samples
+        cfg = default_config()
+        cfg.batch_size, cfg.num_actions, cfg.n_tau = self.N, self.A, self.W
+        cfg.dtype = _lib.IMPALA_DTYPE_BF16 if (dtype or model.compute_dtype) == "bf16" \
+            else _lib.IMPALA_DTYPE_F32
+        self._open("iqn_create", C.byref(cfg), self.device_index(self.device))
+        check(lib().iqn_bind_params(self._h, _lib.ptr(model.flat), _lib.ptr(model.target_flat),
+                                    _lib.stream_ptr(None)), "iqn_bind_params", _ERR)
+        self._version = model._version
+
+    def _fresh(self):
+        if self._version != self.model._version:  # the flat buffers were written from outside
+            check(lib().iqn_refresh_weights(self._h, _lib.stream_ptr(None)), "iqn_refresh_weights", _ERR)
+            self._version = self.model._version
+
+    def _taus(self, taus, n):
+        if taus is None:
+            return None
+        taus = taus.to(self.device, torch.float32).contiguous()
+        if tuple(taus.shape) != (n, self.W):
+            raise ValueError(f"taus: [{n}, {self.W}]")
+        return taus
+
+    def forward(self, obs: torch.Tensor, target: bool = False, taus=None, seed: int = 0,
+                counter: int = 0):
+        """-> (q [n, W, A], taus [n, W]) on the device; ``taus`` None: drawn from (seed, counter)."""
+        self._fresh()
+        obs = obs.contiguous()
+        n = obs.shape[0]
+        taus = self._taus(taus, n)
+        q = torch.empty(n, self.W, self.A, device=self.device)
+        used = torch.empty(n, self.W, device=self.device)
+        check(lib().iqn_forward(self._h, _lib.ptr(obs), n, 1 if target else 0, _lib.ptr(taus),
+                                int(seed), int(counter), _lib.ptr(q), _lib.ptr(used),
+                                _lib.stream_ptr(None)), "iqn_forward", _ERR)
+        return q, used
+
+    def act(self, obs: torch.Tensor, eps, seed: int, counter: int, taus_online=None,
+            taus_target=None):
+        """-> (action [n] i64, q_pi [n], q_star [n, W], greedy [n] i64) on the device."""
+        self._fresh()
+        obs = obs.contiguous()
+        n = obs.shape[0]
+        eps_t, eps_all = None, 0.0
+        if isinstance(eps, torch.Tensor) and eps.numel() > 1:
+            eps_t = eps.reshape(-1).to(self.device, torch.float32).contiguous()
+            if eps_t.numel() != n:
+                raise ValueError("eps: one value, or one per frame")
+        else:
+            eps_all = float(eps.reshape(-1)[0]) if isinstance(eps, torch.Tensor) else float(eps)
+        t_on, t_tg = self._taus(taus_online, n), self._taus(taus_target, n)
+        a = torch.empty(n, dtype=torch.int64, device=self.device)
+        g = torch.empty(n, dtype=torch.int64, device=self.device)
+        q_pi, q_star = torch.empty(n, device=self.device), torch.empty(n, self.W, device=self.device)
+        check(lib().iqn_act(self._h, _lib.ptr(obs), n, _lib.ptr(eps_t), eps_all, int(seed),
+                            int(counter), _lib.ptr(t_on), _lib.ptr(t_tg), _lib.ptr(a),
+                            _lib.ptr(q_pi), _lib.ptr(q_star), _lib.ptr(g), _lib.stream_ptr(None)),
+              "iqn_act", _ERR)
+        return a, q_pi, q_star, g
+
+    def sync_target(self) -> None:
+        self._fresh()
+        check(lib().iqn_sync_target(self._h, _lib.stream_ptr(None)), "iqn_sync_target", _ERR)
+
+
+class DistributionalAtariDQN(FlatModule):
+    """Drop-in for ``models.distributed_models.DistributionalAtariDQN`` on an MI355X: the online
+    and the target net are one flat fp32 buffer each, exposed as ``nn.Parameter`` views under the
+    reference's ``state_dict`` names (``target_net.*`` with ``requires_grad=False``), with the
+    reference's ``embedding_range`` buffers beside them."""
+
+    def __init__(self, observation_space: Tuple[int, ...] = OBS_SHAPE, action_dim: int = 15,
+                 n_tau_samples: int = 32, device="cuda", seed: Optional[int] = None,
+                 dtype: str = "fp32"):
+        super().__init__()
+        if tuple(observation_space) != OBS_SHAPE:
+            raise ValueError(f"AtariBody requires observations of shape {OBS_SHAPE}")
+        if not 1 <= action_dim <= 15:
+            raise ValueError("action_dim must be in [1, 15]")
+        if not 1 <= n_tau_samples <= _lib.IQN_MAX_TAU:
+            raise ValueError(f"n_tau_samples must be in [1, {_lib.IQN_MAX_TAU}]")
+        self.action_dim = action_dim
+        self.n_tau_samples = int(n_tau_samples)
+        self.compute_dtype = dtype
+        device = torch.device(device)
+        self._specs = net_specs(action_dim)
+        self._attach_segments(device)
+        for net in (self.online_net, self.target_net):  # QuantileLayer's buffer (int64, (1, 1, 64))
+            net.q.quantile_layer.register_buffer(
+                "embedding_range", torch.arange(1, N_COS + 1, device=device).reshape(1, 1, N_COS))
+        self._train_engine = None
+        self._infer_engine = None
+        self._act_seed = int.from_bytes(os.urandom(8), "little") >> 2
+        self._act_calls = 0
+        self.reset_parameters(seed)
+
+    def _segment_table(self):
+        return [("online_net", self._specs, "flat", "flat_grad"),
+                ("target_net", self._specs, "target_flat", None)]
+
+    # ---------------------------------------------------------------- parameters
+    def reset_parameters(self, seed: Optional[int] = None) -> None:
+        """Reference init (``iqn_init_flat``, after seeding the global torch RNG with ``seed``);
+        the target net is a copy of the online net (distributed_models.py:40)."""
+        if seed is not None:
+            torch.manual_seed(int(seed))
+        with torch.no_grad():
+            self.flat.copy_(iqn_init_flat(self.action_dim).to(self.flat.device))
+            self.target_flat.copy_(self.flat)
+        self.params_changed()
+
+    def load_flat(self, flat, target=None) -> None:
+        with torch.no_grad():
+            self.flat.copy_(torch.as_tensor(np.asarray(flat, dtype=np.float32)).to(self.flat.device))
+            if target is not None:
+                self.target_flat.copy_(torch.as_tensor(np.asarray(target, dtype=np.float32)).to(
+                    self.flat.device))
+        self.params_changed()
+
+    # ---------------------------------------------------------------- compute
+    def _engine(self) -> IqnEngine:
+        if self._train_engine is not None:
+            return self._train_engine
+        if self._infer_engine is None:
+            # the reference serves act() in batches of <= 128 (distributed_models.py:47)
+            self._infer_engine = IqnEngine(self, batch_size=128)
+        return self._infer_engine
+
+    def _next_draw(self) -> Tuple[int, int]:
+        self._act_calls += 1
+        return self._act_seed, self._act_calls
+
+    def forward(self, obs: torch.Tensor, taus: Optional[torch.Tensor] = None):
+        """distributed_models.py:44-45 -> (q [N, W, A], taus [N, W]) of the online net; ``taus``
+        None: drawn by the library (the reference draws ``torch.rand``)."""
+        if obs.device.type != "cuda" or self.flat.device.type != "cuda":
+            raise RuntimeError("DistributionalAtariDQN.forward runs on the HIP path only (cuda device)")
+        seed, counter = self._next_draw()
+        return self._engine().forward(obs, taus=taus, seed=seed, counter=counter)
+
+    @torch.no_grad()
+    def act(self, obs: torch.Tensor, eps: torch.Tensor):
+        """distributed_models.py:47-66 -> (action [N,1], q_pi [N,1], q_star [N,W]) on the CPU."""
+        if self.flat.device.type != "cuda":
+            raise RuntimeError("DistributionalAtariDQN.act runs on the HIP path only (cuda device)")
+        x = obs.to(self.flat.device)
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        seed, counter = self._next_draw()
+        a, q_pi, q_star, _ = self._engine().act(x, eps, seed=seed, counter=counter)
+        return a.unsqueeze(-1).cpu(), q_pi.unsqueeze(-1).cpu(), q_star.cpu()
+
+    def sync_target_net(self) -> None:  # distributed_models.py:68-69
+        if self.flat.device.type == "cuda":
+            self._engine().sync_target()
+        else:
+            with torch.no_grad():
+                self.target_flat.copy_(self.flat)
+
+    def clone_to(self, device) -> "DistributionalAtariDQN":
+        return self._frozen_clone(DistributionalAtariDQN(
+            OBS_SHAPE, self.action_dim, self.n_tau_samples, device=device, dtype=self.compute_dtype))
+
+
+class ApexDistributionalActor(ApexActor):
+    """``ApexDistributionalActor`` (agents/dqn/learning.py:68-84) for in-process actors: as
+    ``ApexActor``, with ``q_star`` a row of W quantiles per step; ``update`` computes the
+    per-quantile n-step targets and the initial priorities with ``iqn_nstep_targets`` and extends
+    a ``PrioritizedReplay(target_width=W)`` with ``(obs, action, target [W])`` rows."""
+
+    @staticmethod
+    def _star(v) -> torch.Tensor:
+        return torch.as_tensor(v, dtype=torch.float32).reshape(-1)
+
+    def update(self) -> None:
+        if self._replay_buffer is None or len(self._trajectory) < 2:
+            return
+        s, a, r, d, q_pi, q_star = (torch.stack(x) for x in zip(*self._trajectory))
+        self._trajectory = []
+        dev = self._replay_buffer.device
+        targets, prio = iqn_nstep_targets(r, d, q_pi, q_star.to(dev), self._n_step, self._gamma)
+        self._replay_buffer.extend((s[:-1], a[:-1].to(torch.int64), targets), prio)
+
+
+class ApexDistributionalActorFactory:
+    """Actor index -> an ``ApexDistributionalActor`` exploring at ``eps_func(index)``."""
+
+    def __init__(self, model, eps_func, rb=None, **kwargs):
+        self._model, self._eps_func, self._rb, self._kwargs = model, eps_func, rb, kwargs
+
+    def __call__(self, index: int) -> Actor:
+        return ApexDistributionalActor(self._model, self._rb, eps=self._eps_func(index), **self._kwargs)
+
+
+class ApexDistributionalBuilder(ApexDQNBuilder):
+    """agents/dqn/builder.py:124-156 on the HIP library: the network and the actor; the learner's
+    step is not built yet."""
+
+    def make_replay(self, native: bool = False, in_place: bool = False):
+        """A ``PrioritizedReplay`` whose targets are rows of ``n_tau_samples`` quantiles."""
+        if native or in_place:
+            raise NotImplementedError("the native replay holds scalar targets only (target_width 1)")
+        return PrioritizedReplay(self.cfg.agent.replay_buffer_size,
+                                 priority_exponent=float(self.cfg.agent.priority_exponent),
+                                 device=self.cfg.distributed.train_device,
+                                 seed=self.cfg.training.seed,
+                                 target_width=int(self.cfg.agent.n_tau_samples))
+
+    def make_actor(self, model, rb=None, deterministic: bool = False):  # builder.py:140-146
+        if deterministic:
+            eps_func = ConstantEpsFunc(self.cfg.agent.eval_eps)
+        else:
+            eps_func = FlexibleEpsFunc(self.cfg.agent.train_eps, self.cfg.training.num_rollouts)
+        if rb is not None and getattr(rb, "target_width", 1) != model.n_tau_samples:
+            raise ValueError("the replay's target_width must equal the model's n_tau_samples")
+        return ApexDistributionalActorFactory(model, eps_func, rb, n_step=int(self.cfg.agent.n_step),
+                                              rollout_length=int(self.cfg.agent.rollout_length))
+
+    def make_learner(self, model, rb):  # builder.py:126-138
+        raise NotImplementedError(
+            "DistributionalApex's training step (the quantile-regression loss through the quantile "
+            "layer, the modulation and the trunk's backward) is not built yet; iqn_loss_head is the "
+            "loss on given heads")
+
+    def make_network(self, env_spec=None):  # builder.py:148-156
+        obs_shape, n_act = OBS_SHAPE, 15
+        if env_spec is not None:
+            obs_shape = tuple(env_spec.observation_space.shape)
+            n_act = int(env_spec.action_space.n)
+        model = DistributionalAtariDQN(obs_shape, n_act, int(self.cfg.agent.n_tau_samples),
+                                       device=self.cfg.distributed.train_device)
+        self._learner_model = model
+        self._actor_model = model.clone_to(self.cfg.distributed.infer_device)
+        model.downstream = self._actor_model
+        return model

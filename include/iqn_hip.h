@@ -1,0 +1,126 @@
+/* iqn_hip.h — C-ABI of the MI355X-native distributional (IQN) Ape-X actor path (in
+ * libimpala_hip.so).
+ *
+ * The reference's distributional Ape-X variant (paths relative to the d3sm0/impala repository):
+ *
+ *   iqn_forward        models/models.py:90-101  DistributionalAtariNetwork.forward and
+ *                      models/quantile_layers.py:7-54  ImplicitQuantileHead / QuantileLayer
+ *                      (online or target net)
+ *   iqn_act            models/distributed_models.py:47-66  DistributionalAtariDQN.act
+ *   iqn_sync_target    models/distributed_models.py:68-69  sync_target_net
+ *   iqn_nstep_targets  agents/dqn/learning.py:69-84  ApexDistributionalActor._make_replay: the
+ *                      per-quantile n-step targets and the initial priorities of one rollout
+ *   iqn_loss_head      agents/dqn/learning.py:203-216  DistributionalApex._train_step's loss on
+ *                      given heads and models/quantile_layers.py:83-93  quantile_regression_loss
+ *                      (test / reuse entry; the training step through the trunk is not here yet)
+ *
+ * Network, for n frames and W = n_tau quantiles per frame (R = n W rows, row r = f W + k):
+ *   x_f = AtariBody(obs_f / 255); e_r[i] = cos(pi i tau_r), i = 1..64, the argument formed in fp32
+ *   as (pi * i) * tau; phi_r = GELU(Wq e_r + bq); y_r = LayerNorm(x_f * phi_r);
+ *   h_r = GELU(Wfc y_r + bfc); q = v + adv - mean_A(adv).
+ *
+ * Parameters are one flat fp32 buffer per net in torch `parameters()` order:
+ *   body.body.{0,2,4}.{weight,bias}, q.quantile_layer.output_layer.0.{weight,bias},
+ *   q.project.0.{weight,bias} (LayerNorm), q.project.1.{weight,bias}, q.q.{weight,bias},
+ *   q.v.{weight,bias}
+ * i.e. the dueling net's layout (dqn_hip.h) with 66,560 floats inserted before the LayerNorm.
+ *
+ * taus: every entry point that runs the net takes explicit taus (device, [n][W]) or NULL.  With
+ * NULL the library draws u = (mix(mix(seed ^ mix(counter)) + ((1 + which) << 32) + r) >> 40) 2^-24
+ * for row r, mix = splitmix64's finaliser, which = 0 online / 1 target: an index range disjoint
+ * from the action draw's (frame < 2^32) under the same (seed, counter).
+ *
+ * Conventions as impala_hip.h / dqn_hip.h: plain device pointers, `stream` = hipStream_t as void*,
+ * 0 = success else a hipError_t or IMPALA_E_* code with iqn_last_error() (the library's one
+ * last-error slot per thread) describing it.
+ */
+#ifndef IQN_HIP_H_
+#define IQN_HIP_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "impala_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define IQN_ABI_VERSION 1
+
+#define IQN_HIDDEN 512
+#define IQN_COS 64 /* cosine features of a quantile */
+#define IQN_MAX_ACTIONS 15
+#define IQN_MAX_TAU 32
+#define IQN_MAX_ROWS 16384 /* batch_size * n_tau */
+#define IQN_MAX_NSTEP 16   /* = DQN_REPLAY_MAX_NSTEP */
+
+typedef struct iqn_learner iqn_learner;
+
+typedef struct iqn_config {
+  int batch_size;  /* the most frames of one iqn_forward / iqn_act call */
+  int num_actions; /* 1..15 (iqn_act needs >= 2) */
+  int n_tau;       /* W quantiles per frame, 1..32 (conf/agent/apex.yaml n_tau_samples: 8) */
+  int dtype;       /* IMPALA_DTYPE_F32 / IMPALA_DTYPE_BF16 */
+} iqn_config;
+
+int iqn_abi_version(void);
+const char* iqn_last_error(void);
+int iqn_config_default(iqn_config* cfg);
+/* parameters of one net (the online net alone): 677,552 for A = 15 */
+size_t iqn_param_count(int num_actions);
+
+/* Invalid configurations (n_tau outside [1, 32], num_actions outside [1, 15], batch_size < 1 or
+ * batch_size * n_tau > IQN_MAX_ROWS, unknown dtype) are refused before any HIP call. */
+int iqn_create(const iqn_config* cfg, int device, iqn_learner** out);
+int iqn_destroy(iqn_learner* h);
+
+/* The two nets' flat fp32 [iqn_param_count] buffers (caller-owned); emits their kernel-layout
+ * weights. */
+int iqn_bind_params(iqn_learner* h, float* online, float* target, void* stream);
+/* target <- online: the flat parameters and the kernel-layout weights (device copies). */
+int iqn_sync_target(iqn_learner* h, void* stream);
+/* Re-emit both nets' kernel-layout weights after the caller wrote the flat buffers. */
+int iqn_refresh_weights(iqn_learner* h, void* stream);
+
+/* q [n][W][A] of n <= batch_size frames; which: 0 online net, 1 target net.  taus [n][W] or NULL
+ * (drawn from seed / counter, above); taus_out [n][W], optional, receives the taus used. */
+int iqn_forward(iqn_learner* h, const uint8_t* obs, int n, int which, const float* taus,
+                uint64_t seed, uint64_t counter, float* q, float* taus_out, void* stream);
+/* DistributionalAtariDQN.act on n <= batch_size frames: qbar = mean_k q_online[f][k][:] (summed
+ * k = 0..W-1, then divided by W), greedy = first maximal index of qbar, the action drawn as dqn_act
+ * draws it (1 - eps on greedy, eps / (A - 1) elsewhere, keyed by (seed, counter, frame)); eps [n] per
+ * frame, or NULL for eps_all.  actions [n] int64, q_pi [n] = qbar[action], q_star [n][W] =
+ * q_target[f][k][greedy] from a forward through the target net with its own taus; greedy [n]
+ * (int64, optional). */
+int iqn_act(iqn_learner* h, const uint8_t* obs, int n, const float* eps, float eps_all,
+            uint64_t seed, uint64_t counter, const float* taus_online, const float* taus_target,
+            int64_t* actions, float* q_pi, float* q_star, int64_t* greedy, void* stream);
+
+/* One rollout of L >= 2 steps -> L - 1 transitions: targets [L-1][W], column k the n-step return
+ * dqn_replay_extend_rollout defines (same fp32 nesting, one FMA per term) with v_t =
+ * q_star[t+1][k]; priorities [L-1] = |mean_k target[t][k] - q_pi[t]|, the mean a k-ordered fp32 sum
+ * divided by W.  rewards [L], done [L] (uint8), q_pi [L], q_star [L][W].  1 <= W <= IQN_MAX_TAU,
+ * 1 <= n_step <= IQN_MAX_NSTEP. */
+int iqn_nstep_targets(const float* rewards, const uint8_t* done, const float* q_pi,
+                      const float* q_star, int64_t L, int W, int n_step, float gamma,
+                      float* targets, float* priorities, void* stream);
+
+/* The quantile-regression loss alone on adv [N][Ws][A], v [N][Ws], actions [N], taus [N][Ws],
+ * targets [N][Wt], probabilities [N] or NULL (w = 1):
+ *   q[n][i] = dueling q at actions[n]; delta = target[n][j] - q[n][i]; rho = |tau[n][i] - 1[delta < 0]|
+ *   L_n = (1 / Wt) sum_j sum_i rho huber_kappa(delta)   (kappa = 0: |delta|)
+ *   loss = mean_n(w_n L_n), w_n = p_n^-beta / max_batch
+ * -> dadv [N][Ws][A], dv [N][Ws] (d loss / d heads; at an exact tie delta = 0 the kappa = 0
+ * gradient is 0), priorities [N] = |mean_j target - mean_i q|, metrics4 = {mean q, mean target,
+ * mean priorities, loss}.  1 <= Ws, Wt <= IQN_MAX_TAU.  No atomics: bitwise reproducible. */
+int iqn_loss_head(const float* adv, const float* v, const int64_t* actions, const float* taus,
+                  const float* targets, const float* probabilities, int N, int Ws, int Wt, int A,
+                  float huber_param, float beta, float* dadv, float* dv, float* priorities,
+                  float* metrics4, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* IQN_HIP_H_ */
