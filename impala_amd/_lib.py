@@ -80,7 +80,7 @@ DQN_EXPORTS = (
     "dqn_abi_version", "dqn_last_error", "dqn_config_default", "dqn_param_count", "dqn_create",
     "dqn_destroy", "dqn_bind_state", "dqn_bind_target", "dqn_sync_target", "dqn_refresh_weights",
     "dqn_set_step", "dqn_set_metrics", "dqn_set_metrics_host", "dqn_forward", "dqn_act",
-    "dqn_train_step", "dqn_loss_head",
+    "dqn_train_step", "dqn_compute_grads", "dqn_debug_read", "dqn_loss_head",
     "dqn_replay_block", "dqn_replay_create", "dqn_replay_destroy", "dqn_replay_bind",
     "dqn_replay_state", "dqn_replay_extend", "dqn_replay_extend_rollout", "dqn_replay_sample",
     "dqn_replay_update", "dqn_train_step_replay", "dqn_train_step_replay_rows", "dqn_replay_weights",
@@ -286,6 +286,8 @@ def _declare(lib):
     lib.dqn_act.argtypes = [_P, _P, C.c_int, _P, C.c_float, C.c_uint64, C.c_uint64, _P, _P, _P,
                             _P, _P]
     lib.dqn_train_step.argtypes = [_P, C.POINTER(DqnBatch), _P]
+    lib.dqn_compute_grads.argtypes = [_P, C.POINTER(DqnBatch), _P]
+    lib.dqn_debug_read.argtypes = [_P, C.c_int, C.c_int, _P, C.c_size_t, _P]
     lib.dqn_loss_head.argtypes = [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P,
                                   _P]
     lib.dqn_replay_create.argtypes = [C.c_int64, C.c_double, C.c_int, C.POINTER(_P)]

@@ -85,6 +85,20 @@ int dqn_check_frames(dqn_learner* h, const uint8_t* obs, int n) {
   return 0;
 }
 
+// forward, loss and backward of one batch: the pre-clip gradient in the bound grads, the
+// priorities and metrics 0..3 (dqn_train_step's first half, and all of dqn_compute_grads)
+int dqn_enqueue_grads(dqn_learner* h, const dqn_batch* b, void* stream) {
+  if (int r = dqn_check(h, true, false)) return r;
+  if (!b || !b->obs || !b->actions || !b->targets || !b->priorities)
+    return fail(IMPALA_E_INVALID, "null batch pointer");
+  if (((uintptr_t)b->obs & 15) != 0) return fail(IMPALA_E_INVALID, "obs must be 16-byte aligned");
+  impala_learner* c = h->core;
+  CK(hipSetDevice(c->device));
+  c->dqn_prio = b->priorities;
+  const impala_batch ib = dqn_core_batch(b);
+  return enqueue_grads(c, &ib, (hipStream_t)stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -265,16 +279,25 @@ int dqn_act(dqn_learner* h, const uint8_t* obs, int n, const float* eps, float e
 }
 
 int dqn_train_step(dqn_learner* h, const dqn_batch* b, void* stream) {
-  if (int r = dqn_check(h, true, false)) return r;
-  if (!b || !b->obs || !b->actions || !b->targets || !b->priorities)
-    return fail(IMPALA_E_INVALID, "null batch pointer");
-  if (((uintptr_t)b->obs & 15) != 0) return fail(IMPALA_E_INVALID, "obs must be 16-byte aligned");
-  impala_learner* c = h->core;
-  CK(hipSetDevice(c->device));
-  c->dqn_prio = b->priorities;
-  const impala_batch ib = dqn_core_batch(b);
-  if (int r = enqueue_grads(c, &ib, (hipStream_t)stream)) return r;
-  return enqueue_update(c, (hipStream_t)stream);
+  if (int r = dqn_enqueue_grads(h, b, stream)) return r;
+  return enqueue_update(h->core, (hipStream_t)stream);
+}
+
+int dqn_compute_grads(dqn_learner* h, const dqn_batch* b, void* stream) {
+  return dqn_enqueue_grads(h, b, stream);
+}
+
+int dqn_debug_read(dqn_learner* h, int net, int which, void* dst, size_t bytes, void* stream) {
+  if (!h || !h->core) return fail(IMPALA_E_INVALID, "null handle");
+  if (net != 0 && net != 1) return fail(IMPALA_E_INVALID, "net must be 0 (online) or 1 (target)");
+  if (net == 0 || which != IMPALA_DBG_HEADS) return impala_debug_read(h->core, which, dst, bytes, stream);
+  // the one tensor the target net keeps to itself (the workspace serves both nets)
+  if (!dst) return fail(IMPALA_E_INVALID, "null destination");
+  const size_t size = (size_t)h->core->N * net::HEADS * 4;
+  if (bytes == 0 || bytes > size) return fail(IMPALA_E_INVALID, "bytes must be in (0, the tensor's size]");
+  CK(hipSetDevice(h->core->device));
+  CK(hipMemcpyAsync(dst, h->t_heads, bytes, hipMemcpyDefault, (hipStream_t)stream));
+  return 0;
 }
 
 int dqn_loss_head(const float* adv, const float* v, const int64_t* actions, const float* targets,

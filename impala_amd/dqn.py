@@ -101,8 +101,8 @@ class DqnEngine(_lib.NativeHandle):
         self.N, self.A = int(batch_size), model.action_dim
         cfg = default_config()
         cfg.batch_size, cfg.num_actions = self.N, self.A
-        cfg.dtype = _lib.IMPALA_DTYPE_BF16 if (dtype or model.compute_dtype) == "bf16" \
-            else _lib.IMPALA_DTYPE_F32
+        self.bf16 = (dtype or model.compute_dtype) == "bf16"
+        cfg.dtype = _lib.IMPALA_DTYPE_BF16 if self.bf16 else _lib.IMPALA_DTYPE_F32
         cfg.lr, cfg.adam_eps = lr, eps
         cfg.adam_beta1, cfg.adam_beta2 = betas
         cfg.max_grad_norm = max_grad_norm
@@ -168,6 +168,47 @@ class DqnEngine(_lib.NativeHandle):
 
     def train_step(self, obs, actions, targets, probabilities=None) -> torch.Tensor:
         """One learner step; returns the new priorities |err| [N] (device)."""
+        return self._step("dqn_train_step", obs, actions, targets, probabilities)
+
+    def compute_grads(self, obs, actions, targets, probabilities=None) -> torch.Tensor:
+        """``train_step`` without clip and Adam (``dqn_compute_grads``): the pre-clip gradient in
+        ``model.flat_grad`` and metrics q / target / priorities / loss; returns the priorities."""
+        return self._step("dqn_compute_grads", obs, actions, targets, probabilities)
+
+    # name -> (IMPALA_DBG_* id, element kind, shape of one frame): Engine.DEBUG_TENSORS with the
+    # projection HIDDEN wide
+    DEBUG_TENSORS = {
+        "act1": (0, "T", (15, 15, 32)), "act2": (1, "T", (6, 6, 64)), "act3": (2, "T", (1024,)),
+        "y": (3, "T", (1024,)), "h": (4, "T", (HIDDEN,)), "dz": (5, "T", (HIDDEN,)),
+        "dact3": (6, "T", (1024,)), "dact2": (7, "T", (6, 6, 64)), "mask1": (8, "u32", (225,)),
+        "lnstat": (9, "f32", (2,)), "zg": (10, "f32", (HIDDEN,)), "heads": (11, "f32", (16,)),
+        "dy": (12, "f32", (1024,)),
+    }
+
+    def debug_tensor(self, name: str, frames: Optional[int] = None, target: bool = False):
+        """``Engine.debug_tensor`` on this handle (``dqn_debug_read``; a host sync): the workspace
+        tensor ``name`` as the last forward, act or step left it, a numpy array [frames, ...] in
+        ``Engine.debug_tensor``'s layouts with h / dz / zg 512 wide.  The one workspace holds the
+        net that ran last; ``target`` matters for "heads" alone, which then reads the target
+        net's own buffer.  The step keeps its heads in LDS: "heads" is a forward's or act's."""
+        if name not in self.DEBUG_TENSORS:
+            raise ValueError(f"unknown debug tensor {name!r}: one of {sorted(self.DEBUG_TENSORS)}")
+        which, kind, shape = self.DEBUG_TENSORS[name]
+        n = self.N if frames is None else int(frames)
+        if not 1 <= n <= self.N:
+            raise ValueError(f"frames must be in [1, {self.N}]")
+        dt = {"T": torch.bfloat16 if self.bf16 else torch.float32, "f32": torch.float32,
+              "u32": torch.int32}[kind]
+        buf = torch.empty((n,) + shape, dtype=dt, device=self.device)
+        check(lib().dqn_debug_read(self._h, 1 if target else 0, which, _lib.ptr(buf),
+                                   buf.numel() * buf.element_size(), _lib.stream_ptr(None)),
+              "dqn_debug_read", _ERR)
+        torch.cuda.current_stream().synchronize()
+        if kind == "u32":
+            return buf.cpu().numpy().view(np.uint32)
+        return buf.float().cpu().numpy()
+
+    def _step(self, entry: str, obs, actions, targets, probabilities) -> torch.Tensor:
         self._fresh()
         if obs.shape[0] != self.N:
             raise ValueError(f"batch of {obs.shape[0]} transitions on a handle of {self.N}")
@@ -178,7 +219,7 @@ class DqnEngine(_lib.NativeHandle):
                     self.device, torch.float32)]
         b = _lib.DqnBatch(_lib.ptr(keep[0]), _lib.ptr(keep[1]), _lib.ptr(keep[2]), _lib.ptr(keep[3]),
                           _lib.ptr(prio))
-        check(lib().dqn_train_step(self._h, C.byref(b), _lib.stream_ptr(None)), "dqn_train_step", _ERR)
+        check(getattr(lib(), entry)(self._h, C.byref(b), _lib.stream_ptr(None)), entry, _ERR)
         return prio
 
     def train_step_replay(self, replay: "NativePrioritizedReplay", seed: int, counter: int):

@@ -116,6 +116,18 @@ int dqn_act(dqn_learner* h, const uint8_t* obs, int n, const float* eps, float e
             int64_t* greedy, void* stream);
 
 int dqn_train_step(dqn_learner* h, const dqn_batch* batch, void* stream);
+/* dqn_train_step without clip and Adam: the pre-clip gradient in the bound grads, the priorities
+ * and metrics q / target / priorities / loss; the parameters, the Adam state and the metrics
+ * grad_norm / step stay as they are.  (dqn_train_step leaves the CLIPPED gradient in grads: the
+ * Adam kernel writes g * min(1, max_grad_norm / norm) back.) */
+int dqn_compute_grads(dqn_learner* h, const dqn_batch* batch, void* stream);
+
+/* Test / inspection entry: impala_debug_read on the DQN handle's workspace, as the last forward,
+ * act or step left it -- the IMPALA_DBG_* ids and layouts, h / dz / zg DQN_HIDDEN wide.  The one
+ * workspace serves both nets (it holds the net that ran last); net = 1 differs from net = 0 only
+ * for IMPALA_DBG_HEADS, which then reads the target net's own heads buffer.  The step keeps its
+ * heads in LDS: IMPALA_DBG_HEADS holds what the last dqn_forward / dqn_act wrote. */
+int dqn_debug_read(dqn_learner* h, int net, int which, void* dst, size_t bytes, void* stream);
 
 /* The loss alone on adv [N][A], v [N]: d loss / d adv [N][A], d loss / d v [N], the new
  * priorities [N] and metrics4 = {q, target, priorities, loss}.  probabilities may be NULL.

@@ -28,6 +28,10 @@ kernels:
   conv1 bwd  d b1 = sum of the UNROUNDED fp32 dY1 (conv1.h: bsum adds v before the bf16 store);
              d w1 = q(dY1)^T image bytes * (1/255).
 
+The Ape-X DQN step (algo="dqn": the dueling net, the projection 512 wide) runs the same stages
+around its own head, ``dqn_head``; its step kernel keeps the heads in LDS (dqn_head_step.h), so
+that stage reads the exported h.
+
 In the bf16 mode every weight is RNE_bf16(master fp32) (kernels.h pack_params, ``(T)p``); biases,
 LayerNorm gamma / beta and the statistics stay fp32.  ``quant=False`` switches every rounding off
 (the fp32 mode, and the chain identity against ref_cpu).
@@ -70,15 +74,21 @@ def ulp_bf16(r: np.ndarray) -> np.ndarray:
     return np.where(r == 0, 0.0, np.ldexp(1.0, np.maximum(e - 1, -126) - 7))
 
 
-def block_shapes(A: int):
+def block_shapes(A: int, algo: str = "impala"):
+    """(block name, shape) of the 14 canonical blocks: the IMPALA / PPO net's, or -- algo "dqn" --
+    the dueling net's (impala_amd.dqn.net_specs: the same order, the projection 512 wide, the
+    advantage head in the actor's place and the value head in the critic's)."""
+    if algo == "dqn":
+        from impala_amd.dqn import net_specs
+        return [(n, s) for n, (_, s) in zip(BLOCKS, net_specs(A))]
     return [(n, (A,) + s[1:] if k.startswith("model.actor") else s)
             for n, (k, s) in zip(BLOCKS, ref_cpu.PARAM_SPECS)]
 
 
-def split_flat(flat, A: int) -> Dict[str, np.ndarray]:
+def split_flat(flat, A: int, algo: str = "impala") -> Dict[str, np.ndarray]:
     """A flat parameter / gradient vector -> its 14 canonical blocks."""
     out, off = {}, 0
-    for n, s in block_shapes(A):
+    for n, s in block_shapes(A, algo):
         k = int(np.prod(s))
         out[n] = np.asarray(flat[off:off + k]).reshape(s)
         off += k
@@ -89,19 +99,22 @@ def split_flat(flat, A: int) -> Dict[str, np.ndarray]:
 class Weights:
     """The weights as the kernels see them: conv / FC / head weights rounded to bf16 when
     ``quant``, the vectors fp32; the 1024-feature axes in the export order p*64+c; the heads as
-    one [16][256] matrix (rows 0..A-1 actor, row 15 critic)."""
+    one [16][hid] matrix (rows 0..A-1 actor / advantage, row 15 critic / value).  ``hid``: the
+    projection's width, 256 (the IMPALA / PPO net) or 512 (the dueling net, algo "dqn")."""
 
-    def __init__(self, flat, A: int, quant: bool, dtype=torch.float64):
+    def __init__(self, flat, A: int, quant: bool, dtype=torch.float64, hid: int = 256,
+                 algo: str = "impala"):
         src = np.asarray(flat, np.float32 if quant else np.float64)  # (the master weights are fp32)
         b = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dtype)
-             for k, v in split_flat(src, A).items()}
+             for k, v in split_flat(src, A, algo).items()}
+        assert b["wfc"].shape[0] == hid, (b["wfc"].shape, hid)
         q = rne_bf16 if quant else (lambda t: t)
-        self.A = A
+        self.A, self.hid = A, hid
         self.w1, self.w2, self.w3 = q(b["w1"]), q(b["w2"]), q(b["w3"])
         self.b1, self.b2, self.b3 = b["b1"], b["b2"], b["b3"]
         self.lng, self.lnb = b["lng"][_PERM], b["lnb"][_PERM]
         self.wfc, self.bfc = q(b["wfc"])[:, _PERM], b["bfc"]
-        self.wh = torch.zeros(16, 256, dtype=dtype)
+        self.wh = torch.zeros(16, hid, dtype=dtype)
         self.wh[:A], self.wh[VCOL] = q(b["wa"]), q(b["wc"])[0]
         self.bh = torch.zeros(16, dtype=dtype)
         self.bh[:A], self.bh[VCOL] = b["ba"], b["bc"][0]
@@ -194,6 +207,53 @@ def ppo_head(heads, batch, A: int, dtype=torch.float64, entropy_coeff: float = 0
     return dH, {k.split("/")[1]: float(x) for k, x in met.items()}
 
 
+def dqn_head(h, batch, A: int, W: Weights, beta: float = 0.4, dtype=torch.float64, err_abs=None,
+             mean_rows: Optional[int] = None, pnorm=None):
+    """The Ape-X loss on the exported h [N,512] (dqn_head_step.h phases 1 and 2; the step kernel
+    keeps its heads in LDS, so they are formed here: heads = wh h + bh in ``dtype``):
+      q = (v + adv_a) - mean_{k<A} adv_k;  err = target - q;  w = p^-beta / (min p)^-beta (1
+      without probabilities; beta as the kernel holds it, a float32);  dq = -err w / N;
+      dH[k<A] = [k = a] dq - dq / A, dH[15] = dq, rows A..14 zero.
+    ``err_abs`` [N]: the step's own priorities |err| (the kernel stores fabsf(err)); dH then is
+    built from that magnitude under the reference's sign.  q, the metrics and the returned
+    priorities are always the reference's own.
+    ``mean_rows`` / ``pnorm``: a number of rows to average over instead of A, a probability to
+    normalise by instead of min p (defects for the sensitivity tests).
+    -> (dH [N,16] unrounded, metrics q / target / priorities / loss (means; loss = 1/2 mean err^2
+    w) and q_abs = mean |q_a| (the scale of q's normwise bound), {"q": q_a [N], "prio": |err|
+    [N], "w": [N]} in ``dtype``)."""
+    _, act, tgt, prob = batch
+    h = torch.from_numpy(np.ascontiguousarray(h, dtype=np.float64)).to(dtype) \
+        if not torch.is_tensor(h) else h.to(dtype)
+    N = h.shape[0]
+    hd = heads_fwd(h, W)
+    a = torch.from_numpy(np.asarray(act, np.int64)).reshape(-1)
+    adv_a = hd[:, :A].gather(1, a[:, None])[:, 0]
+    R = mean_rows or A
+    q = (hd[:, VCOL] + adv_a) - hd[:, :R].sum(1) / R
+    t = torch.from_numpy(np.asarray(tgt, np.float32)).reshape(-1).to(dtype)
+    err0 = err = t - q  # (the metrics and the returned priorities are the reference's own)
+    if err_abs is not None:
+        mag = torch.from_numpy(np.asarray(err_abs, np.float64)).reshape(-1).to(dtype)
+        err = torch.where(err0 < 0, -mag, mag)
+    if prob is None:
+        w = torch.ones_like(q)
+    else:
+        p = torch.from_numpy(np.asarray(prob, np.float32)).reshape(-1).to(dtype)
+        b = torch.tensor(float(np.float32(beta)), dtype=dtype)
+        pn = p.min() if pnorm is None else torch.as_tensor(float(pnorm), dtype=dtype)
+        w = p.pow(-b) / pn.pow(-b)
+    dq = -(err * w) / N
+    dH = torch.zeros(N, 16, dtype=dtype)
+    dH[:, :A] = (-dq / A)[:, None]
+    dH[torch.arange(N), a] += dq
+    dH[:, VCOL] = dq
+    met = {"q": float(q.mean()), "target": float(t.mean()), "priorities": float(err0.abs().mean()),
+           "loss": float(0.5 * (err0 * err0 * w).mean()), "q_abs": float(q.abs().mean())}
+    return dH, met, {"q": q.double().numpy(), "prio": err0.abs().double().numpy(),
+                     "w": w.double().numpy()}
+
+
 # ------------------------------------------------------------------------------- backward
 def head_bwd(qdH, zg, h, W: Weights):
     """q(dH) [N,16], zg, h [N,256] -> (dz unrounded, d wh [16,256], d bh [16])."""
@@ -245,6 +305,13 @@ def conv1_bwd(dY1, qdY1, obs_u8, W: Weights):
     return dw * (1.0 / 255.0), dY1.sum((0, 1, 2))
 
 
+def _head_grads(g: Dict[str, torch.Tensor], A: int) -> Dict[str, np.ndarray]:
+    """(d wh [16,hid], d bh [16]) -> the four canonical head blocks."""
+    return {"wa": g["wh"][:A].double().numpy(), "ba": g["bh"][:A].double().numpy(),
+            "wc": g["wh"][VCOL:VCOL + 1].double().numpy(),
+            "bc": g["bh"][VCOL:VCOL + 1].double().numpy()}
+
+
 def _canon_grads(g: Dict[str, torch.Tensor], A: int) -> Dict[str, np.ndarray]:
     """Stage gradients (export order) -> the 14 canonical blocks."""
     inv = torch.empty_like(_PERM)
@@ -257,15 +324,26 @@ def _canon_grads(g: Dict[str, torch.Tensor], A: int) -> Dict[str, np.ndarray]:
 
 
 def run(flat, batch, A: int, given: Optional[dict] = None, quant: bool = True,
-        dtype=torch.float64, algo: str = "impala", forward_only: bool = False) -> dict:
+        dtype=torch.float64, algo: str = "impala", forward_only: bool = False,
+        hid: int = 256, beta: float = 0.4, head_only: bool = False) -> dict:
     """Every stage of one step.  ``given`` = the tensors of a real step (teacher forcing: each
     stage reads ITS inputs from there, so the outputs are references for that step's tensors);
     None chains the stages on their own outputs, rounded to bf16 where the kernels round when
     ``quant`` (dtype float32: the CPU stand-in of the bf16 kernels; quant False, float64: the
     network itself).  -> {"t": name -> tensor before rounding (numpy float64), "grads": the 14
     canonical blocks, "met": metrics, "mask1": uint32}.  ``given`` may also carry "dY1" (an
-    unrounded conv2 input gradient to round and use instead of the run's own)."""
-    W = Weights(flat, A, quant, dtype)
+    unrounded conv2 input gradient to round and use instead of the run's own).
+
+    ``algo="dqn"``: the dueling net (``hid`` 512 whatever is passed; blocks of
+    impala_amd.dqn.net_specs), batch = (obs, act, target, prob-or-None), the head stage
+    ``dqn_head`` with importance exponent ``beta``; ``given`` may carry "prio", the step's own
+    priorities (dqn_head's ``err_abs``), and "qdH", a rounded dH to use instead of the run's own.
+    The output also has "prio" [N] and "q" [N] (q_a).  ``head_only``: with ``given``, the head
+    stage and its backward alone ("t" holds heads, dH, dz; "grads" the four head blocks)."""
+    dqn = algo == "dqn"
+    if dqn:
+        hid = 512
+    W = Weights(flat, A, quant, dtype, hid, "dqn" if dqn else "impala")
     q = rne_bf16 if quant else (lambda t: t)
     t: Dict[str, torch.Tensor] = {}
 
@@ -275,20 +353,36 @@ def run(flat, batch, A: int, given: Optional[dict] = None, quant: bool = True,
         return q(t[name]) if name in T_TENSORS or name in ("dH", "dY1") else t[name]
 
     obs = torch.from_numpy(np.ascontiguousarray(batch[0])).reshape(-1, 3, 64, 64)
+    out = {}
+    if not (head_only and given is not None):
+        with torch.no_grad():
+            t["act1"] = conv1_fwd(obs, W)
+            t["act2"] = conv2_fwd(inp("act1"), W)
+            t["act3"], t["lnstat"], t["y"] = conv3_ln_fwd(inp("act2"), W)
+            t["zg"], t["h"] = fc_fwd(inp("y"), W)
+        out["mask1"] = mask_bits(inp("act1").numpy())
     with torch.no_grad():
-        t["act1"] = conv1_fwd(obs, W)
-        t["act2"] = conv2_fwd(inp("act1"), W)
-        t["act3"], t["lnstat"], t["y"] = conv3_ln_fwd(inp("act2"), W)
-        t["zg"], t["h"] = fc_fwd(inp("y"), W)
         t["heads"] = heads_fwd(inp("h"), W)
-    out = {"mask1": mask_bits(inp("act1").numpy())}
     if not forward_only:
-        head = impala_head if algo == "impala" else ppo_head
-        t["dH"], out["met"] = head(inp("heads").double().numpy(), batch, A, dtype=dtype)
+        if dqn:
+            with torch.no_grad():
+                t["dH"], out["met"], x = dqn_head(
+                    inp("h"), batch, A, W, beta, dtype,
+                    err_abs=None if given is None else given.get("prio"))
+            out["prio"], out["q"] = x["prio"], x["q"]
+        else:
+            head = impala_head if algo == "impala" else ppo_head
+            t["dH"], out["met"] = head(inp("heads").double().numpy(), batch, A, dtype=dtype)
         with torch.no_grad():
             qdH = q(t["dH"])  # (never exported: always the run's own)
+            if given is not None and "qdH" in given:
+                qdH = torch.from_numpy(np.asarray(given["qdH"], np.float64)).to(dtype)
             g = {}
             t["dz"], g["wh"], g["bh"] = head_bwd(qdH, inp("zg"), inp("h"), W)
+            if head_only:
+                out["grads"] = _head_grads(g, A)
+                out["t"] = {k: v.double().numpy() for k, v in t.items()}
+                return out
             t["dy"], g["wfc"], g["bfc"] = fc_bwd(inp("dz"), inp("y"), W)
             t["dact3"], g["lng"], g["lnb"] = ln_bwd(inp("dy"), inp("act3"), inp("lnstat"), W)
             t["dact2"], g["w3"], g["b3"] = conv3_bwd(inp("dact3"), inp("act2"), W)

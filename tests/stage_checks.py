@@ -24,6 +24,10 @@ Bounds (r = the float64 reference of a stage's output on the step's own inputs):
                 so they keep 1e-4.
   metrics       1e-5 relative from the exported heads; train/pg normwise, |d| <= 1e-5 (|pg| +
                 mean |log pi(a) adv|).
+
+The Ape-X DQN step (tests/test_gpu_dqn_stages.py) is held to the same bounds; its cases, the
+priorities' and q's bounds and the handling of an undecided rounding of dH are in the last
+section below.
 """
 import numpy as np
 import torch
@@ -50,7 +54,9 @@ _INPUTS = {}
 def inputs(shape):
     """(flat0, batch) of a case: ("ppo",), ("fwd",) or (B, T)."""
     if shape not in _INPUTS:
-        if shape == ("ppo",):
+        if shape[0] in ("dqn", "dqn_fwd"):
+            v = _dqn_inputs(shape)
+        elif shape == ("ppo",):
             v = (ref_cpu.flat_params(ref_cpu.make_model(0, PPO_A)),
                  ref_cpu.synthetic_ppo_batch(PPO_N, PPO_A))
         elif shape == ("fwd",):  # one frame (a T = 1 rollout): the forward stages alone
@@ -65,6 +71,10 @@ def inputs(shape):
 
 
 def case_kw(shape):
+    if shape[0] == "dqn":
+        return dict(A=shape[2], algo="dqn", beta=DQN_BETA, head_only=shape == DQN_HEAD)
+    if shape[0] == "dqn_fwd":
+        return dict(A=DQN_FWD_A, algo="dqn", forward_only=True)
     if shape == ("ppo",):
         return dict(A=PPO_A, algo="ppo")
     if shape == ("fwd",):
@@ -96,7 +106,10 @@ def stand_in(shape, quant=True):
     if (shape, quant) not in _STAND_IN:
         flat0, batch = inputs(shape)
         s = rs.run(flat0, batch, quant=quant, dtype=torch.float32, **case_kw(shape))
-        _STAND_IN[(shape, quant)] = (s, rs.stand_in_tensors(s, quant))
+        S = rs.stand_in_tensors(s, quant)
+        if "prio" in s:  # (the DQN step's priorities: what the kernel would write, a float32)
+            S["prio"] = s["prio"]
+        _STAND_IN[(shape, quant)] = (s, S)
     return _STAND_IN[(shape, quant)]
 
 
@@ -168,3 +181,218 @@ def hold_metrics(got, ref, label):
             bad.append(f"metric {k}: {v:.2e}")
     print(f"{label} metrics rel: " + ", ".join(line))
     return bad
+
+
+# ------------------------------------------------------------------------------ Ape-X DQN
+# The dueling net's step (tests/test_gpu_dqn_stages.py; the module docstring there has the
+# bounds' sources).  A case is ("dqn", N, A, probabilities?) or ("dqn_fwd", frames, target net?).
+DQN_CASES = [("dqn", 1, 15, True), ("dqn", 1, 1, False), ("dqn", 32, 6, True),
+             ("dqn", 33, 2, False), ("dqn", 33, 15, True), ("dqn", 65, 6, False),
+             ("dqn", 100, 15, True)]
+DQN_HEAD = ("dqn", 1030, 15, True)  # the head stage alone; min p at index 1029
+DQN_FWD_FRAMES, DQN_FWD_A = 8, 6
+DQN_FWD_CASES = [("dqn_fwd", n, t) for n in (1, 5) for t in (False, True)]
+DQN_BETA = 0.4
+DQN_STEP_TENSORS = tuple(k for k in rs.T_TENSORS + rs.F32_TENSORS if k != "heads")
+DQN_HEAD_BLOCKS = ("wa", "ba", "wc", "bc")
+DQN_MET_NAMES = ("q", "target", "priorities", "loss")
+PRIO_NORMWISE = 1e-5
+GRAD_NORM_RTOL = 1e-4
+MAX_UNDECIDED = 4
+# u = 2^-24, the unit roundoff of fp32.  With err pinned, the kernel's dq = -(err w) (1 / N) takes:
+# two powf (<= 1 ulp = 2u each: the HIP programming guide's table of device math functions lists
+# powf at 1 ULP, and nothing is compiled with fast-math) and their quotient (u): w within 5u;
+# err w (u); fl(1 / N) (u) and the product with it (u): dq within 8u |dq| to first order.  da =
+# fl(-dq / A) adds u: within 9u |da|; dq + da adds u |dq + da|.  With one u each for the
+# second-order terms, the margins of the three numbers of a row:
+#   dq: 9u |dq|     da: 10u |da|     dq + da: 9u |dq| + 10u |da| + u |dq + da|
+DQN_U = 2.0 ** -24
+
+
+def dqn_margins(dH, act, A):
+    """-> the margin of every element of dH [N,16] (above), zero where dH is zero."""
+    dH = np.asarray(dH, np.float64)
+    dq = np.abs(dH[:, rs.VCOL])
+    da = dq / A
+    m = np.zeros_like(dH)
+    m[:, :A] = (10 * DQN_U * da)[:, None]
+    n = np.arange(dH.shape[0])
+    a = np.asarray(act).reshape(-1)
+    m[n, a] = DQN_U * (9 * dq + 10 * da + np.abs(dH[n, a]))
+    m[:, rs.VCOL] = 9 * DQN_U * dq
+    return np.where(dH == 0, 0.0, m)
+
+
+# the batch seed of a DQN case (100 N + A, test_gpu_dqn.py's, unless the stand-in's share of
+# elements != RNE exceeded STAND_IN_CAP for a tensor there, or an element of its dH was undecided:
+# none did; the largest share is 2.4e-4, h at N = 33, A = 15)
+DQN_SEEDS = {}
+
+
+def _dqn_flat(A):
+    """The dueling net's seed-0 initialisation with every bias and the LayerNorm affine moved off
+    0 / 1 (a stage that dropped one could not pass) -> (online, nudged target), float32."""
+    import torch
+    from impala_amd.dqn import AtariDQNModel
+    with torch.random.fork_rng(devices=[]):
+        flat = AtariDQNModel((3, 64, 64), A, device="cpu", seed=0).flat.numpy().copy()
+    rng = np.random.default_rng(3)
+    off = 0
+    for n, s in rs.block_shapes(A, "dqn"):
+        k = int(np.prod(s))
+        if len(s) == 1:
+            flat[off:off + k] += (0.02 * rng.standard_normal(k)).astype(np.float32)
+        off += k
+    target = flat + (0.01 * rng.standard_normal(flat.size)).astype(np.float32)
+    return flat, target
+
+
+_DQN_FLAT = {}
+
+
+def _dqn_inputs(shape):
+    import dqn_oracle as orc
+    A = DQN_FWD_A if shape[0] == "dqn_fwd" else shape[2]
+    if A not in _DQN_FLAT:
+        _DQN_FLAT[A] = _dqn_flat(A)
+    online, target = _DQN_FLAT[A]
+    if shape[0] == "dqn_fwd":
+        _, n, tgt = shape
+        obs = np.random.default_rng(77).integers(0, 256, size=(DQN_FWD_FRAMES, 3, 64, 64), dtype=np.uint8)
+        return (target if tgt else online), (obs[:n],)
+    _, N, A, probs = shape
+    obs, act, tgt, p = orc.synthetic_batch(N, A, seed=DQN_SEEDS.get(shape, 100 * N + A), probs=probs)
+    if shape == DQN_HEAD:  # the batch minimum where only the second pass of the loop sees it
+        p = p.copy()
+        p[N - 1] = np.float32(0.5) * p.min()
+    return online, (obs, act, tgt, p)
+
+
+def dqn_target_flat(A=DQN_FWD_A):
+    if A not in _DQN_FLAT:
+        _DQN_FLAT[A] = _dqn_flat(A)
+    return _DQN_FLAT[A][1]
+
+
+def dqn_undecided(dH, act, A):
+    """The rounding decisions of dH that fp32 cannot be trusted with: a row holds three distinct
+    numbers -- dq (column 15), da = -dq / A (the A - 1 columns k != a: one fp32 value stored A - 1
+    times, one decision) and dq + da (column a) -- and one of them is undecided when its float64
+    value lies within its margin (dqn_margins) of a bf16 rounding boundary, i.e. when the two
+    ends of that interval round differently.  -> [(row, columns, lower rounding, upper rounding)]"""
+    import torch
+    dH = np.asarray(dH, np.float64)
+    act = np.asarray(act).reshape(-1)
+    m = dqn_margins(dH, act, A)
+    lo = rs.rne_bf16(torch.from_numpy(dH - m)).numpy()
+    hi = rs.rne_bf16(torch.from_numpy(dH + m)).numpy()
+    out = []
+    for n in np.nonzero((lo != hi).any(1))[0]:
+        a = int(act[n])
+        groups = [[rs.VCOL], [a]] + ([[k for k in range(A) if k != a]] if A > 1 else [])
+        for cols in groups:
+            c = cols[0]
+            if dH[n, c] != 0 and lo[n, c] != hi[n, c]:
+                out.append((int(n), cols, float(lo[n, c]), float(hi[n, c])))
+    return out
+
+
+def dqn_head_assignments(dH, act, A):
+    """-> (the undecided decisions, the rounded dH of every assignment of them: the reference's
+    own rounding first).  More than MAX_UNDECIDED decisions: no assignments."""
+    import itertools
+    import torch
+    und = dqn_undecided(dH, act, A)
+    base = rs.rne_bf16(torch.from_numpy(np.asarray(dH, np.float64))).numpy()
+    if len(und) > MAX_UNDECIDED:
+        return und, []
+    out = []
+    for pick in itertools.product((0, 1), repeat=len(und)):
+        q = base.copy()
+        for (n, cols, lo, hi), b in zip(und, pick):
+            q[n, cols] = hi if b else lo
+        out.append(q)
+    out.sort(key=lambda q: not np.array_equal(q, base))
+    return und, out
+
+
+def _head_holds(got, blocks, r, quant, A):
+    """dz and the four head blocks against one head-only reference, without printing."""
+    g = np.asarray(got["dz"], np.float64)
+    if quant:
+        worst, share, _ = rs.bf16_figures(g, r["t"]["dz"])
+        ok = worst <= 1.0 and share <= CAP
+    else:
+        ok = rs.f32_figures(g, r["t"]["dz"]) <= F32_NORMWISE
+    return ok and all(rs.rel_l2(blocks[k], r["grads"][k]) <= BLOCK_RL2 for k in DQN_HEAD_BLOCKS)
+
+
+def dqn_resolve_head(shape, got, blocks, ref, quant, label):
+    """The head stage's hazard (test_gpu_dqn_stages.py): dz, d wh and d bh hang on the bf16
+    rounding of dH, which the kernel takes from fp32 values.  For every assignment of the
+    undecided decisions (at most MAX_UNDECIDED, else the case fails) the head-only reference is
+    evaluated with that rounded dH; the first under which dz, wa, ba, wc and bc hold TOGETHER
+    replaces the reference's own.  -> (ref with dz and the head blocks of the chosen assignment,
+    violations).  Nothing is widened: with no such assignment the reference stays as it was and
+    the ordinary checks report what fails."""
+    if not quant:
+        return ref, []
+    flat0, batch = inputs(shape)
+    A = shape[2]
+    und, cands = dqn_head_assignments(ref["t"]["dH"], batch[1], A)
+    print(f"{label} dH: {len(und)} undecided rounding decisions (row, column, lower, upper) "
+          f"{[(n, cols[0], lo, hi) for n, cols, lo, hi in und[:8]]}")
+    if not cands:
+        return ref, [f"dH: {len(und)} undecided rounding decisions > {MAX_UNDECIDED}"]
+    for i, qdH in enumerate(cands):
+        if i == 0 and "dz" in ref["t"] and len(cands) == 1:
+            return ref, []  # (nothing undecided: the reference's own rounding is the only one)
+        kw = dict(case_kw(shape), head_only=True)
+        r = rs.run(flat0, batch, given=dict(got, qdH=qdH), quant=True, **kw)
+        if _head_holds(got, blocks, r, quant, A):
+            print(f"{label} dH: assignment {i} of {len(cands)} holds dz and the head blocks together")
+            out = dict(ref, t=dict(ref["t"], dz=r["t"]["dz"]), grads=dict(ref["grads"]))
+            out["grads"].update({k: r["grads"][k] for k in DQN_HEAD_BLOCKS})
+            return out, []
+    print(f"{label} dH: no assignment of {len(cands)} holds dz and the head blocks together")
+    return ref, []
+
+
+def hold_dqn_prio(prio, ref, batch, label):
+    """|prio - |target - q_ref|| <= 1e-5 (|q_ref| + rms q_ref + |target|): the heads' normwise
+    bound carried through one subtraction."""
+    q = np.asarray(ref["q"], np.float64)
+    t = np.asarray(batch[2], np.float64).reshape(-1)
+    p = np.asarray(prio, np.float64).reshape(-1)
+    tol = PRIO_NORMWISE * (np.abs(q) + np.sqrt(np.mean(q * q)) + np.abs(t))
+    w = float(np.max(np.abs(p - np.abs(t - q)) / (tol + 1e-300))) if np.isfinite(p).all() else np.inf
+    print(f"{label} prio   worst |d| / (1e-5 (|q| + rms q + |target|)) {w:.3f}")
+    return [f"priorities: bound x{w:.3f}"] if not w <= 1.0 else []
+
+
+def hold_dqn_metrics(got, ref, label):
+    """q normwise against mean |q_a| (as train/pg against pg_abs); target, priorities, loss
+    1e-5 relative."""
+    m = ref["met"]
+    bad, line = [], []
+    for k, g in zip(DQN_MET_NAMES, got):
+        scale = abs(m["q"]) + m["q_abs"] if k == "q" else abs(m[k])
+        v = abs(float(g) - m[k]) / max(scale, 1e-30)
+        line.append(f"{k} {v:.1e}")
+        if not v <= MET_RTOL:
+            bad.append(f"metric {k}: {v:.2e}")
+    print(f"{label} metrics rel: " + ", ".join(line))
+    return bad
+
+
+def hold_dqn_q(q, heads, A, label):
+    """dqn_forward's q [n,A] against the dueling formula on the exported heads: each element
+    within (A + 3) 2^-24 (|v| + |adv_k| + mean |adv|) -- dqn_q_kernel does A + 3 fp32 roundings
+    (A - 1 in the sum, the division, v + adv_k, the subtraction, and one to spare)."""
+    hd = np.asarray(heads, np.float64)
+    adv, v = hd[:, :A], hd[:, rs.VCOL:rs.VCOL + 1]
+    want = (v + adv) - adv.mean(1, keepdims=True)
+    tol = (A + 3) * 2.0 ** -24 * (np.abs(v) + np.abs(adv) + np.abs(adv).mean(1, keepdims=True))
+    w = float(np.max(np.abs(np.asarray(q, np.float64) - want) / (tol + 1e-300)))
+    print(f"{label} q      worst |d| / ((A + 3) 2^-24 (|v| + |adv_k| + mean |adv|)) {w:.3f}")
+    return [f"q: bound x{w:.3f}"] if not w <= 1.0 else []

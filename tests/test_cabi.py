@@ -91,6 +91,8 @@ def test_kernel_entry_points_validate_before_launch():
     assert lib.impala_step_clock_end(None, None, None) == 1001
     # workspace export: likewise
     assert lib.impala_debug_read(None, 0, None, 4, None) == 1001
+    assert lib.dqn_debug_read(None, 0, 0, None, 4, None) == 1001
+    assert lib.dqn_compute_grads(None, None, None) == 1001
 
 
 def test_headers_compile_as_c99(tmp_path):

@@ -10,6 +10,11 @@ checked on the CPU before tests/test_gpu_stages.py holds the kernels to them.
                   most a quarter of the GPU test's cap.
   sensitivity     five defects a kernel could have, applied to the stand-in, each break the check
                   of their stage: the bounds bite.
+
+The same three for the Ape-X DQN step (algo="dqn", tests/test_gpu_dqn_stages.py): the chain
+against tests/dqn_oracle.train_step at A = 15 and A = 1, the stand-in at every GPU case in bf16
+and fp32 (with no undecided rounding of dH at the chosen seeds), six defects of the dueling head
+and the 512-wide FC, and the search over undecided roundings of dH.
 """
 import numpy as np
 import pytest
@@ -152,3 +157,186 @@ def test_defect_head_gradient_left_unrounded():
     assert _fails_tensor("dz", dz, r)
     dz, _, _ = rs.head_bwd(rs.rne_bf16(dH), t["zg"], t["h"], W)
     assert not _fails_tensor("dz", dz, r)
+
+
+# ------------------------------------------------------------------------------ Ape-X DQN
+@pytest.mark.parametrize("A", [15, 1])
+def test_dqn_chain_of_stages_is_the_dueling_net(A):
+    """Rounding off, run(algo="dqn") is tests/dqn_oracle.train_step in float64: the pre-clip
+    gradient, the metrics and the priorities to 1e-10, every bias and the LayerNorm affine away
+    from 0 / 1, at A = 15 and at A = 1 (where the advantage head's gradient is exactly zero)."""
+    import dqn_oracle as orc
+    N = 5
+    obs, act, tgt, p = orc.synthetic_batch(N, A, seed=7, probs=True)
+    flat = sc._dqn_flat(A)[0].astype(np.float64)
+    flat += 0.02 * np.random.default_rng(3).standard_normal(flat.size)
+    beta = float(np.float32(sc.DQN_BETA))  # the exponent as the kernel holds it
+    net = orc.make_net(flat, A, dtype=torch.float64)
+    exp = orc.train_step(net, orc.make_optimizer(net), obs, act, tgt.astype(np.float64),
+                         p.astype(np.float64), beta=beta, max_grad_norm=1e30)  # (no clip)
+    want = rs.split_flat(exp["grads"], A, "dqn")
+    out = rs.run(flat, (obs, act, tgt, p), A, quant=False, algo="dqn", beta=sc.DQN_BETA)
+    for k in rs.BLOCKS:
+        if A == 1 and k == "wa" or A == 1 and k == "ba":
+            assert not np.any(want[k]) and not np.any(out["grads"][k]), k
+        else:
+            assert rs.rel_l2(out["grads"][k], want[k]) <= 1e-10, k
+    for k in sc.DQN_MET_NAMES:
+        assert abs(out["met"][k] - exp[k]) <= 1e-10 * abs(exp[k]), k
+    assert np.max(np.abs(out["prio"] - exp["prio"])) <= 1e-10 * np.max(exp["prio"])
+    norm = np.sqrt(sum(float(np.sum(v * v)) for v in out["grads"].values()))
+    assert abs(norm - exp["grad_norm"]) <= 1e-10 * norm
+
+
+def _check_dqn_stand_in(shape, quant):
+    s, S = sc.stand_in(shape, quant)
+    _, batch = sc.inputs(shape)
+    r = sc.reference(shape, S, quant, key="stand-in" if quant else None)
+    label = f"stand-in {'bf16' if quant else 'fp32'} dqn N={shape[1]} A={shape[2]}"
+    head = shape == sc.DQN_HEAD
+    if quant:
+        und = sc.dqn_undecided(r["t"]["dH"], batch[1], shape[2])
+        assert not und, f"the seed of {shape} leaves undecided roundings of dH: {und}"
+    r, bad = sc.dqn_resolve_head(shape, S, s["grads"], r, quant, label)
+    bad += sc.hold_tensors(S, r, ("dz",) if head else sc.DQN_STEP_TENSORS, quant, label,
+                           cap=sc.STAND_IN_CAP)
+    bounds = {}
+    if not head:
+        bad += sc.hold_mask(s["mask1"], S["act1"], label)
+        if quant:
+            bounds = {"w1": sc.w1_bound(shape)[0]}
+            print(f"{label} w1: reference fed float32- vs float64-accumulated q(dY1) "
+                  f"{sc.w1_bound(shape)[1]:.2e} -> bound {bounds['w1']:.1e}")
+    bad += sc.hold_blocks(s["grads"], r, label, bounds, sc.DQN_HEAD_BLOCKS if head else rs.BLOCKS)
+    bad += sc.hold_dqn_prio(S["prio"], r, batch, label)
+    bad += sc.hold_dqn_metrics([s["met"][k] for k in sc.DQN_MET_NAMES], r, label)
+    assert not bad, bad
+
+
+_dqn_ids = lambda s: "_".join(str(v) for v in s[1:])  # noqa: E731
+
+
+@pytest.mark.parametrize("quant", [True, False], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("shape", sc.DQN_CASES + [sc.DQN_HEAD], ids=_dqn_ids)
+def test_dqn_float32_stand_in_holds_the_bounds_with_a_quarter_of_the_cap(shape, quant):
+    _check_dqn_stand_in(shape, quant)
+
+
+@pytest.mark.parametrize("quant", [True, False], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("shape", sc.DQN_FWD_CASES, ids=_dqn_ids)
+def test_dqn_forward_stand_in_holds_the_bounds_with_a_quarter_of_the_cap(shape, quant):
+    s, S = sc.stand_in(shape, quant)
+    r = sc.reference(shape, S, quant)
+    label = f"stand-in {'bf16' if quant else 'fp32'} dqn forward n={shape[1]} target={shape[2]}"
+    bad = sc.hold_tensors(S, r, rs.FORWARD_TENSORS, quant, label, cap=sc.STAND_IN_CAP)
+    bad += sc.hold_mask(s["mask1"], S["act1"], label)
+    assert not bad, bad
+
+
+def _dqn_sens(shape):
+    flat0, batch = sc.inputs(shape)
+    s, S = sc.stand_in(shape)
+    r = sc.reference(shape, S, True, key="stand-in")
+    W = rs.Weights(flat0, shape[2], True, torch.float32, 512, "dqn")
+    t = {k: torch.from_numpy(np.asarray(v)).float() for k, v in S.items()}
+    return s, S, r, W, t, batch
+
+
+def _dqn_head_defect(shape, **defect):
+    """The stand-in's head stage with a defect -> (violations of the priorities / metrics checks,
+    violations of dz's check)."""
+    s, S, r, W, t, batch = _dqn_sens(shape)
+    dH, met, x = rs.dqn_head(t["h"], batch, shape[2], W, sc.DQN_BETA, torch.float32, **defect)
+    dz, _, _ = rs.head_bwd(rs.rne_bf16(dH), t["zg"], t["h"], W)
+    loss = sc.hold_dqn_prio(x["prio"], r, batch, "defect") + \
+        sc.hold_dqn_metrics([met[k] for k in sc.DQN_MET_NAMES], r, "defect")
+    return loss, _fails_tensor("dz", dz, r)
+
+
+def test_dqn_defect_mean_over_15_rows_instead_of_A():
+    shape = ("dqn", 32, 6, True)
+    loss, dz = _dqn_head_defect(shape, mean_rows=15)
+    assert any(m.startswith("priorities") for m in loss) and any("metric q" in m for m in loss), loss
+    assert dz
+    assert _dqn_head_defect(shape) == ([], False)  # (and the sound one passes)
+
+
+def test_dqn_defect_weights_normalised_by_max_p():
+    shape = ("dqn", 33, 15, True)
+    loss, dz = _dqn_head_defect(shape, pnorm=float(sc.inputs(shape)[1][3].max()))
+    assert any("metric loss" in m for m in loss) and dz, loss
+
+
+def test_dqn_defect_pmin_over_the_first_1024_probabilities():
+    shape = sc.DQN_HEAD
+    p = sc.inputs(shape)[1][3]
+    assert int(np.argmin(p)) == 1029
+    loss, dz = _dqn_head_defect(shape, pnorm=float(p[:1024].min()))
+    assert any("metric loss" in m for m in loss) and dz, loss
+    assert _dqn_head_defect(shape) == ([], False)
+
+
+def test_dqn_defect_row_after_a_ragged_blocks_last_transition_counted():
+    shape = ("dqn", 33, 15, True)  # the second block of 32 holds transition 32 alone
+    s, _, r, W, t, _ = _dqn_sens(shape)
+    qdH = rs.rne_bf16(torch.from_numpy(s["t"]["dH"]).float())
+    _, wh, bh = rs.head_bwd(qdH, t["zg"], t["h"], W)
+    g = rs._head_grads({"wh": wh, "bh": bh}, 15)
+    assert not sc.hold_blocks(g, r, "sound", names=sc.DQN_HEAD_BLOCKS)
+    wh = wh + torch.outer(qdH[32], t["h"][32])  # row 33 of the tile: a copy of the last one
+    g = rs._head_grads({"wh": wh, "bh": bh}, 15)
+    bad = sc.hold_blocks(g, r, "defect", names=("wa", "wc"))
+    assert len(bad) == 2, bad
+
+
+def test_dqn_defect_dz_of_slice_s_times_zg_of_slice_0():
+    shape = ("dqn", 33, 15, True)
+    s, _, r, W, t, _ = _dqn_sens(shape)
+    qdH = rs.rne_bf16(torch.from_numpy(s["t"]["dH"]).float())
+    zg = t["zg"][:, :64].repeat(1, 8)  # every 64-column slice reads slice 0's gelu'
+    dz, _, _ = rs.head_bwd(qdH, zg, t["h"], W)
+    assert _fails_tensor("dz", dz, r)
+    dz, _, _ = rs.head_bwd(qdH, t["zg"], t["h"], W)
+    assert not _fails_tensor("dz", dz, r)
+
+
+def test_dqn_defect_bfc_summed_over_the_first_256_columns():
+    shape = ("dqn", 33, 15, True)
+    _, _, r, W, t, _ = _dqn_sens(shape)
+    _, _, bfc = rs.fc_bwd(t["dz"], t["y"], W)
+    assert not sc.hold_blocks({"bfc": bfc.double().numpy()}, r, "sound", names=("bfc",))
+    bfc[256:] = 0
+    assert sc.hold_blocks({"bfc": bfc.double().numpy()}, r, "defect", names=("bfc",))
+
+
+def test_dqn_undecided_rounding_of_dH_is_resolved_not_tolerated(monkeypatch):
+    """A kernel whose fp32 dH rounded the other way at an undecided element: the reference's own
+    rounding fails the head blocks at N = 1 (the bounds see it), the assignment search finds the
+    kernel's rounding and everything holds under it -- and with more than MAX_UNDECIDED
+    undecided decisions the case fails.  (The margin is widened to make elements undecided.)"""
+    shape = ("dqn", 1, 15, True)
+    s, S, r, W, t, batch = _dqn_sens(shape)
+    monkeypatch.setattr(sc, "DQN_U", 2.0 ** -11)
+    und, cands = sc.dqn_head_assignments(r["t"]["dH"], batch[1], 15)
+    assert 1 <= len(und) <= 3 and len(cands) == 2 ** len(und)
+    qdH = torch.from_numpy(cands[-1]).float()  # every undecided decision at its upper rounding
+    assert not np.array_equal(cands[-1], cands[0])
+    dz, wh, bh = rs.head_bwd(qdH, t["zg"], t["h"], W)
+    got = dict(S, dz=rs.rne_bf16(dz).double().numpy())
+    blocks = rs._head_grads({"wh": wh, "bh": bh}, 15)
+    assert sc.hold_blocks(blocks, r, "other rounding, reference's own", names=sc.DQN_HEAD_BLOCKS)
+    r2, bad = sc.dqn_resolve_head(shape, got, blocks, r, True, "other rounding")
+    assert not bad
+    assert not sc.hold_blocks(blocks, r2, "other rounding, resolved", names=sc.DQN_HEAD_BLOCKS)
+    assert not sc.hold_tensors(got, r2, ("dz",), True, "other rounding, resolved")
+    # a genuinely wrong dH is not rescued: no assignment holds, and the ordinary checks report it
+    dz, wh, bh = rs.head_bwd(qdH * 1.01, t["zg"], t["h"], W)
+    got = dict(S, dz=rs.rne_bf16(dz).double().numpy())
+    blocks = rs._head_grads({"wh": wh, "bh": bh}, 15)
+    r3, bad = sc.dqn_resolve_head(shape, got, blocks, r, True, "wrong dH")
+    assert sc.hold_blocks(blocks, r3, "wrong dH", names=sc.DQN_HEAD_BLOCKS)
+    # too many undecided decisions: the case fails
+    shape = ("dqn", 33, 15, True)
+    s, S, r, W, t, batch = _dqn_sens(shape)
+    _, bad = sc.dqn_resolve_head(shape, S, s["grads"], r, True, "wide margin")
+    assert bad and "undecided" in bad[0], bad
