@@ -89,7 +89,7 @@ DQN_EXPORTS = (
 IQN_EXPORTS = (
     "iqn_abi_version", "iqn_last_error", "iqn_config_default", "iqn_param_count", "iqn_create",
     "iqn_destroy", "iqn_bind_params", "iqn_sync_target", "iqn_refresh_weights", "iqn_forward",
-    "iqn_act", "iqn_nstep_targets", "iqn_loss_head",
+    "iqn_act", "iqn_nstep_targets", "iqn_loss_head", "iqn_debug_read",
 )
 IQN_ABI_VERSION = 1
 IQN_MAX_TAU = 32
@@ -316,6 +316,7 @@ def _declare(lib):
                                       _P, _P]
     lib.iqn_loss_head.argtypes = [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_float, C.c_float, _P, _P, _P, _P, _P]
+    lib.iqn_debug_read.argtypes = [_P, C.c_int, _P, C.c_size_t, _P]
     for name in IQN_EXPORTS:
         getattr(lib, name).restype = (C.c_char_p if name == "iqn_last_error" else
                                       C.c_size_t if name == "iqn_param_count" else C.c_int)

@@ -253,6 +253,32 @@ int iqn_act(iqn_learner* h, const uint8_t* obs, int n, const float* eps, float e
   return 0;
 }
 
+int iqn_debug_read(iqn_learner* h, int which, void* dst, size_t bytes, void* stream) {
+  using namespace net;
+  if (!h || !h->core) return fail(IMPALA_E_INVALID, "null handle");
+  impala_learner* c = h->core;
+  const size_t R = (size_t)h->rows, es = c->bf16 ? 2 : 4;
+  const void* src = nullptr;
+  size_t size = 0;
+  switch (which) {  // the quantile head's rows (the carve-up in iqn_create); the trunk's are the core's
+    case IMPALA_DBG_ACT1:
+    case IMPALA_DBG_ACT2:
+    case IMPALA_DBG_ACT3:
+    case IMPALA_DBG_MASK1: return impala_debug_read(c, which, dst, bytes, stream);
+    case IMPALA_DBG_Y: src = h->work.y; size = R * FLAT * es; break;
+    case IMPALA_DBG_ZG: src = h->work.zg; size = R * HID_DQN * 4; break;
+    case IMPALA_DBG_H: src = h->work.h; size = R * HID_DQN * es; break;
+    case IMPALA_DBG_HEADS: src = h->work.heads; size = R * HEADS * 4; break;
+    default: return fail(IMPALA_E_INVALID, "not a tensor of the IQN forward (act1-3, mask1, y, zg, h, heads)");
+  }
+  if (!dst) return fail(IMPALA_E_INVALID, "null destination");
+  if (bytes == 0 || bytes > size) return fail(IMPALA_E_INVALID, "bytes must be in (0, the tensor's size]");
+  static_assert(YLD == FLAT, "y's rows are exported as they lie: one copy");
+  CK(hipSetDevice(c->device));
+  CK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, (hipStream_t)stream));
+  return 0;
+}
+
 int iqn_nstep_targets(const float* rewards, const uint8_t* done, const float* q_pi, const float* q_star,
                       int64_t L, int W, int n_step, float gamma, float* targets, float* priorities,
                       void* stream) {

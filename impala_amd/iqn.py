@@ -137,8 +137,8 @@ class IqnEngine(_lib.NativeHandle):
         self.N, self.A, self.W = int(batch_size), model.action_dim, model.n_tau_samples
         cfg = default_config()
         cfg.batch_size, cfg.num_actions, cfg.n_tau = self.N, self.A, self.W
-        cfg.dtype = _lib.IMPALA_DTYPE_BF16 if (dtype or model.compute_dtype) == "bf16" \
-            else _lib.IMPALA_DTYPE_F32
+        self.bf16 = (dtype or model.compute_dtype) == "bf16"
+        cfg.dtype = _lib.IMPALA_DTYPE_BF16 if self.bf16 else _lib.IMPALA_DTYPE_F32
         self._open("iqn_create", C.byref(cfg), self.device_index(self.device))
         check(lib().iqn_bind_params(self._h, _lib.ptr(model.flat), _lib.ptr(model.target_flat),
                                     _lib.stream_ptr(None)), "iqn_bind_params", _ERR)
@@ -197,6 +197,37 @@ class IqnEngine(_lib.NativeHandle):
     def sync_target(self) -> None:
         self._fresh()
         check(lib().iqn_sync_target(self._h, _lib.stream_ptr(None)), "iqn_sync_target", _ERR)
+
+    # name -> (IMPALA_DBG_* id, element kind, shape of one row, rows per frame: 1 or W)
+    DEBUG_TENSORS = {
+        "act1": (0, "T", (15, 15, 32), False), "act2": (1, "T", (6, 6, 64), False),
+        "act3": (2, "T", (1024,), False), "mask1": (8, "u32", (225,), False),
+        "y": (3, "T", (1024,), True), "h": (4, "T", (HIDDEN,), True),
+        "zg": (10, "f32", (HIDDEN,), True), "heads": (11, "f32", (16,), True),
+    }
+
+    def debug_tensor(self, name: str, frames: Optional[int] = None):
+        """``DqnEngine.debug_tensor`` on this handle (``iqn_debug_read``; a host sync): the
+        workspace tensor ``name`` as the last forward or act left it, a numpy array in
+        ``Engine.debug_tensor``'s layouts -- act1, act2, act3 (the trunk's features before the
+        modulation) and mask1 per frame [frames, ...]; y, zg, h and heads per quantile row
+        r = f W + k [frames * W, ...], h / zg 512 wide.  The one workspace holds the net that ran
+        last."""
+        if name not in self.DEBUG_TENSORS:
+            raise ValueError(f"unknown debug tensor {name!r}: one of {sorted(self.DEBUG_TENSORS)}")
+        which, kind, shape, per_row = self.DEBUG_TENSORS[name]
+        n = self.N if frames is None else int(frames)
+        if not 1 <= n <= self.N:
+            raise ValueError(f"frames must be in [1, {self.N}]")
+        dt = {"T": torch.bfloat16 if self.bf16 else torch.float32, "f32": torch.float32,
+              "u32": torch.int32}[kind]
+        buf = torch.empty((n * self.W if per_row else n,) + shape, dtype=dt, device=self.device)
+        check(lib().iqn_debug_read(self._h, which, _lib.ptr(buf), buf.numel() * buf.element_size(),
+                                   _lib.stream_ptr(None)), "iqn_debug_read", _ERR)
+        torch.cuda.current_stream().synchronize()
+        if kind == "u32":
+            return buf.cpu().numpy().view(np.uint32)
+        return buf.float().cpu().numpy()
 
 
 class DistributionalAtariDQN(FlatModule):

@@ -119,6 +119,15 @@ int iqn_loss_head(const float* adv, const float* v, const int64_t* actions, cons
                   float huber_param, float beta, float* dadv, float* dv, float* priorities,
                   float* metrics4, void* stream);
 
+/* Test / inspection entry: the workspace tensor `which` (IMPALA_DBG_*, impala_hip.h) as the last
+ * iqn_forward / iqn_act left it, copied to dst (device or host) on `stream`.  act1, act2, act3
+ * and mask1 are the conv trunk's, per frame (impala_debug_read on the handle's core); y, zg, h
+ * and heads are the quantile head's, per row r = f W + k ([R][1024] of the compute type,
+ * [R][512] fp32, [R][512] of the compute type, [R][16] fp32), and `bytes` reads their leading
+ * rows: in (0, batch_size * n_tau rows].  Both nets run through the one workspace: it holds the
+ * net that ran last.  Every other id is refused. */
+int iqn_debug_read(iqn_learner* h, int which, void* dst, size_t bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,8 @@ kernels:
 
 The Ape-X DQN step (algo="dqn": the dueling net, the projection 512 wide) runs the same stages
 around its own head, ``dqn_head``; its step kernel keeps the heads in LDS (dqn_head_step.h), so
-that stage reads the exported h.
+that stage reads the exported h.  The distributional (IQN) actor path's forward (algo="iqn") has a
+section of its own below.
 
 In the bf16 mode every weight is RNE_bf16(master fp32) (kernels.h pack_params, ``(T)p``); biases,
 LayerNorm gamma / beta and the statistics stay fp32.  ``quant=False`` switches every rounding off
@@ -339,7 +340,13 @@ def run(flat, batch, A: int, given: Optional[dict] = None, quant: bool = True,
     ``dqn_head`` with importance exponent ``beta``; ``given`` may carry "prio", the step's own
     priorities (dqn_head's ``err_abs``), and "qdH", a rounded dH to use instead of the run's own.
     The output also has "prio" [N] and "q" [N] (q_a).  ``head_only``: with ``given``, the head
-    stage and its backward alone ("t" holds heads, dH, dz; "grads" the four head blocks)."""
+    stage and its backward alone ("t" holds heads, dH, dz; "grads" the four head blocks).
+
+    ``algo="iqn"``: the distributional actor path's forward (``run_iqn``), batch = (obs, taus);
+    ``head_only``: with ``given``, without the trunk."""
+    if algo == "iqn":
+        return run_iqn(flat, batch, A, given, quant, dtype,
+                       trunk=not (head_only and given is not None))
     dqn = algo == "dqn"
     if dqn:
         hid = 512
@@ -392,6 +399,158 @@ def run(flat, batch, A: int, given: Optional[dict] = None, quant: bool = True,
                 qdY1 = q(torch.from_numpy(np.asarray(given["dY1"], np.float64)).to(dtype))
             g["w1"], g["b1"] = conv1_bwd(t["dY1"], qdY1, obs, W)
         out["grads"] = _canon_grads(g, A)
+    out["t"] = {k: v.double().numpy() for k, v in t.items()}
+    return out
+
+
+# ------------------------------------------------------------------------------- IQN forward
+# The distributional actor path (csrc/iqn.hip; algo="iqn", forward only).  R = n W rows, row
+# r = f W + k.  What each stage reads, from the kernels:
+#   trunk     conv1, conv2 as above; conv3 WITHOUT the LayerNorm: the handle runs the forward in
+#             trunk-only mode, act3 = relu(conv(w3, act2) + b3) rounded is all the head reads.
+#   embed_ln  iqn_embed_ln_kernel: e[r][i] = cos(fl(fl(pi) (i + 1)) tau_r), i = 0..63, the argument
+#             formed in float32 (two roundings, as torch forms torch.pi * embedding_range * tau);
+#             the tile is of the compute type, so e is ROUNDED in the bf16 mode; pre = Wq e + bq
+#             (Wq rounded as packed), phi = erf-GELU(pre), z = act3[r // W] phi, y = LN(z) gamma +
+#             beta with the two-pass variance and eps 1e-5, all fp32; y stored in the compute type.
+#   fc/heads  FcFwd / HeadsFwd (the 512-wide projection's) over the R rows: fc_fwd, heads_fwd.
+#   q         iqn_q_kernel: the dueling formula on the heads (dueling_q).
+IQN_COS = 64
+IQN_HEAD_TENSORS = ("y", "zg", "h", "heads")
+IQN_FORWARD_TENSORS = ("act1", "act2", "act3") + IQN_HEAD_TENSORS
+# The maximum error of the device cosf in fp32 ulps.  ASSUMED: the HIP programming guide's table
+# of device math functions (which the DQN stage test took powf's 1 ULP from) is not at hand; 4 is
+# taken in its place, so the margin of iqn_undecided is 8 fp32 ulps of the cosine.
+COSF_ULPS = 4
+
+
+def iqn_split(flat, A: int):
+    """One IQN net's flat parameters (impala_amd.iqn.net_specs) -> (the dueling net's flat vector
+    without the quantile layer's segment, Wq [1024,64], bq [1024])."""
+    from impala_amd.iqn import net_specs
+    flat = np.asarray(flat)
+    off, parts = 0, {}
+    for k, s in net_specs(A):
+        n = int(np.prod(s))
+        parts[k] = (off, n)
+        off += n
+    assert off == flat.size, (off, flat.size)
+    (ow, nw), (ob, nb) = (parts["q.quantile_layer.output_layer.0." + x] for x in ("weight", "bias"))
+    assert ob == ow + nw
+    return (np.concatenate([flat[:ow], flat[ob + nb:]]), flat[ow:ow + nw].reshape(1024, IQN_COS),
+            flat[ob:ob + nb])
+
+
+class IqnWeights(Weights):
+    """``Weights`` of the dueling net plus the quantile layer's: wq [1024,64] (rounded to bf16
+    when ``quant``: iqn_pack_kernel's ``(T)src``) and bq [1024] fp32, the features in the export
+    order p*64+c (the pack kernel's permutation)."""
+
+    def __init__(self, flat, A: int, quant: bool, dtype=torch.float64):
+        dflat, wq, bq = iqn_split(np.asarray(flat, np.float32 if quant else np.float64), A)
+        super().__init__(dflat, A, quant, dtype, 512, "dqn")
+        wq = torch.from_numpy(np.ascontiguousarray(wq)).to(dtype)
+        self.wq = (rne_bf16(wq) if quant else wq)[_PERM]
+        self.bq = torch.from_numpy(np.ascontiguousarray(bq)).to(dtype)[_PERM]
+
+
+def iqn_cos_arg(taus) -> np.ndarray:
+    """taus [R] -> the cosine's argument [R,64] exactly as the kernel (and torch) form it in
+    float32: fl(fl(fl(pi) i) tau), i = 1..64."""
+    pi_i = np.float32(np.pi) * np.arange(1, IQN_COS + 1, dtype=np.float32)
+    assert pi_i.dtype == np.float32
+    return pi_i[None, :] * np.asarray(taus, np.float32).reshape(-1, 1)
+
+
+def iqn_cos(taus, dtype=torch.float64):
+    """-> e [R,64] unrounded: the cosine of the float32 argument taken in ``dtype``."""
+    return torch.cos(torch.from_numpy(iqn_cos_arg(taus)).to(dtype))
+
+
+def ulp_f32(r: np.ndarray) -> np.ndarray:
+    """2^(floor(log2 |r|) - 23): the spacing of float32 at r (0 at r = 0)."""
+    r = np.asarray(r, np.float64)
+    _, e = np.frexp(r)
+    return np.where(r == 0, 0.0, np.ldexp(1.0, np.maximum(e - 1, -126) - 23))
+
+
+def iqn_undecided(taus):
+    """The elements of the bf16 cosine tile whose rounding the float64 cosine cannot decide: the
+    kernel rounds the device cosf, which may differ from the float64 value c by COSF_ULPS fp32
+    ulps; the margin is twice that, and an element is undecided when c - margin and c + margin
+    round to different bf16.  -> (lower rounding [R,64], upper rounding, mask of the undecided)."""
+    c = np.cos(iqn_cos_arg(taus).astype(np.float64))
+    m = 2 * COSF_ULPS * ulp_f32(c)
+    lo = rne_bf16(torch.from_numpy(c - m)).numpy()
+    hi = rne_bf16(torch.from_numpy(c + m)).numpy()
+    return lo, hi, lo != hi
+
+
+def iqn_embed_ln_rows(x, e, W: "IqnWeights", defect: Optional[str] = None):
+    """x [R,1024] (the frame's act3 of every row), e [R,64] (the cosine tile as the MFMA reads
+    it) -> y [R,1024] unrounded.  ``defect`` (for the sensitivity tests): "tanh_gelu", "no_bq",
+    "raw_second_moment" (the variance without the mean subtracted)."""
+    pre = e @ W.wq.T
+    if defect != "no_bq":
+        pre = pre + W.bq
+    if defect == "tanh_gelu":
+        phi = 0.5 * pre * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (pre + 0.044715 * pre ** 3)))
+    else:
+        phi = 0.5 * pre * (1.0 + torch.erf(pre / math.sqrt(2.0)))
+    z = x * phi
+    mean = z.mean(1, keepdim=True)
+    var = (z * z).mean(1, keepdim=True) if defect == "raw_second_moment" else \
+        ((z - mean) ** 2).mean(1, keepdim=True)
+    return (z - mean) / torch.sqrt(var + LN_EPS) * W.lng + W.lnb
+
+
+def iqn_embed_ln(act3, e, W: "IqnWeights", n_tau: int, defect: Optional[str] = None):
+    """act3 [n,1024] (rounded), e [n n_tau, 64] -> y [R,1024] unrounded: row r reads frame
+    r // n_tau.  ``defect`` "first_frame": every row of a 16-row tile reads the frame of the
+    tile's first row; the others as iqn_embed_ln_rows."""
+    r = torch.arange(e.shape[0])
+    if defect == "first_frame":
+        r = r // 16 * 16
+    return iqn_embed_ln_rows(act3[r // n_tau], e, W, None if defect == "first_frame" else defect)
+
+
+def dueling_q(heads, A: int, mean_cols: Optional[int] = None):
+    """heads [R,16] -> q [R,A] = (v + adv_k) - mean_{k<A} adv (``mean_cols``: columns to average
+    over instead of A, a defect)."""
+    M = mean_cols or A
+    return (heads[:, VCOL:VCOL + 1] + heads[:, :A]) - heads[:, :M].sum(1, keepdim=True) / M
+
+
+def run_iqn(flat, batch, A: int, given: Optional[dict] = None, quant: bool = True,
+            dtype=torch.float64, trunk: bool = True) -> dict:
+    """``run`` for algo "iqn": batch = (obs u8 [n,3,64,64], taus float32 [n,W]); flat = one IQN
+    net's parameters.  ``trunk`` False: the head stages alone, on given["act3"].  -> {"t": the
+    tensors before rounding, "mask1" (with the trunk), "q" [R,A], "e": the unrounded cosine tile}."""
+    obs, taus = batch
+    taus = np.asarray(taus, np.float32)
+    n_tau = taus.shape[1]
+    W = IqnWeights(flat, A, quant, dtype)
+    q = rne_bf16 if quant else (lambda t: t)
+    t: Dict[str, torch.Tensor] = {}
+
+    def inp(name):
+        if given is not None:
+            return torch.from_numpy(np.ascontiguousarray(given[name], dtype=np.float64)).to(dtype)
+        return q(t[name]) if name in T_TENSORS else t[name]
+
+    out = {}
+    with torch.no_grad():
+        if trunk:
+            t["act1"] = conv1_fwd(torch.from_numpy(np.ascontiguousarray(obs)).reshape(-1, 3, 64, 64), W)
+            t["act2"] = conv2_fwd(inp("act1"), W)
+            t["act3"] = conv3_ln_fwd(inp("act2"), W)[0]
+            out["mask1"] = mask_bits(inp("act1").numpy())
+        e = iqn_cos(taus.reshape(-1), dtype)
+        t["y"] = iqn_embed_ln(inp("act3"), q(e), W, n_tau)
+        t["zg"], t["h"] = fc_fwd(inp("y"), W)
+        t["heads"] = heads_fwd(inp("h"), W)
+        out["q"] = dueling_q(inp("heads"), A).double().numpy()
+    out["e"] = e.double().numpy()
     out["t"] = {k: v.double().numpy() for k, v in t.items()}
     return out
 

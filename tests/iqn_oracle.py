@@ -48,18 +48,19 @@ class IqnNet(nn.Module):
         self.q.q = nn.Linear(HIDDEN, A)
         self.q.v = nn.Linear(HIDDEN, 1)
 
-    def heads(self, obs_u8: torch.Tensor, taus: torch.Tensor):
-        """-> adv [n, W, A], v [n, W, 1]."""
+    def heads(self, obs_u8: torch.Tensor, taus: torch.Tensor, arg32: bool = False):
+        """-> adv [n, W, A], v [n, W, 1].  ``arg32``: the cosine's argument formed in float32 (as
+        the reference's own float32 run and the kernel form it), whatever the net's dtype."""
         dt = self.q.v.weight.dtype
         x = self.body.body(obs_u8.to(dt) / 255.)
-        tau = torch.as_tensor(taus).to(dt)
-        e = torch.cos(torch.pi * self.q.quantile_layer.embedding_range * tau.unsqueeze(-1))
+        tau = torch.as_tensor(taus).to(torch.float32 if arg32 else dt)
+        e = torch.cos((torch.pi * self.q.quantile_layer.embedding_range * tau.unsqueeze(-1)).to(dt))
         phi = self.q.quantile_layer.output_layer(e)
         h = self.q.project(x.unsqueeze(1) * phi)
         return self.q.q(h), self.q.v(h)
 
-    def forward(self, obs_u8: torch.Tensor, taus: torch.Tensor) -> torch.Tensor:
-        adv, v = self.heads(obs_u8, taus)
+    def forward(self, obs_u8: torch.Tensor, taus: torch.Tensor, arg32: bool = False) -> torch.Tensor:
+        adv, v = self.heads(obs_u8, taus, arg32)
         return v + adv - adv.mean(dim=-1, keepdim=True)
 
 

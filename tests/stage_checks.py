@@ -26,8 +26,8 @@ Bounds (r = the float64 reference of a stage's output on the step's own inputs):
                 mean |log pi(a) adv|).
 
 The Ape-X DQN step (tests/test_gpu_dqn_stages.py) is held to the same bounds; its cases, the
-priorities' and q's bounds and the handling of an undecided rounding of dH are in the last
-section below.
+priorities' and q's bounds and the handling of an undecided rounding of dH are in the section
+after these; the IQN actor path's forward (tests/test_gpu_iqn_stages.py) is the last section.
 """
 import numpy as np
 import torch
@@ -56,6 +56,8 @@ def inputs(shape):
     if shape not in _INPUTS:
         if shape[0] in ("dqn", "dqn_fwd"):
             v = _dqn_inputs(shape)
+        elif shape[0] == "iqn":
+            v = _iqn_inputs(shape)
         elif shape == ("ppo",):
             v = (ref_cpu.flat_params(ref_cpu.make_model(0, PPO_A)),
                  ref_cpu.synthetic_ppo_batch(PPO_N, PPO_A))
@@ -71,6 +73,8 @@ def inputs(shape):
 
 
 def case_kw(shape):
+    if shape[0] == "iqn":
+        return dict(A=shape[3], algo="iqn", head_only=shape[:4] == IQN_LARGE[:4])
     if shape[0] == "dqn":
         return dict(A=shape[2], algo="dqn", beta=DQN_BETA, head_only=shape == DQN_HEAD)
     if shape[0] == "dqn_fwd":
@@ -396,3 +400,128 @@ def hold_dqn_q(q, heads, A, label):
     w = float(np.max(np.abs(np.asarray(q, np.float64) - want) / (tol + 1e-300)))
     print(f"{label} q      worst |d| / ((A + 3) 2^-24 (|v| + |adv_k| + mean |adv|)) {w:.3f}")
     return [f"q: bound x{w:.3f}"] if not w <= 1.0 else []
+
+
+# ------------------------------------------------------------------------------ IQN forward
+# The distributional actor path's forward (tests/test_gpu_iqn_stages.py; the module docstring there
+# has the cases' reasons).  A case is ("iqn", frames n, quantiles W, A, target net?); the stages and
+# the bounds are those above, y held as a tensor of the compute type over R = n W rows.
+IQN_SMALL = [(1, 1, 2), (3, 8, 6), (2, 5, 15), (1, 32, 15), (5, 32, 15)]
+IQN_CASES = [("iqn",) + s + (t,) for s in IQN_SMALL for t in (False, True)]
+IQN_LARGE = ("iqn", 63, 31, 6, False)  # R = 1953 = 16 * 122 + 1: past the FC's grid cap
+IQN_STALE = (("iqn", 5, 32, 15, False), ("iqn", 1, 32, 15, False))  # the second after the first
+IQN_MAX_UNDECIDED = 3      # undecided elements of one row of the cosine tile
+IQN_LARGE_UNDECIDED = 0.02  # share of the large case's rows that may hold one
+# the seed of a case's taus, iqn_oracle.edge_taus(n, W, seed): the first seed >= n (test_gpu_iqn.py
+# uses n) at which NO element of the bf16 cosine tile is undecided (rs.iqn_undecided: 8 fp32 ulps
+# of margin) and the stand-in's share of elements != RNE stays under STAND_IN_CAP for every
+# tensor; the large case's: the first >= n that leaves at most 1 % of its rows undecided and none
+# with more than IQN_MAX_UNDECIDED elements.  test_ref_stages_host.py asserts all of it.
+# Undecided rows by seed, on the reference alone: (2, 5) seed 2: 1; (1, 32) seeds 1, 2: 1, 3;
+# (5, 32) seeds 5..10: 3, 1, 2, 3, 4, 3; (63, 31) seeds 63, 64: 25, 27 of 1953, seed 65: 16 (0.8 %).
+IQN_TAU_SEEDS = {(1, 1): 1, (3, 8): 3, (2, 5): 3, (1, 32): 3, (5, 32): 11, (63, 31): 65}
+
+_IQN_FLAT = {}
+
+
+def iqn_flats(A):
+    """(online, nudged target) of test_gpu_iqn.py's edge shapes: iqn_oracle.fixture_params, every
+    bias and the LayerNorm affine off 0 / 1."""
+    import iqn_oracle as orc
+    if A not in _IQN_FLAT:
+        online = orc.fixture_params(A, 31 + A)
+        target = (online + 0.05 * (orc.fixture_params(A, 32 + A) - online)).astype(np.float32)
+        _IQN_FLAT[A] = (online, target)
+    return _IQN_FLAT[A]
+
+
+def iqn_taus(n, W):
+    import iqn_oracle as orc
+    return orc.edge_taus(n, W, seed=IQN_TAU_SEEDS[(n, W)])
+
+
+def _iqn_inputs(shape):
+    import iqn_oracle as orc
+    _, n, W, A, tgt = shape
+    return iqn_flats(A)[1 if tgt else 0], (orc.fixture_obs(100 + n, n), iqn_taus(n, W))
+
+
+def iqn_undecided_rows(shape):
+    """-> (lower rounding, upper rounding, mask [R,64]) of the case's cosine tile."""
+    _, n, W, _, _ = shape
+    return rs.iqn_undecided(iqn_taus(n, W).reshape(-1))
+
+
+def _row_holds(g, r, rms):
+    """One row of a bf16 tensor under hold_tensors' two conditions (rms: the whole tensor's)."""
+    d = np.abs(g - r)
+    want = rs.rne_bf16(torch.from_numpy(np.ascontiguousarray(r))).numpy()
+    return bool(np.all(d <= rs.ulp_bf16(r) + 1e-5 * (np.abs(r) + rms)) and np.mean(g != want) <= CAP)
+
+
+def iqn_resolve_embed(shape, got, ref, quant, label):
+    """The embed_ln stage's hazard (test_gpu_iqn_stages.py): the bf16 cosine tile never leaves LDS
+    and its rounding is taken from the device cosf.  Rows are independent in this stage: for a row
+    with undecided elements (at most IQN_MAX_UNDECIDED, else the case fails) the row of y is
+    evaluated under every assignment of them, the reference's own rounding first; the first under
+    which the row holds (_row_holds: hold_tensors' conditions on the row) replaces the
+    reference's row.  -> (ref with those rows of y, violations).  Nothing is widened: a row no
+    assignment holds stays as it was and the ordinary check reports it."""
+    import itertools
+    if not quant:
+        return ref, []
+    flat, (_, taus) = inputs(shape)
+    n_tau = taus.shape[1]
+    lo, hi, und = iqn_undecided_rows(shape)
+    cnt = und.sum(1)
+    rows = np.nonzero(cnt)[0]
+    print(f"{label} cosine tile: {len(rows)} of {len(cnt)} rows hold undecided roundings "
+          f"({int(cnt.sum())} elements, at most {int(cnt.max())} in a row)")
+    bad = []
+    if cnt.max() > IQN_MAX_UNDECIDED:
+        bad.append(f"cosine tile: a row with {int(cnt.max())} undecided elements > {IQN_MAX_UNDECIDED}")
+    if not len(rows):
+        return ref, bad
+    W = rs.IqnWeights(flat, shape[3], True)
+    act3 = torch.from_numpy(np.ascontiguousarray(got["act3"], dtype=np.float64))
+    base = rs.rne_bf16(torch.from_numpy(ref["e"])).numpy()
+    y = ref["t"]["y"].copy()
+    g = np.asarray(got["y"], np.float64).reshape(y.shape)
+    rms = float(np.sqrt(np.mean(y * y)))
+    moved = []
+    for r in rows:
+        idx = np.nonzero(und[r])[0]
+        if len(idx) > IQN_MAX_UNDECIDED:
+            continue
+        cands = []
+        for pick in itertools.product((0, 1), repeat=len(idx)):
+            e = base[r].copy()
+            e[idx] = np.where(np.array(pick, bool), hi[r, idx], lo[r, idx])
+            cands.append(e)
+        cands.sort(key=lambda e: not np.array_equal(e, base[r]))
+        with torch.no_grad():
+            Y = rs.iqn_embed_ln_rows(act3[r // n_tau][None].expand(len(cands), -1),
+                                     torch.from_numpy(np.stack(cands)), W).numpy()
+        for i, yr in enumerate(Y):
+            if _row_holds(g[r], yr, rms):
+                if not np.array_equal(cands[i], base[r]):
+                    y[r] = yr
+                    moved.append(int(r))
+                break
+    print(f"{label} cosine tile: rows held under another assignment than the reference's own: {moved}")
+    return dict(ref, t=dict(ref["t"], y=y)), bad
+
+
+def hold_iqn_forward(shape, got, mask1, q, quant, label, cap=CAP):
+    """Every stage of one IQN forward on its own exports -> violations.  The large case holds the
+    head stages alone (its trunk is not evaluated)."""
+    trunk = shape[:4] != IQN_LARGE[:4]
+    A = shape[3]
+    ref = reference(shape, got, quant)
+    ref, bad = iqn_resolve_embed(shape, got, ref, quant, label)
+    bad += hold_tensors(got, ref, rs.IQN_FORWARD_TENSORS if trunk else rs.IQN_HEAD_TENSORS, quant,
+                        label, cap)
+    if trunk:
+        bad += hold_mask(mask1, got["act1"], label)
+    bad += hold_dqn_q(np.asarray(q).reshape(-1, A), got["heads"], A, label)
+    return bad

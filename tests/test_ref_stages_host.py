@@ -15,6 +15,12 @@ The same three for the Ape-X DQN step (algo="dqn", tests/test_gpu_dqn_stages.py)
 against tests/dqn_oracle.train_step at A = 15 and A = 1, the stand-in at every GPU case in bf16
 and fp32 (with no undecided rounding of dH at the chosen seeds), six defects of the dueling head
 and the 512-wide FC, and the search over undecided roundings of dH.
+
+And for the IQN actor path's forward (algo="iqn", tests/test_gpu_iqn_stages.py): the chain against
+tests/iqn_oracle.make_net in float64 at every small case, the conditions on the taus' seeds (no
+undecided rounding of the bf16 cosine tile at the small cases, at most 1 % of the rows at the
+large one), the stand-in at every case, seven defects, and the row-by-row search over undecided
+roundings of the cosine tile.
 """
 import numpy as np
 import pytest
@@ -340,3 +346,152 @@ def test_dqn_undecided_rounding_of_dH_is_resolved_not_tolerated(monkeypatch):
     s, S, r, W, t, batch = _dqn_sens(shape)
     _, bad = sc.dqn_resolve_head(shape, S, s["grads"], r, True, "wide margin")
     assert bad and "undecided" in bad[0], bad
+
+
+# ------------------------------------------------------------------------------ IQN forward
+_iqn_ids = lambda s: "_".join(str(v) for v in s[1:])  # noqa: E731
+IQN_ALL = sc.IQN_CASES + [sc.IQN_LARGE]
+
+
+@pytest.mark.parametrize("shape", sc.IQN_CASES, ids=_iqn_ids)
+def test_iqn_chain_of_stages_is_the_quantile_net(shape):
+    """Rounding off, run(algo="iqn") in float64 is tests/iqn_oracle.make_net(..., float64) to
+    1e-10 at every small case and both nets, with the cosine's argument formed in float32 in both
+    (``arg32``: the oracle's own float64 run forms the last product in double, the kernel and the
+    reference's float32 run do not).  The argument's rounding moves it by at most 2^-24 of up to
+    64 pi = 201, i.e. 1.2e-5 absolute: q of the two oracles differs by that order, also checked."""
+    import iqn_oracle as orc
+    flat, (obs, taus) = sc.inputs(shape)
+    A = shape[3]
+    out = rs.run(flat.astype(np.float64), (obs, taus), A, quant=False, algo="iqn")
+    net = orc.make_net(flat, A, torch.float64)
+    with torch.no_grad():
+        want = net(torch.from_numpy(obs), torch.from_numpy(taus), arg32=True).numpy().reshape(-1, A)
+        f64 = net(torch.from_numpy(obs), torch.from_numpy(taus)).numpy().reshape(-1, A)
+    err = np.max(np.abs(out["q"] - want)) / np.max(np.abs(want))
+    d = np.max(np.abs(f64 - want)) / np.max(np.abs(want))
+    print(f"{_iqn_ids(shape)} chain vs oracle (float32 argument) {err:.1e}; "
+          f"oracle float64 vs float32 argument {d:.1e}")
+    assert err <= 1e-10
+    assert d <= 1e-4
+
+
+def test_iqn_seeds_leave_no_undecided_cosine_at_the_small_cases_and_few_at_the_large():
+    """On the reference alone: no element of the bf16 cosine tile is undecided at any small case;
+    at the large case at most 1 % of the rows hold one (the GPU test allows 2 %) and no row more
+    than IQN_MAX_UNDECIDED."""
+    for shape in sc.IQN_CASES:
+        _, _, und = sc.iqn_undecided_rows(shape)
+        assert und.shape == (shape[1] * shape[2], rs.IQN_COS)
+        assert not und.any(), (shape, np.argwhere(und))
+    cnt = sc.iqn_undecided_rows(sc.IQN_LARGE)[2].sum(1)
+    print(f"large case: {int((cnt > 0).sum())} of {len(cnt)} rows undecided, at most {int(cnt.max())} in a row")
+    assert len(cnt) == 1953 and 0 < np.mean(cnt > 0) <= 0.01 < sc.IQN_LARGE_UNDECIDED
+    assert cnt.max() <= sc.IQN_MAX_UNDECIDED
+
+
+def test_iqn_edge_taus_hold_the_ends_of_the_interval():
+    top = np.nextafter(np.float32(1), np.float32(0))
+    for shape in IQN_ALL:
+        t = sc.inputs(shape)[1][1].reshape(-1)
+        assert t.dtype == np.float32 and t[0] == 0.0 and t.max() < 1.0
+        assert len(t) == 1 or t[-1] == top
+        assert len(t) <= 2 or t[len(t) // 2] == np.nextafter(top, np.float32(0))
+
+
+def _iqn_stand_in_holds(shape, quant):
+    s, S = sc.stand_in(shape, quant)
+    label = f"stand-in {'bf16' if quant else 'fp32'} iqn {_iqn_ids(shape)}"
+    q = rs.dueling_q(torch.from_numpy(S["heads"]).float(), shape[3]).numpy()
+    return sc.hold_iqn_forward(shape, S, s["mask1"], q, quant, label, cap=sc.STAND_IN_CAP)
+
+
+@pytest.mark.parametrize("quant", [True, False], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("shape", IQN_ALL, ids=_iqn_ids)
+def test_iqn_float32_stand_in_holds_the_bounds_with_a_quarter_of_the_cap(shape, quant):
+    bad = _iqn_stand_in_holds(shape, quant)
+    assert not bad, bad
+
+
+def _iqn_sens(shape):
+    flat, (obs, taus) = sc.inputs(shape)
+    s, S = sc.stand_in(shape)
+    r = sc.reference(shape, S, True, key="stand-in")
+    W = rs.IqnWeights(flat, shape[3], True, torch.float32)
+    t = {k: torch.from_numpy(np.asarray(v)).float() for k, v in S.items()}
+    e = rs.iqn_cos(taus.reshape(-1), torch.float32)
+    return S, r, W, t, e, taus.shape[1]
+
+
+IQN_SENS = ("iqn", 3, 8, 6, False)  # 16-row tiles spanning frames
+
+
+@pytest.mark.parametrize("defect", ["first_frame", "tanh_gelu", "no_bq", "raw_second_moment"])
+def test_iqn_defect_of_the_embed_stage(defect):
+    """A tile's rows all reading its first row's frame; tanh-GELU for erf-GELU; bq dropped; the
+    variance without the mean subtracted: each fails y's check, and the sound stage passes."""
+    _, r, W, t, e, n_tau = _iqn_sens(IQN_SENS)
+    assert _fails_tensor("y", rs.iqn_embed_ln(t["act3"], rs.rne_bf16(e), W, n_tau, defect), r)
+    assert not _fails_tensor("y", rs.iqn_embed_ln(t["act3"], rs.rne_bf16(e), W, n_tau), r)
+
+
+def test_iqn_defect_cosine_tile_left_unrounded():
+    _, r, W, t, e, n_tau = _iqn_sens(IQN_SENS)
+    assert not torch.equal(e, rs.rne_bf16(e))
+    assert _fails_tensor("y", rs.iqn_embed_ln(t["act3"], e, W, n_tau), r)
+
+
+def test_iqn_defect_q_mean_over_W_columns():
+    S, _, _, t, _, n_tau = _iqn_sens(IQN_SENS)
+    A = IQN_SENS[3]
+    assert n_tau != A
+    assert sc.hold_dqn_q(rs.dueling_q(t["heads"], A, mean_cols=n_tau).numpy(), S["heads"], A, "defect")
+    assert not sc.hold_dqn_q(rs.dueling_q(t["heads"], A).numpy(), S["heads"], A, "sound")
+
+
+@pytest.mark.parametrize("quant,rows", [(True, 1536), (False, 1920)], ids=["bf16", "fp32"])
+def test_iqn_defect_fc_skips_the_row_tiles_past_its_capped_grid(quant, rows):
+    """The FC's grid is capped at 3 x 256 CUs = 768 tiles; tile t is (feature tile t % n, row tile
+    t / n), so its first pass covers 768 / 16 row tiles of 32 (bf16) or 768 / 32 of 80 (fp32).  A
+    loop that stopped there would leave the rows behind unwritten (zero: the workspace starts
+    zeroed): the large case reaches them, and h's and zg's checks fail."""
+    shape = sc.IQN_LARGE
+    s, S = sc.stand_in(shape, quant)
+    r = sc.reference(shape, S, quant, key="stand-in" if quant else None)
+    assert rows < shape[1] * shape[2]
+    got = {k: S[k].copy() for k in ("h", "zg")}
+    assert not sc.hold_tensors(got, r, ("h", "zg"), quant, "sound")
+    for k in got:
+        got[k][rows:] = 0
+    bad = sc.hold_tensors(got, r, ("h", "zg"), quant, "defect")
+    assert any(b.startswith("h:") for b in bad) and any(b.startswith("zg:") for b in bad), bad
+
+
+def test_iqn_undecided_cosine_is_resolved_row_by_row_not_tolerated():
+    """A kernel whose cosf rounded the other way at the undecided elements of the large case: the
+    reference's own rounding fails y (the bounds see it), the row search finds the kernel's
+    rounding and y holds under it; a row that is wrong (another frame's act3) is not rescued."""
+    shape = sc.IQN_LARGE
+    flat, (_, taus) = sc.inputs(shape)
+    s, S = sc.stand_in(shape)
+    r = sc.reference(shape, S, True, key="stand-in")
+    lo, hi, und = sc.iqn_undecided_rows(shape)
+    W = rs.IqnWeights(flat, shape[3], True, torch.float32)
+    base = rs.rne_bf16(torch.from_numpy(r["e"])).numpy()
+    other = np.where(und, np.where(base == lo, hi, lo), base)  # every undecided element flipped
+    rows = np.nonzero(und.any(1))[0]
+    act3 = torch.from_numpy(S["act3"]).float()
+    y = rs.rne_bf16(rs.iqn_embed_ln(act3, torch.from_numpy(other).float(), W, taus.shape[1]))
+    got = dict(S, y=y.double().numpy())
+    assert sc.hold_tensors(got, r, ("y",), True, "other rounding, reference's own")
+    r2, bad = sc.iqn_resolve_embed(shape, got, r, True, "other rounding")
+    assert not bad and not sc.hold_tensors(got, r2, ("y",), True, "other rounding, resolved")
+    changed = np.nonzero((r2["t"]["y"] != r["t"]["y"]).any(1))[0]
+    assert set(changed) <= set(rows) and len(changed) >= len(rows) // 2
+    f = int(rows[0]) // taus.shape[1]
+    wrong = got["y"].copy()
+    wrong[rows[0]] = rs.rne_bf16(rs.iqn_embed_ln_rows(
+        act3[(f + 1) % shape[1]][None], torch.from_numpy(other[rows[0]]).float()[None], W)).numpy()[0]
+    got = dict(S, y=wrong)
+    r3, _ = sc.iqn_resolve_embed(shape, got, r, True, "wrong row")
+    assert sc.hold_tensors(got, r3, ("y",), True, "wrong row")
