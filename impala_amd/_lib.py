@@ -89,9 +89,12 @@ DQN_EXPORTS = (
 IQN_EXPORTS = (
     "iqn_abi_version", "iqn_last_error", "iqn_config_default", "iqn_param_count", "iqn_create",
     "iqn_destroy", "iqn_bind_params", "iqn_sync_target", "iqn_refresh_weights", "iqn_forward",
-    "iqn_act", "iqn_nstep_targets", "iqn_loss_head", "iqn_debug_read",
+    "iqn_act", "iqn_nstep_targets", "iqn_loss_head", "iqn_debug_read", "iqn_optim_default",
+    "iqn_bind_state", "iqn_set_metrics", "iqn_set_step", "iqn_train_step", "iqn_compute_grads",
+    "iqn_apply_update",
 )
-IQN_ABI_VERSION = 1
+IQN_ABI_VERSION = 2
+IQN_DBG_DPRE, IQN_DBG_DX, IQN_DBG_COS = 100, 101, 102
 IQN_MAX_TAU = 32
 IQN_MAX_ROWS = 16384
 DQN_ABI_VERSION = 2
@@ -170,6 +173,18 @@ class DqnConfig(C.Structure):
 class IqnConfig(C.Structure):
     _fields_ = [("batch_size", C.c_int), ("num_actions", C.c_int), ("n_tau", C.c_int),
                 ("dtype", C.c_int)]
+
+
+class IqnOptim(C.Structure):
+    _fields_ = [("lr", C.c_float), ("adam_beta1", C.c_float), ("adam_beta2", C.c_float),
+                ("adam_eps", C.c_float), ("max_grad_norm", C.c_float),
+                ("importance_sampling_exponent", C.c_float), ("huber_param", C.c_float)]
+
+
+class IqnBatch(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("targets", C.c_void_p),
+                ("probabilities", C.c_void_p), ("taus", C.c_void_p), ("priorities", C.c_void_p),
+                ("taus_out", C.c_void_p), ("seed", C.c_uint64), ("counter", C.c_uint64)]
 
 
 class DqnBatch(C.Structure):
@@ -317,6 +332,13 @@ def _declare(lib):
     lib.iqn_loss_head.argtypes = [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_float, C.c_float, _P, _P, _P, _P, _P]
     lib.iqn_debug_read.argtypes = [_P, C.c_int, _P, C.c_size_t, _P]
+    lib.iqn_optim_default.argtypes = [C.POINTER(IqnOptim)]
+    lib.iqn_bind_state.argtypes = [_P, _P, _P, _P, _P, _P, C.POINTER(IqnOptim), _P]
+    lib.iqn_set_metrics.argtypes = [_P, _P]
+    lib.iqn_set_step.argtypes = [_P, C.c_int64, _P]
+    lib.iqn_train_step.argtypes = [_P, C.POINTER(IqnBatch), _P]
+    lib.iqn_compute_grads.argtypes = [_P, C.POINTER(IqnBatch), _P]
+    lib.iqn_apply_update.argtypes = [_P, _P]
     for name in IQN_EXPORTS:
         getattr(lib, name).restype = (C.c_char_p if name == "iqn_last_error" else
                                       C.c_size_t if name == "iqn_param_count" else C.c_int)

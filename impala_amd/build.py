@@ -27,8 +27,8 @@ def hip_units():
     dqn_replay.hip: the kernels of the DQN learner's device-side replay, kept out of impala.hip's
     code object; ppo_replay.hip: the PPO actor's lambda-return ingest kernel, kept out likewise;
     dqn_inplace.hip: the DQN step's three batch-reading kernels instantiated for a replay ring read in
-    place, kept out likewise; iqn.hip: the kernels of the distributional (IQN) actor path, kept out
-    likewise)."""
+    place, kept out likewise; iqn.hip: the kernels of the distributional (IQN) actor path and
+    training step, kept out likewise)."""
     return [os.path.join(SRC_DIR, f)
             for f in ("impala.hip", "sac.hip", "dqn_replay.hip", "ppo_replay.hip", "dqn_inplace.hip",
                       "iqn.hip")]

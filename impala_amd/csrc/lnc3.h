@@ -16,6 +16,12 @@
 //       shifted-window LDS reads.
 // LN gamma / beta gradient partials are kept per lane and written as one fp32 slab per
 // workgroup (fixed-order combine of the groups), reduced by reduce_grads like the others.
+//
+// MODE (a template parameter of the bodies, LNC3_LN unless a caller says otherwise): with
+// LNC3_DX the net has no LayerNorm directly on act3 (the IQN net modulates act3 by the quantile
+// embedding first), `dy` holds the pre-mask gradient of act3 itself, and the LayerNorm
+// arithmetic, its statistics / gamma loads and its slab are compiled out; the ReLU mask, the
+// conv3 input gradient and everything after are the same code.
 #pragma once
 #include "conv1.h"
 #include "gemm.h"
@@ -27,6 +33,7 @@ namespace lc3 {
 constexpr int ZR = 9 * OC2 + 4;  // Z row (fp32): [tap][ci] of one output pixel, padded
 }
 
+constexpr int LNC3_LN = 0, LNC3_DX = 1;  // MODE
 constexpr int LNC3_GROUPS = 2;  // bf16: 4-wave groups per workgroup (lnc3_body_g)
 // threads of a launch: bf16 2 groups of 4 waves on alternating frames; fp32 8 waves on one
 // frame (lnc3_body_f32r)
@@ -54,6 +61,7 @@ template <> struct Lnc3Lds<float> { static constexpr int BYTES = Lnc3F32::BYTES;
 
 // The bf16 kernel body, on workgroup `wg` (frames wg*fpw ..) with the LDS passed in
 // (Lnc3Lds<__bf16>::BYTES), so a launch can run it ahead of another per-frame body.
+template <int MODE = LNC3_LN>
 DEV void lnc3_body_g(const float* __restrict__ dy, const __bf16* __restrict__ act3,
                      const float* __restrict__ stats, const float* __restrict__ gam,
                      const __bf16* __restrict__ w3, const __bf16* __restrict__ act2,
@@ -91,8 +99,10 @@ DEV void lnc3_body_g(const float* __restrict__ dy, const __bf16* __restrict__ ac
   auto fetch = [&](int f) {
     ndy = *reinterpret_cast<const f32x4*>(dy + (size_t)f * FLAT + j0);
     load4(act3 + (size_t)f * FLAT + j0, nx);
-    nm = stats[2 * f];
-    nr = stats[2 * f + 1];
+    if constexpr (MODE == LNC3_LN) {
+      nm = stats[2 * f];
+      nr = stats[2 * f + 1];
+    }
 #pragma unroll
     for (int r = 0; r < 3; ++r) {  // gather items e = tid + 256 r: pixel e / 16, channels 4 (e % 16)
       const int e = min(tid + 256 * r, P2 * 16 - 1);
@@ -101,8 +111,10 @@ DEV void lnc3_body_g(const float* __restrict__ dy, const __bf16* __restrict__ ac
   };
   if (f0 + grp < f1) fetch(f0 + grp);
   float gm[4], dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (MODE == LNC3_LN) {
 #pragma unroll
-  for (int q = 0; q < 4; ++q) gm[q] = gam[j0 + q];
+    for (int q = 0; q < 4; ++q) gm[q] = gam[j0 + q];
+  }
 
   // ---- W3 fragments: B[k = oc][n = ci] = W3[oc][tap][ci] of every tap (k-major), held in
   // registers for the whole frame run (72 VGPRs), staged through LDS (rows bit-2/3 swapped,
@@ -131,8 +143,10 @@ DEV void lnc3_body_g(const float* __restrict__ dy, const __bf16* __restrict__ ac
   }
   __syncthreads();  // the staging area becomes the Z / dact3 tiles
   // consume the prologue loads before the loop (see conv1.h: waits merged over the back-edge)
+  if constexpr (MODE == LNC3_LN) {
 #pragma unroll
-  for (int q = 0; q < 4; ++q) asm volatile("" ::"v"(gm[q]));
+    for (int q = 0; q < 4; ++q) asm volatile("" ::"v"(gm[q]));
+  }
 
   for (int e = tid; e < lc3::ZR / 4; e += 256)  // the zero row of this group's Z tile
     *reinterpret_cast<f32x4*>(zs + P3 * lc3::ZR + 4 * e) = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -150,29 +164,36 @@ DEV void lnc3_body_g(const float* __restrict__ dy, const __bf16* __restrict__ ac
 #pragma unroll
       for (int q = 0; q < 4; ++q) am[pt][q] = na[pt][q];
     // ---- LayerNorm backward: the two per-frame sums ----
-    float s1 = 0.f, s2 = 0.f;
+    if constexpr (MODE == LNC3_LN) {
+      float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      xh[q] = (x[q] - mean) * rstd;
-      const float gd = d[q] * gm[q];
-      s1 += gd;
-      s2 += gd * xh[q];
+      for (int q = 0; q < 4; ++q) {
+        xh[q] = (x[q] - mean) * rstd;
+        const float gd = d[q] * gm[q];
+        s1 += gd;
+        s2 += gd * xh[q];
+      }
+      s1 = wave_sum(s1);
+      s2 = wave_sum(s2);
+      if (lane == 0) { red[grp][wave][0] = s1; red[grp][wave][1] = s2; }
     }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    if (lane == 0) { red[grp][wave][0] = s1; red[grp][wave][1] = s2; }
     __syncthreads();
     if (f + G < f1) fetch(f + G);
     if (active) {
-      const float S1 = (red[grp][0][0] + red[grp][1][0] + red[grp][2][0] + red[grp][3][0]) * (1.f / FLAT);
-      const float S2 = (red[grp][0][1] + red[grp][1][1] + red[grp][2][1] + red[grp][3][1]) * (1.f / FLAT);
       float o[4];
+      if constexpr (MODE == LNC3_LN) {
+        const float S1 = (red[grp][0][0] + red[grp][1][0] + red[grp][2][0] + red[grp][3][0]) * (1.f / FLAT);
+        const float S2 = (red[grp][0][1] + red[grp][1][1] + red[grp][2][1] + red[grp][3][1]) * (1.f / FLAT);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        dg[q] += d[q] * xh[q];
-        db[q] += d[q];
-        const float gx = rstd * (d[q] * gm[q] - S1 - xh[q] * S2);
-        o[q] = x[q] > 0.f ? gx : 0.f;
+        for (int q = 0; q < 4; ++q) {
+          dg[q] += d[q] * xh[q];
+          db[q] += d[q];
+          const float gx = rstd * (d[q] * gm[q] - S1 - xh[q] * S2);
+          o[q] = x[q] > 0.f ? gx : 0.f;
+        }
+      } else {  // d is the gradient of act3 itself
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = x[q] > 0.f ? d[q] : 0.f;
       }
       store4(dact3 + (size_t)f * FLAT + j0, o);
       store4(d3s + p0 * LD3 + c0, o);
@@ -232,6 +253,7 @@ DEV void lnc3_body_g(const float* __restrict__ dy, const __bf16* __restrict__ ac
     }
   }
   // ---- gamma / beta partials: fixed-order combine of the groups -> slab [2][1024] ----
+  if constexpr (MODE != LNC3_LN) return;
   __syncthreads();
   if (grp == 0) {
 #pragma unroll
@@ -265,7 +287,7 @@ DEV void lnc3_body_g(const float* __restrict__ dy, const __bf16* __restrict__ ac
 //   role 1: the W3 fragments of all nine taps (ci tile = wave & 3), the scatter GEMM, the other
 //           half of the gather.
 // Same sums in the same order as the one-group form.
-template <int ROLE, class Pre>
+template <int ROLE, int MODE = LNC3_LN, class Pre>
 DEV void lnc3_body_f32r(const float* __restrict__ dy, const float* __restrict__ act3,
                         const float* __restrict__ stats, const float* __restrict__ gam,
                         const float* __restrict__ w3t, const float* __restrict__ act2,
@@ -292,8 +314,10 @@ DEV void lnc3_body_f32r(const float* __restrict__ dy, const float* __restrict__ 
     if constexpr (LN) {
       ndy = *reinterpret_cast<const f32x4*>(dy + (size_t)f * FLAT + j0);
       load4(act3 + (size_t)f * FLAT + j0, nx);
-      nm = stats[2 * f];
-      nr = stats[2 * f + 1];
+      if constexpr (MODE == LNC3_LN) {
+        nm = stats[2 * f];
+        nr = stats[2 * f + 1];
+      }
     }
 #pragma unroll
     for (int r = 0; r < NGI; ++r) {  // gather items e = t + 512 r: pixel e / 16, channels 4 (e % 16)
@@ -308,12 +332,12 @@ DEV void lnc3_body_f32r(const float* __restrict__ dy, const float* __restrict__ 
   // tap * 4 + ko of wave ct is 1 KB contiguous, this lane's 16 bytes at 16 lane, the wave's 36
   // instructions one after the other (36 KB)
   V wa[LN ? 1 : 9][NKO];
-  if constexpr (LN) {
+  if constexpr (LN && MODE == LNC3_LN) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) gm[q] = gam[j0 + q];
 #pragma unroll
     for (int q = 0; q < 4; ++q) asm volatile("" ::"v"(gm[q]));
-  } else {
+  } else if constexpr (!LN) {
     static_assert(w3t_index(KS * 1 + 4 * 2 + 3, 5, 16 * 3 + 7) == ((3 * 9 + 5) * NKO + 1) * WFRAG + 4 * (16 * 2 + 7) + 3,
                   "w3t: [ci tile][tap][ko][lane][q]");
     int ln = lane;
@@ -336,7 +360,7 @@ DEV void lnc3_body_f32r(const float* __restrict__ dy, const float* __restrict__ 
     // ---- LayerNorm backward (role 0): the two per-frame sums, then dact3 ----
     float d[4], x[4], xh[4];
     const float mean = nm, rstd = nr;
-    if constexpr (LN) {
+    if constexpr (LN && MODE == LNC3_LN) {
       float s1 = 0.f, s2 = 0.f;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -350,6 +374,12 @@ DEV void lnc3_body_f32r(const float* __restrict__ dy, const float* __restrict__ 
       s1 = wave_sum(s1);
       s2 = wave_sum(s2);
       if (lane == 0) { red[wave][0] = s1; red[wave][1] = s2; }
+    } else if constexpr (LN) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        d[q] = ndy[q];
+        x[q] = nx[q];
+      }
     }
     __syncthreads();
     if (f + 1 < f1) fetch(f + 1);
@@ -357,15 +387,20 @@ DEV void lnc3_body_f32r(const float* __restrict__ dy, const float* __restrict__ 
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (f == f0 + 1 + k) pre(k);
-      const float S1 = (red[0][0] + red[1][0] + red[2][0] + red[3][0]) * (1.f / FLAT);
-      const float S2 = (red[0][1] + red[1][1] + red[2][1] + red[3][1]) * (1.f / FLAT);
       float o[4];
+      if constexpr (MODE == LNC3_LN) {
+        const float S1 = (red[0][0] + red[1][0] + red[2][0] + red[3][0]) * (1.f / FLAT);
+        const float S2 = (red[0][1] + red[1][1] + red[2][1] + red[3][1]) * (1.f / FLAT);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        dg[q] += d[q] * xh[q];
-        db[q] += d[q];
-        const float gx = rstd * (d[q] * gm[q] - S1 - xh[q] * S2);
-        o[q] = x[q] > 0.f ? gx : 0.f;
+        for (int q = 0; q < 4; ++q) {
+          dg[q] += d[q] * xh[q];
+          db[q] += d[q];
+          const float gx = rstd * (d[q] * gm[q] - S1 - xh[q] * S2);
+          o[q] = x[q] > 0.f ? gx : 0.f;
+        }
+      } else {  // d is the gradient of act3 itself
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = x[q] > 0.f ? d[q] : 0.f;
       }
       store4(dact3 + (size_t)f * FLAT + j0, o);
       store4(d3s + p0 * LD3 + c0, o);
@@ -425,8 +460,10 @@ DEV void lnc3_body_f32r(const float* __restrict__ dy, const float* __restrict__ 
     for (int k = 0; k < 4; ++k)
       if (f1 - f0 < k + 2) pre(k);
     // ---- gamma / beta partials -> slab [2][1024] ----
-    *reinterpret_cast<f32x4*>(slab + (size_t)wg * 2 * FLAT + j0) = f32x4{dg[0], dg[1], dg[2], dg[3]};
-    *reinterpret_cast<f32x4*>(slab + (size_t)wg * 2 * FLAT + FLAT + j0) = f32x4{db[0], db[1], db[2], db[3]};
+    if constexpr (MODE == LNC3_LN) {
+      *reinterpret_cast<f32x4*>(slab + (size_t)wg * 2 * FLAT + j0) = f32x4{dg[0], dg[1], dg[2], dg[3]};
+      *reinterpret_cast<f32x4*>(slab + (size_t)wg * 2 * FLAT + FLAT + j0) = f32x4{db[0], db[1], db[2], db[3]};
+    }
   }
 }
 
@@ -500,6 +537,53 @@ __global__ __launch_bounds__(lnc3_threads<T>()) void lnc3_conv12_bwd(
     }
   } else {
     lnc3_body<T>(dy, act3, stats, gam, w3, w3t, act2, dact3, dact2, ln_slab, N, fpw, (int)blockIdx.x, lds);
+    __syncthreads();  // this workgroup's dact2 stores are visible to all its waves; LDS is reused
+    conv12_bwd_body<T>(x, w2, w2t, dact2, mask1, c1_slab, c1_slab_bias, N, fpw, (int)blockIdx.x, lds, wm);
+  }
+}
+
+// The same launch from the gradient of act3 itself (LNC3_DX; the IQN step, iqn.hip): `dy` is dx
+// [N][1024] fp32 in the kernel order p*64 + c, before the ReLU mask; no statistics, gamma or slab.
+// The glue between the two bodies is repeated here, not shared through a device function: with
+// the kernel above calling such a function its fp32 code grew by 1.5 KB (the restrict
+// qualifiers reach the bodies as scoped metadata instead of argument attributes), and the
+// existing kernels keep their machine code (profiles/iqn_step/isa_cmp.txt).
+template <typename T>
+__global__ __launch_bounds__(lnc3_threads<T>()) void lnc3_conv12_bwd_dx(
+    const float* __restrict__ dy, const T* __restrict__ act3, const T* __restrict__ w3,
+    const T* __restrict__ w3t, const T* __restrict__ act2, T* __restrict__ dact3, T* __restrict__ dact2,
+    const uint8_t* __restrict__ x, const T* __restrict__ w2, const T* __restrict__ w2t,
+    const uint32_t* __restrict__ mask1, float* __restrict__ c1_slab, float* __restrict__ c1_slab_bias, int N,
+    int fpw) {
+  constexpr int MODE = LNC3_DX;
+  const float *stats = nullptr, *gam = nullptr;
+  float* ln_slab = nullptr;
+  const ObsDirect rm{};
+  constexpr int B1 = Lnc3Lds<T>::BYTES, B2 = C12BLds<T>::BYTES;
+  __shared__ __attribute__((aligned(16))) char lds[B1 > B2 ? B1 : B2];
+  const auto& wm = obs_wg(rm, (int)blockIdx.x * fpw, N);
+  if constexpr (sizeof(T) == 4) {
+    const float* w3f = reinterpret_cast<const float*>(w3t);
+    const float* w2f = reinterpret_cast<const float*>(w2t);
+    const float* a3 = reinterpret_cast<const float*>(act3);
+    const float* a2 = reinterpret_cast<const float*>(act2);
+    float* d3 = reinterpret_cast<float*>(dact3);
+    float* d2 = reinterpret_cast<float*>(dact2);
+    Frag<float>::vec wb[4][OC2 / Frag<float>::KSTEP][2];
+    const int wg = (int)blockIdx.x;
+    if (threadIdx.x < 256) {
+      const int cls = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+      lnc3_body_f32r<0, MODE>(dy, a3, stats, gam, w3f, a2, d3, d2, ln_slab, N, fpw, wg, lds,
+                        [&](int k) { c12_load_w2(w2f, wb, cls, lane, k, k + 1); });
+      __syncthreads();  // this workgroup's dact2 stores are visible to all its waves; LDS is reused
+      conv12_bwd_body_f32<0>(x, w2f, d2, mask1, c1_slab, c1_slab_bias, N, fpw, wg, lds, wb, false, wm);
+    } else {
+      lnc3_body_f32r<1, MODE>(dy, a3, stats, gam, w3f, a2, d3, d2, ln_slab, N, fpw, wg, lds, [](int) {});
+      __syncthreads();
+      conv12_bwd_body_f32<1>(x, w2f, d2, mask1, c1_slab, c1_slab_bias, N, fpw, wg, lds, wb, false, wm);
+    }
+  } else {
+    lnc3_body_g<MODE>(dy, act3, stats, gam, w3, act2, dact3, dact2, ln_slab, N, fpw, (int)blockIdx.x, lds);
     __syncthreads();  // this workgroup's dact2 stores are visible to all its waves; LDS is reused
     conv12_bwd_body<T>(x, w2, w2t, dact2, mask1, c1_slab, c1_slab_bias, N, fpw, (int)blockIdx.x, lds, wm);
   }

@@ -630,11 +630,15 @@ class ApexLearner(Learner):
         self._update_priorities_future = None
         self._device = model.flat.device
         self.can_train = False
-        self._engine = DqnEngine(model, batch_size=batch_size, dtype=dtype, lr=optimizer.lr,
-                                 eps=optimizer.eps, betas=optimizer.betas,
-                                 max_grad_norm=max_grad_norm,
-                                 importance_sampling_exponent=importance_sampling_exponent)
+        self._engine = self._make_engine(model, batch_size, dtype)
         model._train_engine = self._engine
+
+    def _make_engine(self, model, batch_size, dtype):
+        """The training engine bound to ``model`` (``DistributionalApexLearner`` makes an IQN one)."""
+        o = self._optimizer
+        return DqnEngine(model, batch_size=batch_size, dtype=dtype, lr=o.lr, eps=o.eps, betas=o.betas,
+                         max_grad_norm=self._max_grad_norm,
+                         importance_sampling_exponent=self._importance_sampling_exponent)
 
     @property
     def engine(self) -> DqnEngine:

@@ -1,14 +1,15 @@
-"""The distributional (IQN) Ape-X actor path on the HIP library:
+"""The distributional (IQN) Ape-X agent on the HIP library:
 ``DistributionalAtariDQN`` (models/distributed_models.py:35-69 over
 models/models.py:90-101 and models/quantile_layers.py:7-54), ``ApexDistributionalActor``
-(agents/dqn/learning.py:68-84), ``ApexDistributionalBuilder`` (agents/dqn/builder.py:124-156)
-and the quantile-regression loss as a standalone head (``iqn_loss_head``).
+(agents/dqn/learning.py:68-84), ``DistributionalApexLearner`` (agents/dqn/learning.py:197-237),
+``ApexDistributionalBuilder`` (agents/dqn/builder.py:124-156) and the quantile-regression loss as
+a standalone head (``iqn_loss_head``).
 
 The network is the dueling DQN's trunk and heads with a quantile embedding multiplied into the
 trunk's features before the LayerNorm: W = ``n_tau_samples`` quantiles per frame, so one call on
 n frames runs the head on n W rows.  Every compute entry is one call of include/iqn_hip.h; the
-compute path is the HIP library only.  The training step through the trunk is not built yet:
-``ApexDistributionalBuilder.make_learner`` raises ``NotImplementedError``.
+compute path is the HIP library only.  The learner samples from the torch
+``PrioritizedReplay(target_width=W)``; a native replay with ``[W]`` targets is not built.
 """
 from __future__ import annotations
 
@@ -23,8 +24,8 @@ import torch.nn as nn
 from impala_amd import _lib
 from impala_amd._lib import check, lib
 from impala_amd.core import Actor
-from impala_amd.dqn import (ApexActor, ApexDQNBuilder, ConstantEpsFunc, FlexibleEpsFunc,
-                            PrioritizedReplay)
+from impala_amd.dqn import (ApexActor, ApexDQNBuilder, ApexLearner, ConstantEpsFunc,
+                            FlexibleEpsFunc, PrioritizedReplay)
 from impala_amd.flat import FlatModule, layer_init_truncated, spec_count
 from impala_amd.model import OBS_SHAPE
 
@@ -129,7 +130,9 @@ class IqnEngine(_lib.NativeHandle):
     _destroy, _last_error = "iqn_destroy", _ERR
 
     def __init__(self, model: "DistributionalAtariDQN", batch_size: int = 128,
-                 dtype: Optional[str] = None):
+                 dtype: Optional[str] = None, train: bool = False, lr: float = 6.25e-5,
+                 eps: float = 1e-4, betas=(0.9, 0.999), max_grad_norm: float = 40.0,
+                 importance_sampling_exponent: float = 0.4, huber_param: float = 1.0):
         self.model = model
         self.device = model.flat.device
         if self.device.type != "cuda":
@@ -142,6 +145,18 @@ class IqnEngine(_lib.NativeHandle):
         self._open("iqn_create", C.byref(cfg), self.device_index(self.device))
         check(lib().iqn_bind_params(self._h, _lib.ptr(model.flat), _lib.ptr(model.target_flat),
                                     _lib.stream_ptr(None)), "iqn_bind_params", _ERR)
+        self.train = bool(train)
+        self.metrics = torch.zeros(_lib.DQN_NUM_METRICS, device=self.device)
+        if self.train:  # the Adam state beside the flat parameters, in their order
+            n = model.flat.numel()
+            self.exp_avg = torch.zeros(n, device=self.device)
+            self.exp_avg_sq = torch.zeros(n, device=self.device)
+            opt = _lib.IqnOptim(lr, betas[0], betas[1], eps, max_grad_norm,
+                                importance_sampling_exponent, huber_param)
+            check(lib().iqn_bind_state(self._h, _lib.ptr(model.flat), _lib.ptr(model.flat_grad),
+                                       _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
+                                       _lib.ptr(self.metrics), C.byref(opt), _lib.stream_ptr(None)),
+                  "iqn_bind_state", _ERR)
         self._version = model._version
 
     def _fresh(self):
@@ -198,21 +213,70 @@ class IqnEngine(_lib.NativeHandle):
         self._fresh()
         check(lib().iqn_sync_target(self._h, _lib.stream_ptr(None)), "iqn_sync_target", _ERR)
 
-    # name -> (IMPALA_DBG_* id, element kind, shape of one row, rows per frame: 1 or W)
+    # ---------------------------------------------------------------- training
+    def bind_metrics(self, m: torch.Tensor) -> None:
+        self.metrics = m
+        check(lib().iqn_set_metrics(self._h, _lib.ptr(m)), "iqn_set_metrics", _ERR)
+
+    def set_step(self, step: int) -> None:
+        check(lib().iqn_set_step(self._h, int(step), _lib.stream_ptr(None)), "iqn_set_step", _ERR)
+
+    def train_step(self, obs, actions, targets, probabilities=None, taus=None, seed: int = 0,
+                   counter: int = 0):
+        """One learner step (``iqn_train_step``) -> (priorities [N], taus [N, W]) on the device;
+        ``taus`` None: the online net's quantiles are drawn from (seed, counter)."""
+        return self._step("iqn_train_step", obs, actions, targets, probabilities, taus, seed, counter)
+
+    def compute_grads(self, obs, actions, targets, probabilities=None, taus=None, seed: int = 0,
+                      counter: int = 0):
+        """``train_step`` without clip and Adam (``iqn_compute_grads``): the pre-clip gradient in
+        ``model.flat_grad`` and metrics q / target / priorities / loss; ``apply_update`` completes
+        the step."""
+        return self._step("iqn_compute_grads", obs, actions, targets, probabilities, taus, seed, counter)
+
+    def apply_update(self) -> None:
+        check(lib().iqn_apply_update(self._h, _lib.stream_ptr(None)), "iqn_apply_update", _ERR)
+
+    def _step(self, entry, obs, actions, targets, probabilities, taus, seed, counter):
+        if not self.train:
+            raise RuntimeError("an inference engine: construct IqnEngine(train=True)")
+        self._fresh()
+        if obs.shape[0] != self.N:
+            raise ValueError(f"batch of {obs.shape[0]} transitions on a handle of {self.N}")
+        targets = targets.to(self.device, torch.float32).contiguous()
+        if tuple(targets.shape) != (self.N, self.W):
+            raise ValueError(f"targets: [{self.N}, {self.W}]")
+        prio = torch.empty(self.N, device=self.device)
+        used = torch.empty(self.N, self.W, device=self.device)
+        keep = [obs.contiguous(), actions.reshape(-1).contiguous().to(torch.int64), targets,
+                None if probabilities is None else probabilities.reshape(-1).contiguous().to(
+                    self.device, torch.float32), self._taus(taus, self.N)]
+        b = _lib.IqnBatch(_lib.ptr(keep[0]), _lib.ptr(keep[1]), _lib.ptr(keep[2]), _lib.ptr(keep[3]),
+                          _lib.ptr(keep[4]), _lib.ptr(prio), _lib.ptr(used), int(seed), int(counter))
+        check(getattr(lib(), entry)(self._h, C.byref(b), _lib.stream_ptr(None)), entry, _ERR)
+        return prio, used
+
+    # name -> (debug tensor id, element kind, shape of one row, rows per frame: 1 or W)
     DEBUG_TENSORS = {
         "act1": (0, "T", (15, 15, 32), False), "act2": (1, "T", (6, 6, 64), False),
         "act3": (2, "T", (1024,), False), "mask1": (8, "u32", (225,), False),
         "y": (3, "T", (1024,), True), "h": (4, "T", (HIDDEN,), True),
         "zg": (10, "f32", (HIDDEN,), True), "heads": (11, "f32", (16,), True),
+        # of the training step
+        "lnstat": (9, "f32", (2,), True), "cos": (_lib.IQN_DBG_COS, "T", (N_COS,), True),
+        "dz": (5, "T", (HIDDEN,), True), "dy": (12, "f32", (1024,), True),
+        "dpre": (_lib.IQN_DBG_DPRE, "T", (1024,), True), "dx": (_lib.IQN_DBG_DX, "f32", (1024,), False),
+        "dact3": (6, "T", (1024,), False), "dact2": (7, "T", (6, 6, 64), False),
     }
 
     def debug_tensor(self, name: str, frames: Optional[int] = None):
         """``DqnEngine.debug_tensor`` on this handle (``iqn_debug_read``; a host sync): the
-        workspace tensor ``name`` as the last forward or act left it, a numpy array in
+        workspace tensor ``name`` as the last forward, act or step left it, a numpy array in
         ``Engine.debug_tensor``'s layouts -- act1, act2, act3 (the trunk's features before the
         modulation) and mask1 per frame [frames, ...]; y, zg, h and heads per quantile row
-        r = f W + k [frames * W, ...], h / zg 512 wide.  The one workspace holds the net that ran
-        last."""
+        r = f W + k [frames * W, ...], h / zg 512 wide; of a training step also lnstat, cos, dz,
+        dy and dpre per row and dx, dact3, dact2 per frame, the 1024-wide ones in the kernel order
+        p*64 + c.  The one workspace holds the net that ran last."""
         if name not in self.DEBUG_TENSORS:
             raise ValueError(f"unknown debug tensor {name!r}: one of {sorted(self.DEBUG_TENSORS)}")
         which, kind, shape, per_row = self.DEBUG_TENSORS[name]
@@ -359,9 +423,43 @@ class ApexDistributionalActorFactory:
         return ApexDistributionalActor(self._model, self._rb, eps=self._eps_func(index), **self._kwargs)
 
 
+class DistributionalApexLearner(ApexLearner):
+    """``DistributionalApex`` (agents/dqn/learning.py:197-237) over ``ApexLearner``'s loop: sample
+    from the ``PrioritizedReplay(target_width=W)``, one ``iqn_train_step`` call, the priorities
+    written back at the sampled keys, target sync every ``target_sync_period`` steps; the
+    reference's metric names.  The online net's quantiles of a step are drawn by the library from
+    the model's act seed and call counter (the reference draws ``torch.rand``)."""
+
+    def __init__(self, model, replay_buffer, *args, huber_param: float = 1.0, **kwargs) -> None:
+        if getattr(replay_buffer, "target_width", 1) != model.n_tau_samples:
+            raise ValueError("the replay's target_width must equal the model's n_tau_samples")
+        self._huber_param = float(huber_param)
+        super().__init__(model, replay_buffer, *args, **kwargs)
+
+    def _make_engine(self, model, batch_size, dtype):
+        o = self._optimizer
+        return IqnEngine(model, batch_size=batch_size, dtype=dtype, train=True, lr=o.lr, eps=o.eps,
+                         betas=o.betas, max_grad_norm=self._max_grad_norm,
+                         importance_sampling_exponent=self._importance_sampling_exponent,
+                         huber_param=self._huber_param)
+
+    def _train_step(self, keys, batch, probabilities) -> Dict[str, torch.Tensor]:  # :199-237
+        e = self._engine
+        m = torch.empty(_lib.DQN_NUM_METRICS, dtype=torch.float32, device=e.device)
+        e.bind_metrics(m)
+        obs, action, target = batch
+        seed, counter = self._model._next_draw()
+        priorities, self.last_taus = e.train_step(obs, action, target, probabilities, seed=seed,
+                                                  counter=counter)
+        self._replay_buffer.update(keys, priorities)  # stays on the device
+        v = m.unbind(0)  # device scalars; float(v) synchronises lazily
+        out = {name: v[i] for name, i in _lib.DQN_METRIC_SLOTS}
+        out["debug/priority_update_time"] = 0
+        return out
+
+
 class ApexDistributionalBuilder(ApexDQNBuilder):
-    """agents/dqn/builder.py:124-156 on the HIP library: the network and the actor; the learner's
-    step is not built yet."""
+    """agents/dqn/builder.py:124-156 on the HIP library: the network, the actor and the learner."""
 
     def make_replay(self, native: bool = False, in_place: bool = False):
         """A ``PrioritizedReplay`` whose targets are rows of ``n_tau_samples`` quantiles."""
@@ -384,10 +482,10 @@ class ApexDistributionalBuilder(ApexDQNBuilder):
                                               rollout_length=int(self.cfg.agent.rollout_length))
 
     def make_learner(self, model, rb):  # builder.py:126-138
-        raise NotImplementedError(
-            "DistributionalApex's training step (the quantile-regression loss through the quantile "
-            "layer, the modulation and the trunk's backward) is not built yet; iqn_loss_head is the "
-            "loss on given heads")
+        if model.flat.device.type != "cuda":
+            raise NotImplementedError("DistributionalApex's training step runs on the HIP path only "
+                                      "(a model on a cuda device)")
+        return DistributionalApexLearner(model, rb, **self.learner_kwargs())
 
     def make_network(self, env_spec=None):  # builder.py:148-156
         obs_shape, n_act = OBS_SHAPE, 15

@@ -1,5 +1,5 @@
-/* iqn_hip.h — C-ABI of the MI355X-native distributional (IQN) Ape-X actor path (in
- * libimpala_hip.so).
+/* iqn_hip.h — C-ABI of the MI355X-native distributional (IQN) Ape-X agent: the actor path and the
+ * learner's training step (in libimpala_hip.so).
  *
  * The reference's distributional Ape-X variant (paths relative to the d3sm0/impala repository):
  *
@@ -12,7 +12,11 @@
  *                      per-quantile n-step targets and the initial priorities of one rollout
  *   iqn_loss_head      agents/dqn/learning.py:203-216  DistributionalApex._train_step's loss on
  *                      given heads and models/quantile_layers.py:83-93  quantile_regression_loss
- *                      (test / reuse entry; the training step through the trunk is not here yet)
+ *                      (test / reuse entry)
+ *   iqn_train_step     agents/dqn/learning.py:197-237  DistributionalApex._train_step: forward of the
+ *                      online net, the importance-weighted quantile-regression loss, the backward
+ *                      through heads, projection, LayerNorm, modulation, quantile layer and conv
+ *                      trunk, clip_grad_norm_ and Adam; iqn_compute_grads stops before the clip
  *
  * Network, for n frames and W = n_tau quantiles per frame (R = n W rows, row r = f W + k):
  *   x_f = AtariBody(obs_f / 255); e_r[i] = cos(pi i tau_r), i = 1..64, the argument formed in fp32
@@ -46,7 +50,7 @@
 extern "C" {
 #endif
 
-#define IQN_ABI_VERSION 1
+#define IQN_ABI_VERSION 2
 
 #define IQN_HIDDEN 512
 #define IQN_COS 64 /* cosine features of a quantile */
@@ -63,6 +67,33 @@ typedef struct iqn_config {
   int n_tau;       /* W quantiles per frame, 1..32 (conf/agent/apex.yaml n_tau_samples: 8) */
   int dtype;       /* IMPALA_DTYPE_F32 / IMPALA_DTYPE_BF16 */
 } iqn_config;
+
+/* Optimizer and loss settings of the training step (iqn_bind_state); iqn_config keeps the shapes. */
+typedef struct iqn_optim {
+  float lr;                           /* 6.25e-5 */
+  float adam_beta1, adam_beta2;       /* 0.9, 0.999 */
+  float adam_eps;                     /* 1e-4 */
+  float max_grad_norm;                /* 40 */
+  float importance_sampling_exponent; /* 0.4 */
+  float huber_param;                  /* kappa of the quantile Huber loss: 1 (0: |delta|) */
+} iqn_optim;
+
+/* One training batch of exactly batch_size transitions (device pointers). */
+typedef struct iqn_batch {
+  const uint8_t* obs;         /* [N][3][64][64], 16-byte aligned */
+  const int64_t* actions;     /* [N] */
+  const float* targets;       /* [N][W] */
+  const float* probabilities; /* [N] sampling probabilities, or NULL (weights 1) */
+  const float* taus;          /* [N][W] the online net's quantiles, or NULL: drawn from seed / counter */
+  float* priorities;          /* [N] out: |mean_j target - mean_i q| */
+  float* taus_out;            /* [N][W] out, optional: the taus used */
+  uint64_t seed, counter;     /* the draw's key when taus is NULL (which = 0, as iqn_forward) */
+} iqn_batch;
+
+/* Debug tensors of the training step beyond impala_hip.h's ids (iqn_debug_read). */
+#define IQN_DBG_DPRE 100 /* [R][1024] compute type: d loss / d (Wq e + bq), kernel order p*64+c */
+#define IQN_DBG_DX 101   /* [N][1024] fp32: d loss / d act3 (ReLU mask applied), kernel order */
+#define IQN_DBG_COS 102  /* [R][64] compute type: the cosine tile e */
 
 int iqn_abi_version(void);
 const char* iqn_last_error(void);
@@ -119,13 +150,41 @@ int iqn_loss_head(const float* adv, const float* v, const int64_t* actions, cons
                   float huber_param, float beta, float* dadv, float* dv, float* priorities,
                   float* metrics4, void* stream);
 
+/* The defaults of dqn_config_default and huber_param = 1. */
+int iqn_optim_default(iqn_optim* optim);
+/* Training state of the online net, caller-owned flat fp32 [iqn_param_count] buffers in the IQN flat
+ * order (`parameters()` order: Wq, bq between the conv trunk and the LayerNorm): params (it becomes
+ * the online net of iqn_bind_params), grads, exp_avg, exp_avg_sq, and metrics [IMPALA_NUM_METRICS].
+ * optim NULL: iqn_optim_default.  Allocates the step's workspace on the first call and emits the
+ * online net's kernel-layout weights.  The target net is bound by iqn_bind_params. */
+int iqn_bind_state(iqn_learner* h, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                   float* metrics, const iqn_optim* optim, void* stream);
+/* Point the following steps' metrics at another [IMPALA_NUM_METRICS] device vector. */
+int iqn_set_metrics(iqn_learner* h, float* metrics);
+/* Set the Adam step counter (0 after iqn_create); synchronises `stream`. */
+int iqn_set_step(iqn_learner* h, int64_t step, void* stream);
+/* One learner step on `b`: loss L = mean_f w_f l_f with l_f iqn_loss_head's L_n on the online net's
+ * own heads (Ws = Wt = n_tau) and w_f = p_f^-beta / max_batch; gradient of every parameter into
+ * grads (pre-clip values scaled by the clip coefficient, as torch leaves them), clip to
+ * max_grad_norm over all parameters, Adam, the kernel-layout weights re-emitted.  metrics: [0] mean
+ * q, [1] mean target, [2] mean priorities, [3] loss, [6] gradient norm before the clip, [7] the
+ * step count.  Every sum runs in a fixed order without atomics: equal inputs give equal bits. */
+int iqn_train_step(iqn_learner* h, const iqn_batch* b, void* stream);
+/* iqn_train_step without clip and Adam: the pre-clip gradient in grads, priorities, metrics 0..3;
+ * the step counter advances.  iqn_apply_update then completes the step, bit for bit. */
+int iqn_compute_grads(iqn_learner* h, const iqn_batch* b, void* stream);
+int iqn_apply_update(iqn_learner* h, void* stream);
+
 /* Test / inspection entry: the workspace tensor `which` (IMPALA_DBG_*, impala_hip.h) as the last
  * iqn_forward / iqn_act left it, copied to dst (device or host) on `stream`.  act1, act2, act3
  * and mask1 are the conv trunk's, per frame (impala_debug_read on the handle's core); y, zg, h
  * and heads are the quantile head's, per row r = f W + k ([R][1024] of the compute type,
  * [R][512] fp32, [R][512] of the compute type, [R][16] fp32), and `bytes` reads their leading
  * rows: in (0, batch_size * n_tau rows].  Both nets run through the one workspace: it holds the
- * net that ran last.  Every other id is refused. */
+ * net that ran last.  After a training step also: IMPALA_DBG_LNSTAT [R][2] (mean, rstd of the
+ * modulated features), IQN_DBG_COS, IMPALA_DBG_DZ [R][512] compute type, IMPALA_DBG_DY [R][1024]
+ * fp32, IQN_DBG_DPRE, IQN_DBG_DX, and the trunk's IMPALA_DBG_DACT3 / IMPALA_DBG_DACT2 per frame.
+ * Every other id is refused. */
 int iqn_debug_read(iqn_learner* h, int which, void* dst, size_t bytes, void* stream);
 
 #ifdef __cplusplus
