@@ -72,7 +72,7 @@ SAC_EXPORTS = (
     "sac_config_default", "sac_actor_param_count", "sac_critic_param_count", "sac_create",
     "sac_destroy", "sac_bind_state", "sac_refresh_weights", "sac_set_steps", "sac_train_step",
     "sac_act", "sac_policy", "sac_q_forward", "sac_phase_count", "sac_phase_name",
-    "sac_timer_start", "sac_timer_read", "sac_sample",
+    "sac_timer_start", "sac_timer_read", "sac_sample", "sac_debug_info", "sac_debug_read",
 )
 SAC_NUM_METRICS = 12
 # every symbol declared in include/dqn_hip.h
@@ -284,6 +284,10 @@ def _declare(lib):
     lib.sac_phase_name.restype = C.c_char_p
     lib.sac_timer_start.argtypes = [_P, C.c_int, C.c_int]
     lib.sac_timer_read.argtypes = [_P, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    lib.sac_debug_info.argtypes = [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int)]
+    lib.sac_debug_info.restype = C.c_char_p
+    lib.sac_debug_read.argtypes = [_P, C.c_int, _P, C.c_size_t, _P]
     lib.sac_sample.argtypes = [C.c_uint64, C.c_uint64, C.c_int64, C.c_int, _P, _P,
                                C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t), C.c_int, _P]
     lib.dqn_config_default.argtypes = [C.POINTER(DqnConfig)]
@@ -348,7 +352,7 @@ def _declare(lib):
     for name in SAC_EXPORTS:
         if name in ("sac_actor_param_count", "sac_critic_param_count"):
             getattr(lib, name).restype = C.c_size_t
-        elif name != "sac_phase_name":
+        elif name not in ("sac_phase_name", "sac_debug_info"):
             getattr(lib, name).restype = C.c_int
 
 

@@ -52,10 +52,13 @@ int fail(int code, const std::string& msg) { return impala_internal::set_error(c
 
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-inline double dec(float x) {  // the decimal constant a float config value was written as
+// The decimal constant a float config value was written as: x rounded to 7 significant digits.
+// (An eighth digit is below a float's resolution: it turned 0.999f, 0.99900001287..., into
+// 0.99900001 and 0.9f into 0.89999998, so that Adam ran with 1 - beta2 = 0.00099999.)
+inline double dec(float x) {
   if (x == 0.f) return 0.0;
   const double e = std::floor(std::log10(std::fabs((double)x)));
-  const double s = std::pow(10.0, 7.0 - e);
+  const double s = std::pow(10.0, 6.0 - e);
   return std::round((double)x * s) / s;
 }
 
@@ -823,6 +826,60 @@ int check_bound(sac_learner* h) {
   return 0;
 }
 
+// ---- workspace export (sac_debug_info / sac_debug_read): every buffer carve() allocates that a
+// step writes, by name.  Host code only.
+struct DbgBuf {
+  const char* name;
+  const void* p;
+  long long rows, ld;
+  int f32;
+};
+// buffer `which` of the table (h may be null: names only); name == nullptr past the end
+DbgBuf dbg_buf(const sac_learner* h, int which) {
+  static const sac_learner none{};
+  const sac_learner& s = h ? *h : none;
+  const long long Np = s.Np, NK = (long long)s.N * s.K;
+  const DbgBuf tab[] = {
+      {"xs", s.xs, Np, s.Dp, 0}, {"xs1", s.xs1, Np, s.Dp, 0}, {"xc", s.xc, Np, s.Cp, 0},
+      {"xt", s.xt, Np, s.Cp, 0}, {"xp", s.xp, Np, s.Cp, 0}, {"xst", s.xst, s.Dt, Np, 0},
+      {"xct", s.xct, s.Ct, Np, 0},
+      {"hta1", s.hta1, Np, H, 0}, {"hta2", s.hta2, Np, H, 0}, {"ha1", s.ha1, Np, H, 0},
+      {"ha2", s.ha2, Np, H, 0}, {"hb1", s.hb1, Np, H, 0}, {"hb2", s.hb2, Np, H, 0},
+      {"hc1_0", s.hc1[0], Np, H, 0}, {"hc1_1", s.hc1[1], Np, H, 0},
+      {"hc2_0", s.hc2[0], Np, H, 0}, {"hc2_1", s.hc2[1], Np, H, 0},
+      {"htc1_0", s.htc1[0], Np, H, 0}, {"htc1_1", s.htc1[1], Np, H, 0},
+      {"htc2_0", s.htc2[0], Np, H, 0}, {"htc2_1", s.htc2[1], Np, H, 0},
+      {"hp1_0", s.hp1[0], Np, H, 0}, {"hp1_1", s.hp1[1], Np, H, 0},
+      {"hp2_0", s.hp2[0], Np, H, 0}, {"hp2_1", s.hp2[1], Np, H, 0},
+      {"hc1t_0", s.hc1t[0], HT, Np, 0}, {"hc1t_1", s.hc1t[1], HT, Np, 0},
+      {"hc2t_0", s.hc2t[0], HT, Np, 0}, {"hc2t_1", s.hc2t[1], HT, Np, 0},
+      {"ha1t", s.ha1t, HT, Np, 0}, {"ha2t", s.ha2t, HT, Np, 0},
+      {"dh2_0", s.dh2[0], Np, H, 0}, {"dh2_1", s.dh2[1], Np, H, 0},
+      {"dh2t_0", s.dh2t[0], H, Np, 0}, {"dh2t_1", s.dh2t[1], H, Np, 0},
+      {"dhc1t_0", s.dhc1t[0], H, Np, 0}, {"dhc1t_1", s.dhc1t[1], H, Np, 0},
+      {"dhp2_0", s.dhp2[0], Np, H, 0}, {"dhp2_1", s.dhp2[1], Np, H, 0},
+      {"dhp1_0", s.dhp1[0], Np, H, 0}, {"dhp1_1", s.dhp1[1], Np, H, 0},
+      {"dqt_0", s.dqt[0], 16, Np, 0}, {"dqt_1", s.dqt[1], 16, Np, 0},
+      {"dha2", s.dha2, Np, H, 0}, {"dha2t", s.dha2t, H, Np, 0}, {"dha1t", s.dha1t, H, Np, 0},
+      {"gmt", s.gmt, 16, Np, 0}, {"gut", s.gut, 16, Np, 0},
+      {"q1", s.q1, 1, Np, 1}, {"q2", s.q2, 1, Np, 1}, {"logp1", s.logp1, 1, Np, 1},
+      {"logp", s.logp, 1, Np, 1}, {"logp2", s.logp2, 1, Np, 1}, {"save", s.save, 4, NK, 1},
+      {"rowm", s.rowm, 8, Np, 1}, {"eps", s.eps, 3, NK, 1}, {"wmax", s.wmax, 1, 4, 1},
+      {"sq_c", s.sq_c, 1, s.nsq_c, 1}, {"sq_a", s.sq_a, 1, s.nsq_a, 1},
+      {"ka_w1", s.ka.w1, H, s.Dp, 0}, {"ka_w2", s.ka.w2, H, H, 0}, {"ka_w2t", s.ka.w2t, H, H, 0},
+      {"kta_w1", s.kta.w1, H, s.Dp, 0}, {"kta_w2", s.kta.w2, H, H, 0},
+      {"kq0_w1", s.kq[0].w1, H, s.Cp, 0}, {"kq0_w2", s.kq[0].w2, H, H, 0},
+      {"kq0_w2t", s.kq[0].w2t, H, H, 0},
+      {"kq1_w1", s.kq[1].w1, H, s.Cp, 0}, {"kq1_w2", s.kq[1].w2, H, H, 0},
+      {"kq1_w2t", s.kq[1].w2t, H, H, 0},
+      {"ktq0_w1", s.ktq[0].w1, H, s.Cp, 0}, {"ktq0_w2", s.ktq[0].w2, H, H, 0},
+      {"ktq1_w1", s.ktq[1].w1, H, s.Cp, 0}, {"ktq1_w2", s.ktq[1].w2, H, H, 0},
+  };
+  const int n = (int)(sizeof(tab) / sizeof(tab[0]));
+  if (which < 0 || which >= n) return DbgBuf{nullptr, nullptr, 0, 0, 0};
+  return tab[which];
+}
+
 }  // namespace
 
 extern "C" {
@@ -1017,6 +1074,29 @@ int sac_q_forward(sac_learner* h, const float* obs, const float* act, int n, int
   hipStream_t st = (hipStream_t)stream;
   return h->bf16 ? enqueue_q_forward<__bf16>(h, obs, act, n, target != 0, q1, q2, st)
                  : enqueue_q_forward<float>(h, obs, act, n, target != 0, q1, q2, st);
+}
+
+const char* sac_debug_info(sac_learner* h, int which, int* rows, int* ld, int* is_f32) {
+  const DbgBuf b = dbg_buf(h, which);
+  if (rows) *rows = (int)b.rows;
+  if (ld) *ld = (int)b.ld;
+  if (is_f32) *is_f32 = b.f32;
+  return b.name;
+}
+
+int sac_debug_read(sac_learner* h, int which, void* dst, size_t bytes, void* stream) {
+  if (!h || !dst) return fail(IMPALA_E_INVALID, "sac_debug_read: null argument");
+  const DbgBuf b = dbg_buf(h, which);
+  if (!b.name || !b.p) return fail(IMPALA_E_INVALID, "sac_debug_read: no such buffer");
+  const size_t want = (size_t)b.rows * (size_t)b.ld * (b.f32 ? 4 : h->esz);
+  if (bytes != want)
+    return fail(IMPALA_E_INVALID, "sac_debug_read: " + std::string(b.name) + " holds " +
+                                      std::to_string(want) + " bytes, not " + std::to_string(bytes));
+  SCK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  SCK(hipMemcpyAsync(dst, b.p, bytes, hipMemcpyDeviceToHost, st));
+  SCK(hipStreamSynchronize(st));
+  return 0;
 }
 
 int sac_phase_count(void) { return P_COUNT; }

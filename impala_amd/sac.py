@@ -359,6 +359,32 @@ class SACEngine(_lib.NativeHandle):
                    "sac_q_forward")
         return q1, q2
 
+    @staticmethod
+    def debug_names() -> List[str]:
+        """The workspace buffers ``debug_tensor`` exports (``sac_debug_info``)."""
+        L, out, i = _lib.lib(), [], 0
+        while True:
+            name = L.sac_debug_info(None, i, None, None, None)
+            if name is None:
+                return out
+            out.append(name.decode())
+            i += 1
+
+    def debug_tensor(self, name: str) -> np.ndarray:
+        """One workspace buffer of the last step as it lies in memory (``sac_debug_read``; a host
+        sync): numpy float32 [rows, leading dimension], the padding intact.  bf16 buffers are
+        widened exactly."""
+        which = self.debug_names().index(name)
+        rows, ld, f32 = C.c_int(), C.c_int(), C.c_int()
+        _lib.lib().sac_debug_info(self._h, which, C.byref(rows), C.byref(ld), C.byref(f32))
+        dt = torch.float32 if f32.value or self.dtype == "fp32" else torch.bfloat16
+        buf = torch.empty(rows.value, ld.value, dtype=dt)
+        torch.cuda.synchronize(self.device)
+        _lib.check(_lib.lib().sac_debug_read(self._h, which, _lib.ptr(buf),
+                                             buf.numel() * buf.element_size(), _lib.stream_ptr(None)),
+                   "sac_debug_read")
+        return buf.float().numpy()
+
     # live per-phase timer (bench roofline)
     @staticmethod
     def phase_names() -> List[str]:

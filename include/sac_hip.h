@@ -140,7 +140,18 @@ const char* sac_phase_name(int phase);
 int sac_timer_start(sac_learner* h, int phase, int max_launches);
 int sac_timer_read(sac_learner* h, float* total_ms, int* launches);
 
-/* Uniform replay sampling in HBM (UniformSampler over keys [0, size); without replacement
+/* Test / inspection entries (host code: a table and one copy, no kernel).  The step's workspace
+ * is a set of named buffers, ids 0 .. count - 1: the packed operands and their transposed copies,
+ * every hidden activation and gradient tile (row-major and transposed), the fp32 scratch rows, the
+ * two norm-slot arrays and the kernel-layout weights of the four networks.
+ * sac_debug_info returns the name of buffer `which` (NULL past the last id) and, with a handle,
+ * its rows, leading dimension (elements) and whether its elements are fp32 (else the handle's
+ * compute type).  sac_debug_read copies the raw buffer, padding included: rows * ld elements,
+ * `bytes` must be exactly that; it synchronises `stream`. */
+const char* sac_debug_info(sac_learner* h, int which, int* rows, int* ld, int* is_f32);
+int sac_debug_read(sac_learner* h, int which, void* dst, size_t bytes, void* stream);
+
+/* Uniform replay sampling in HBM(UniformSampler over keys [0, size); without replacement
  * when n <= size, as impala_amd.replay.ReplayBuffer): idx [n] int64 drawn from a counter-based
  * generator (seed, counter), probabilities [n] = 1/size, then row idx[i] of each of up to 8
  * fields src[f] (rows of row_bytes[f] bytes, any size) copied to row i of dst[f]. */

@@ -27,8 +27,11 @@ Bounds (r = the float64 reference of a stage's output on the step's own inputs):
 
 The Ape-X DQN step (tests/test_gpu_dqn_stages.py) is held to the same bounds; its cases, the
 priorities' and q's bounds and the handling of an undecided rounding of dH are in the section
-after these; the IQN actor path's forward (tests/test_gpu_iqn_stages.py) is the last section.
+after these; the IQN actor path's forward (tests/test_gpu_iqn_stages.py) follows, and the SAC step
+(tests/test_gpu_sac_stages.py, references oracle/sac_stages.py) is the last section.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -524,4 +527,510 @@ def hold_iqn_forward(shape, got, mask1, q, quant, label, cap=CAP):
     if trunk:
         bad += hold_mask(mask1, got["act1"], label)
     bad += hold_dqn_q(np.asarray(q).reshape(-1, A), got["heads"], A, label)
+    return bad
+
+
+# ------------------------------------------------------------------------------ SAC step
+# The SAC learner's step (tests/test_gpu_sac_stages.py; CPU: tests/test_sac_stages_host.py), every
+# launch of the per-layer path against oracle/sac_stages.py on that launch's own exported inputs.
+# A case is (N, D, K); Cp = rup(D + K, 32) and Dp = rup(D, 32) pick the first-layer regime of the
+# chain kernels (<= 64 prefetched, <= 256 wide, above: per-layer path only).
+SAC_CASES = [
+    (1, 1, 1),       # one transition; uniform weights
+    (16, 3, 1),      # exactly one row block
+    (17, 11, 16),    # one row into the second row block; K = MAXK
+    (37, 26, 6),     # D + K = 32 = Cp (no padding) while Dp pads
+    (33, 58, 6),     # Cp = 64, the small regime's limit
+    (37, 60, 6),     # Dp = 64 small, Cp = 96 wide: mixed regimes
+    (100, 111, 8),   # both first layers wide
+    (37, 240, 16),   # Cp = 256, the fused limit
+    (37, 241, 16),   # Cp = 288: per-layer path only
+    (33, 760, 4),    # nsq_c = 2114 > 2048; max_grad_norm 0.05: the clip is active
+    (520, 17, 6),    # the smallest probability at index 519
+]
+SAC_CLIP_CASE, SAC_CLIP_NORM = (33, 760, 4), 0.05
+SAC_TAIL_CASE = (520, 17, 6)
+SAC_NO_ALPHA = ((520, 17, 6), "fp32")  # tune_alpha=False in this dtype of this case
+SAC_LA0 = -0.3
+SAC_PARAM_ATOL, SAC_LA_ATOL = 2e-6, 1e-6  # test_gpu_sac.py's header
+SAC_SLOT_RTOL = 1e-5
+SAC_MAX_TIES = 1
+# the batch seed of a case (1000 N + D unless the float32 stand-in exceeded a quarter of a cap
+# there, or the reference's actor loss had an undecided row: chosen on the CPU by
+# test_sac_stages_host.py's conditions alone).  (37, 26, 6) at 37026: row 26 undecided in bf16;
+# (37, 240, 16) at 37240: one of gu's 592 elements != RNE, 1.7e-3 > CAP / 4; (33, 760, 4) at
+# 33760..33763: a first layer's fp32 sum over 764 inputs at 2.5e-6 .. 2.7e-6 normwise on the
+# stand-in, just over a quarter of 1e-5.
+SAC_SEEDS = {(37, 26, 6): 37027, (37, 240, 16): 37241, (33, 760, 4): 33764}
+# (the exported gradient blocks are the clipped ones, so the clip -- the slots' sum against the
+# exported gradient's own norm, which needs no reference block -- is held before them)
+SAC_STAGES = ("layout", "pack", "fwd", "heads", "target_critic", "critic_loss", "critic_bwd",
+              "critic_clip", "critic_wgrad", "critic_adam", "weights", "actor_q", "actor_loss",
+              "actor_q_dgrad", "actor_head_bwd", "actor_bwd", "actor_clip", "actor_wgrad",
+              "actor_adam", "alpha", "metrics")
+SAC_KEYS = ("qf1_loss", "qf2_loss", "qf1", "qf2", "qf_loss", "critic_grad_norm", "actor_loss",
+            "actor_std", "actor_grad_norm", "alpha_loss", "alpha")
+
+
+def sac_kw(case, dtype):
+    """Engine / reference options of a case in one dtype ("fp32" | "bf16")."""
+    return dict(max_grad_norm=SAC_CLIP_NORM if case == SAC_CLIP_CASE else 40.0,
+                tune_alpha=(case, dtype) != SAC_NO_ALPHA)
+
+
+_SAC_IN = {}
+
+
+def sac_inputs(case, step=0):
+    """-> dict(actor0, critic0, tactor0, tcritic0 (flat float32), batch, probs, eps) of a case.
+    Parameters: the reference's initialisation (oracle/sac_cpu.py, seeds 3 / 4) with every bias
+    moved off 0 and the targets nudged off the online networks, so that no stage can drop a bias
+    or read the wrong network and pass.  step = 1: the second step's batch."""
+    from oracle import sac_cpu
+    from oracle import sac_stages as sst
+    if (case, step) in _SAC_IN:
+        return _SAC_IN[(case, step)]
+    N, D, K = case
+    with torch.random.fork_rng(devices=[]):
+        a0 = sac_cpu.flat(sac_cpu.make_models(D, K, seed=3)[0].parameters())
+        c0 = sac_cpu.flat(sac_cpu.make_models(D, K, seed=4)[1].critic.parameters())
+    rng = np.random.default_rng(5)
+
+    def nudge(flat, shapes, reps):
+        off = 0
+        for _ in range(reps):
+            for _, s in shapes:
+                k = int(np.prod(s)) if len(s) else 1
+                if len(s) <= 1:
+                    flat[off:off + k] += (0.02 * rng.standard_normal(k)).astype(np.float32)
+                off += k
+        assert off == flat.size
+    # (a critic's w3 is a vector too: nudged with the biases, harmlessly)
+    nudge(a0, sst.actor_shapes(D, K), 1)
+    nudge(c0, sst.q_shapes(D, K), 2)
+    ta0 = a0 + (0.01 * rng.standard_normal(a0.size)).astype(np.float32) * np.abs(a0).max()
+    tc0 = c0 + (0.01 * rng.standard_normal(c0.size)).astype(np.float32) * np.abs(c0).max()
+    seed = SAC_SEEDS.get(case, 1000 * N + D) + 7919 * step
+    batch = sac_cpu.synthetic_batch(N, D, K, seed)
+    r2 = np.random.default_rng(seed + 1)
+    probs = None if N == 1 else (r2.uniform(0.5, 2.0, N) / 1000).astype(np.float32)
+    if case == SAC_TAIL_CASE:  # the largest weight where only a later round of the loops sees it
+        probs[N - 1] = np.float32(0.5) * probs.min()
+    eps = r2.standard_normal((3, N, K)).astype(np.float32)
+    v = dict(actor0=a0, critic0=c0, tactor0=ta0.astype(np.float32), tcritic0=tc0.astype(np.float32),
+             batch=batch, probs=probs, eps=eps)
+    _SAC_IN[(case, step)] = v
+    return v
+
+
+def sac_reference(case, dtype, given=None, quant=None, torch_dtype=torch.float64, defect=None):
+    from oracle import sac_stages as sst
+    i = sac_inputs(case)
+    return sst.run(case[1], case[2], i["actor0"], i["critic0"], SAC_LA0, i["batch"], i["probs"],
+                   i["eps"], tactor0=i["tactor0"], tcritic0=i["tcritic0"], given=given,
+                   quant=(dtype == "bf16") if quant is None else quant, dtype=torch_dtype,
+                   defect=defect, **sac_kw(case, dtype))
+
+
+def _rup(x, m):
+    return (x + m - 1) // m * m
+
+
+def sac_dims(case):
+    N, D, K = case
+    return dict(N=N, D=D, K=K, DK=D + K, Np=_rup(N, 32), Dp=_rup(D, 32), Cp=_rup(D + K, 32),
+                Dt=_rup(D + 1, 16), Ct=_rup(D + K + 1, 16))
+
+
+def sac_export(run_out, case, dtype, defect=None):
+    """What a device whose kernels computed `run_out` (a chained float32 run: the stand-in) would
+    export: (raw workspace buffers by sac_debug_info's names, padded as the kernels lay them out;
+    the bound state after the step).  defect "pad_col": a non-zero padded column in xct."""
+    from oracle import sac_stages as sst
+    d = sac_dims(case)
+    N, D, K, DK, Np = d["N"], d["D"], d["K"], d["DK"], d["Np"]
+    t = run_out["t"]
+    raw = {}
+
+    def rm(x, ld):  # row-major [Np][ld]
+        b = np.zeros((Np, ld), np.float32)
+        b[:N, :x.shape[1]] = x
+        return b
+
+    def tr(x, rows, ones=False):  # transposed [rows][Np]
+        b = np.zeros((rows, Np), np.float32)
+        b[:x.shape[1], :N] = x.T
+        if ones:
+            b[x.shape[1], :N] = 1.0
+        return b
+    raw["xs"], raw["xs1"] = rm(t["xs"], d["Dp"]), rm(t["xs1"], d["Dp"])
+    for k in ("xc", "xt", "xp"):
+        raw[k] = rm(t[k], d["Cp"])
+    raw["xst"], raw["xct"] = tr(t["xs"], d["Dt"], True), tr(t["xc"], d["Ct"], True)
+    if defect == "pad_col":
+        raw["xct"][1 % DK, Np - 1] = 0.5
+    for k in sst.HID:
+        if k in t:
+            raw[k] = rm(t[k], sst.H)
+    for k in ("hc1_0", "hc1_1", "hc2_0", "hc2_1", "ha1", "ha2"):
+        n, q = (k.split("_") + [None])[:2]
+        raw[n + "t" + ("_" + q if q else "")] = tr(t[k], 272, True)
+    for q in ("0", "1"):
+        raw["dh2_" + q], raw["dh2t_" + q] = rm(t["dh2_" + q], sst.H), tr(t["dh2_" + q], sst.H)
+        raw["dhc1t_" + q] = tr(t["dhc1_" + q], sst.H)
+        raw["dhp2_" + q], raw["dhp1_" + q] = rm(t["dhp2_" + q], sst.H), rm(t["dhp1_" + q], sst.H)
+        raw["dqt_" + q] = tr(t["dq_" + q][:, None], 16)
+    raw["dha2"], raw["dha2t"] = rm(t["dha2"], sst.H), tr(t["dha2"], sst.H)
+    raw["dha1t"], raw["gmt"], raw["gut"] = tr(t["dha1"], sst.H), tr(t["gm"], 16), tr(t["gu"], 16)
+    for k in ("q1", "q2", "logp1", "logp", "logp2"):
+        if k in t:
+            raw[k] = np.zeros((1, Np), np.float32)
+            raw[k][0, :N] = t[k]
+    raw["save"] = t["save"].reshape(4, N * K).astype(np.float32)
+    raw["rowm"] = np.zeros((8, Np), np.float32)
+    raw["rowm"][:6, :N] = t["rowm"]
+    f32 = lambda x: np.asarray(x, np.float32)  # noqa: E731
+    cg = np.concatenate([run_out["cgrads"][k].reshape(-1) for k in sst.C_BLOCKS])
+    ag = np.concatenate([run_out["agrads"][k].reshape(-1) for k in sst.A_BLOCKS])
+    raw["sq_c"] = np.array([[float(cg @ cg), 0.0]], np.float32)
+    raw["sq_a"] = np.array([[float(ag @ ag), 0.0]], np.float32)
+    la = run_out["la"]
+    met = np.zeros(12, np.float32)
+    met[:11] = [run_out["met"][k] for k in SAC_KEYS]
+    state = dict(actor=f32(run_out["actor1"]), critic=f32(run_out["critic1"]),
+                 tactor=f32(run_out["tactor1"]), tcritic=f32(run_out["tcritic1"]),
+                 actor_grad=f32(ag * run_out["acoef"]), critic_grad=f32(cg * run_out["ccoef"]),
+                 actor_m=f32(run_out["am"]), actor_v=f32(run_out["av"]), critic_m=f32(run_out["cm"]),
+                 critic_v=f32(run_out["cv"]), la_buf=f32([la["la"], la["g"], la["m"], la["v"]]),
+                 metrics=met, prio=f32(t["prio"]))
+    q_ = (lambda x: rs.rne_bf16(torch.from_numpy(f32(x))).numpy()) if dtype == "bf16" else f32
+    for name, flat, split, in1 in (("ka", state["actor"], "a", D), ("kta", state["tactor"], "a", D),
+                                   ("kq", state["critic"], "c", DK), ("ktq", state["tcritic"], "c", DK)):
+        nets = [sst.split_actor(flat, D, K)] if split == "a" else sst.split_critic(flat, D, K)
+        for q, P in enumerate(nets):
+            pre = name if split == "a" else f"{name}{q}"
+            w1 = np.zeros((sst.H, _rup(in1, 32)), np.float32)
+            w1[:, :in1] = q_(P["w1"].numpy())
+            raw[pre + "_w1"], raw[pre + "_w2"] = w1, q_(P["w2"].numpy())
+            if name in ("ka", "kq"):
+                raw[pre + "_w2t"] = np.ascontiguousarray(raw[pre + "_w2"].T)
+    return raw, state
+
+
+class _Bad(list):
+    """Violations, each under the stage that owns it."""
+
+    def add(self, stage, msg):
+        assert stage in SAC_STAGES
+        self.append((stage, msg))
+
+    def first_stage(self):
+        return min((SAC_STAGES.index(s) for s, _ in self), default=None)
+
+
+def sac_logical(raw, case, tune_alpha, bad):
+    """Strip the padding of the exported buffers -> the logical tensors (oracle/sac_stages.py).
+    Holds on the way (stage "layout"): every padded row or column is exactly 0, every transposed
+    copy equals its row-major tensor bit for bit, every ones row is 1."""
+    from oracle import sac_stages as sst
+    d = sac_dims(case)
+    N, D, K, DK, Np = d["N"], d["D"], d["K"], d["DK"], d["Np"]
+    t = {}
+
+    def zero(name, buf, *regions):
+        n = sum(int(np.count_nonzero(buf[r])) for r in regions)
+        if n:
+            bad.add("layout", f"{name}: {n} non-zero padded elements")
+
+    def rm(name, cols):
+        b = raw[name]
+        assert b.shape[0] == Np, (name, b.shape)
+        zero(name, b, np.s_[N:, :], np.s_[:N, cols:])
+        return b[:N, :cols]
+
+    def tr(name, rows, of=None, ones=False):
+        b = raw[name]
+        assert b.shape[1] == Np, (name, b.shape)
+        zero(name, b, np.s_[:, N:], np.s_[rows + (1 if ones else 0):, :N])
+        if ones and not np.all(b[rows, :N] == 1.0):
+            bad.add("layout", f"{name}: the ones row is not 1")
+        x = np.ascontiguousarray(b[:rows, :N].T)
+        if of is not None and not np.array_equal(x, of):
+            bad.add("layout", f"{name}: {int(np.sum(x != of))} elements differ from the row-major tensor")
+        return x
+    t["xs"], t["xs1"] = rm("xs", D), rm("xs1", D)
+    for k in ("xc", "xt", "xp"):
+        t[k] = rm(k, DK)
+    tr("xst", D, t["xs"], True)
+    tr("xct", DK, t["xc"], True)
+    for k in sst.HID:
+        if k in raw and (tune_alpha or k not in ("hb1", "hb2")):
+            t[k] = rm(k, sst.H)
+    for k in ("hc1_0", "hc1_1", "hc2_0", "hc2_1", "ha1", "ha2"):
+        n, q = (k.split("_") + [None])[:2]
+        tr(n + "t" + ("_" + q if q else ""), sst.H, t[k], True)
+    for q in ("0", "1"):
+        t["dh2_" + q] = rm("dh2_" + q, sst.H)
+        tr("dh2t_" + q, sst.H, t["dh2_" + q])
+        t["dhc1_" + q] = tr("dhc1t_" + q, sst.H)
+        t["dhp2_" + q], t["dhp1_" + q] = rm("dhp2_" + q, sst.H), rm("dhp1_" + q, sst.H)
+        t["dq_" + q] = tr("dqt_" + q, 1)[:, 0]
+    t["dha2"] = rm("dha2", sst.H)
+    tr("dha2t", sst.H, t["dha2"])
+    t["dha1"], t["gm"], t["gu"] = tr("dha1t", sst.H), tr("gmt", K), tr("gut", K)
+    for k in ("q1", "q2", "logp1", "logp") + (("logp2",) if tune_alpha else ()):
+        zero(k, raw[k], np.s_[:, N:])
+        t[k] = raw[k][0, :N]
+    t["save"] = raw["save"].reshape(4, N, K)
+    zero("rowm", raw["rowm"], np.s_[:, N:], np.s_[6:, :N])
+    t["rowm"] = raw["rowm"][:6, :N]
+    return t
+
+
+_SAC_STAGE_OF = {}
+for _k in ("hta1", "hta2", "ha1", "ha2", "hc1_0", "hc1_1", "hc2_0", "hc2_1"):
+    _SAC_STAGE_OF[_k] = "fwd"
+for _k in ("xt", "xp", "logp1", "logp", "save", "q1", "q2"):
+    _SAC_STAGE_OF[_k] = "heads"
+for _k in ("htc1_0", "htc1_1", "htc2_0", "htc2_1"):
+    _SAC_STAGE_OF[_k] = "target_critic"
+for _k in ("dq_0", "dq_1", "dh2_0", "dh2_1", "prio"):
+    _SAC_STAGE_OF[_k] = "critic_loss"
+for _k in ("dhc1_0", "dhc1_1"):
+    _SAC_STAGE_OF[_k] = "critic_bwd"
+for _k in ("hp1_0", "hp1_1", "hp2_0", "hp2_1"):
+    _SAC_STAGE_OF[_k] = "actor_q"
+for _k in ("dhp2_0", "dhp2_1"):
+    _SAC_STAGE_OF[_k] = "actor_loss"
+for _k in ("dhp1_0", "dhp1_1"):
+    _SAC_STAGE_OF[_k] = "actor_q_dgrad"
+for _k in ("gm", "gu", "dha2"):
+    _SAC_STAGE_OF[_k] = "actor_head_bwd"
+_SAC_STAGE_OF["dha1"] = "actor_bwd"
+for _k in ("hb1", "hb2", "logp2"):
+    _SAC_STAGE_OF[_k] = "alpha"
+SAC_ROWM = ("qf1_term", "qf2_term", "q1", "q2", "actor_term", "std_mean")
+SAC_ROWM_STAGE = ("critic_loss", "critic_loss", "critic_loss", "critic_loss", "actor_loss", "heads")
+SAC_SAVE = ("std", "y", "x-mean", "tanh_u")
+
+
+def _hold_one(bad, fig, stage, name, g, r, as_t, label, cap):
+    """One tensor under the bf16 (as_t) or the fp32 bound; figures into `fig` and printed."""
+    g, r = np.asarray(g, np.float64), np.asarray(r, np.float64)
+    if not np.isfinite(g).all():
+        bad.add(stage, f"{name}: not finite")
+        return
+    if as_t:
+        worst, share, wu = rs.bf16_figures(g, r)
+        fig[name] = (worst, share)
+        print(f"{label} {name:10s} worst |d| / (ulp + 1e-5 (|r| + rms)) {worst:.3f}, share != RNE "
+              f"{share:.2e} (worst {wu:.2f} ulp)")
+        if worst > 1.0:
+            bad.add(stage, f"{name}: element bound x{worst:.3f}")
+        if share > cap:
+            bad.add(stage, f"{name}: mismatch share {share:.2e} > {cap:.2e}")
+    else:
+        w = rs.f32_figures(g, r)
+        fig[name] = (w,)
+        print(f"{label} {name:10s} normwise {w:.2e}")
+        if w > F32_NORMWISE * (cap / CAP):
+            bad.add(stage, f"{name}: normwise {w:.2e}")
+
+
+def hold_sac_step(raw, state, case, dtype, label, cap=CAP):
+    """Every stage of one SAC step (from zero Adam state) on the step's own exports -> (the
+    violations, each under its stage; the figures).  cap: CAP for the device, STAND_IN_CAP for the
+    stand-in, which scales every other bound by the same quarter."""
+    from oracle import sac_stages as sst
+    N, D, K = case
+    quant = dtype == "bf16"
+    kw = sac_kw(case, dtype)
+    tune = kw["tune_alpha"]
+    scale = cap / CAP
+    i = sac_inputs(case)
+    bad, fig = _Bad(), {}
+    t = sac_logical(raw, case, tune, bad)
+    # ---- pack: exact
+    s, a, r_, s1, _ = i["batch"]
+    p = sst.pack(*(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64).reshape(N, -1))
+                   for x in (s, a, s1)), quant)
+    for k, want in (("xs", p["xs"]), ("xs1", p["xs1"]), ("xc", p["xc"]), ("xt", p["xt_obs"]),
+                    ("xp", p["xp_obs"])):
+        want = want.numpy().astype(np.float32)
+        n = int(np.sum(t[k][:, :want.shape[1]] != want))
+        if n:
+            bad.add("pack", f"{k}: {n} elements are not RNE of the fp32 source")
+    print(f"{label} pack       exact")
+    given = dict(t, critic1=state["critic"], actor1=state["actor"], critic_grad=state["critic_grad"],
+                 actor_grad=state["actor_grad"])
+    ref = sac_reference(case, dtype, given=given)
+    # ---- tensors, in launch order
+    names = [k for k in sst.T_TENSORS + sst.F32_TENSORS if k in _SAC_STAGE_OF and (tune or _SAC_STAGE_OF[k] != "alpha")]
+    names.sort(key=lambda k: SAC_STAGES.index(_SAC_STAGE_OF[k]))
+    for k in names:
+        g = state["prio"] if k == "prio" else t[k]
+        if k == "save":
+            for j, nm in enumerate(SAC_SAVE):
+                _hold_one(bad, fig, "heads", "save." + nm, g[j], ref["t"][k][j], False, label, cap)
+            continue
+        cols = np.s_[:, D:] if k in ("xt", "xp") else np.s_[...]
+        _hold_one(bad, fig, _SAC_STAGE_OF[k], k, g[cols], ref["t"][k][cols], quant and k in sst.T_TENSORS,
+                  label, cap)
+    for j, nm in enumerate(SAC_ROWM):
+        _hold_one(bad, fig, SAC_ROWM_STAGE[j], "rowm." + nm, t["rowm"][j], ref["t"]["rowm"][j], False,
+                  label, cap)
+    und = ref["undecided"]
+    fig["undecided"] = len(und)
+    print(f"{label} actor loss: {len(und)} undecided rows {und[:4]} (assigned {ref['assign']})")
+    if len(und) > SAC_MAX_TIES:
+        bad.add("actor_loss", f"{len(und)} undecided rows > {SAC_MAX_TIES}")
+    # ---- gradient blocks (the reference scaled by its own clip coefficient), clip, Adam
+    for net, blocks, gk, names_b, sq in (("critic", sst.critic_blocks, "cgrads", sst.C_BLOCKS, "sq_c"),
+                                         ("actor", sst.actor_blocks, "agrads", sst.A_BLOCKS, "sq_a")):
+        got = blocks(state[net + "_grad"], D, K)
+        rnorm = ref["cnorm" if net == "critic" else "anorm"]
+        coef = ref["ccoef" if net == "critic" else "acoef"]
+        line = []
+        for k in names_b:
+            v = rs.rel_l2(got[k], ref[gk][k] * coef)
+            line.append(f"{k} {v:.1e}")
+            fig[f"{net}.{k}"] = (v,)
+            if not v <= BLOCK_RL2 * scale:
+                bad.add(net + "_wgrad", f"block {k}: rel-L2 {v:.2e}")
+        print(f"{label} {net} blocks rel-L2: " + ", ".join(line))
+        slots = float(np.sum(np.asarray(raw[sq], np.float64)))
+        g = np.asarray(state[net + "_grad"], np.float64)
+        c_dev = sst.clip_coef(math.sqrt(slots), kw["max_grad_norm"])
+        v = abs(float(g @ g) - c_dev ** 2 * slots) / max(c_dev ** 2 * slots, 1e-300)
+        mi = 5 if net == "critic" else 8
+        gn = abs(float(state["metrics"][mi]) - rnorm) / rnorm
+        gs = abs(float(state["metrics"][mi]) - math.sqrt(slots)) / math.sqrt(slots)
+        fig[f"{net}.clip"] = (v, gn, coef)
+        print(f"{label} {net} clip: coefficient {coef:.4f} (norm {rnorm:.4e}); |g|^2 against coef^2 x the "
+              f"slots' sum {v:.1e}; grad-norm metric against the reference {gn:.1e}, the slots {gs:.1e}")
+        if not v <= SAC_SLOT_RTOL:
+            bad.add(net + "_clip", f"|g|^2 against coef^2 x the slots' sum: {v:.2e}")
+        if not gs <= GRAD_NORM_RTOL * scale:
+            bad.add(net + "_clip", f"grad-norm metric against the slots: {gs:.2e}")
+        if not gn <= GRAD_NORM_RTOL * scale:
+            bad.add(net + "_wgrad", f"grad-norm metric against the reference: {gn:.2e}")
+        line = []
+        for k, gotv, want, tol in ((net, state[net], ref[net + "1"], SAC_PARAM_ATOL),
+                                   ("t" + net, state["t" + net], ref["t" + net + "1"], SAC_PARAM_ATOL)):
+            v = float(np.max(np.abs(np.asarray(gotv, np.float64) - want)))
+            line.append(f"{k} {v:.1e}")
+            fig[f"{k}.adam"] = (v,)
+            if not v <= tol * scale:
+                bad.add(net + "_adam", f"{k} after Adam: max |d| {v:.2e}")
+        for k, want in ((net + "_m", ref[net[0] + "m"]), (net + "_v", ref[net[0] + "v"])):
+            v = rs.f32_figures(state[k], want)
+            line.append(f"{k} {v:.1e}")
+            if not v <= F32_NORMWISE * scale:
+                bad.add(net + "_adam", f"{k}: normwise {v:.2e}")
+        print(f"{label} {net} Adam (given the device's clipped gradient) max |d|: " + ", ".join(line))
+    # ---- the re-emitted kernel layouts: exact
+    q_ = (lambda x: rs.rne_bf16(torch.from_numpy(np.asarray(x, np.float32))).numpy()) if quant else \
+        (lambda x: np.asarray(x, np.float32))
+    for name, flat, split, in1 in (("ka", state["actor"], "a", D), ("kta", state["tactor"], "a", D),
+                                   ("kq", state["critic"], "c", D + K), ("ktq", state["tcritic"], "c", D + K)):
+        nets = [sst.split_actor(flat, D, K, torch.float32)] if split == "a" else \
+            sst.split_critic(flat, D, K, torch.float32)
+        for q, P in enumerate(nets):
+            pre = name if split == "a" else f"{name}{q}"
+            w1 = raw[pre + "_w1"]
+            n = int(np.sum(w1[:, :in1] != q_(P["w1"].numpy()))) + int(np.count_nonzero(w1[:, in1:]))
+            n += int(np.sum(raw[pre + "_w2"] != q_(P["w2"].numpy())))
+            if pre + "_w2t" in raw:
+                n += int(np.sum(raw[pre + "_w2t"] != raw[pre + "_w2"].T))
+            if n:
+                bad.add("weights", f"{pre}: {n} elements are not RNE of the fp32 master (or padding != 0)")
+    print(f"{label} weights    exact")
+    # ---- alpha and the metrics
+    la = np.asarray(state["la_buf"], np.float64)
+    if tune:
+        rl = ref["la"]
+        v = abs(la[0] - rl["la"])
+        fig["log_alpha"] = (v,)
+        print(f"{label} log_alpha |d| {v:.1e}; grad rel {abs(la[1] - rl['g']) / abs(rl['g']):.1e}")
+        if not v <= SAC_LA_ATOL * scale:
+            bad.add("alpha", f"log_alpha: |d| {v:.2e}")
+        for j, k in ((1, "g"), (2, "m"), (3, "v")):
+            if not abs(la[j] - rl[k]) <= MET_RTOL * scale * abs(rl[k]):
+                bad.add("alpha", f"log_alpha {k}: {la[j]} against {rl[k]}")
+    elif la[0] != np.float32(SAC_LA0) or np.any(la[1:] != 0):
+        bad.add("alpha", f"log_alpha moved with tune_alpha off: {la}")
+    line = []
+    for j, k in enumerate(SAC_KEYS):
+        if k.endswith("grad_norm") or (not tune and k in ("alpha_loss", "alpha")):
+            continue
+        v = abs(float(state["metrics"][j]) - ref["met"][k]) / max(abs(ref["met"][k]), 1e-30)
+        line.append(f"{k} {v:.1e}")
+        fig["met." + k] = (v,)
+        if not v <= MET_RTOL * scale:
+            bad.add("metrics", f"metric {k}: {v:.2e}")
+    print(f"{label} metrics rel: " + ", ".join(line))
+    return bad, fig, ref
+
+
+# ---- the policy head where 1 - y^2 is small (sac_policy, forward only)
+SAC_POLICY_CASE = (5, 17, 6)  # n, D, K
+SAC_POLICY_BM = (0.5, 3.0, 6.0, 9.5, -9.5, 12.0)  # fc_mean's bias: |x| > 9 in three columns
+SAC_U = 2.0 ** -24  # fp32's unit roundoff: |fl(a) - a| <= u |a|
+SAC_TANH_ULPS = 4   # |y - tanh x| <= 4 x 2^-24: tanhf within 2 ulp of a value below 1 (spacing 2^-24), doubled
+
+
+def sac_policy_inputs():
+    """-> (actor flat float32 with fc_mean's bias raised, obs [n, D], noise [n, K])."""
+    from oracle import sac_stages as sst
+    n, D, K = SAC_POLICY_CASE
+    a0 = sac_inputs((37, D, K))["actor0"].copy()
+    off = sum(int(np.prod(s)) for _, s in sst.actor_shapes(D, K)[:5])
+    a0[off:off + K] = np.asarray(SAC_POLICY_BM, np.float32)
+    rng = np.random.default_rng(11)
+    return a0, rng.standard_normal((n, D)).astype(np.float32), rng.standard_normal((n, K)).astype(np.float32)
+
+
+def hold_sac_policy(mean, std, y, logp, eps, label, share=1.0):
+    """sac_policy's y and log-prob on the head's own float32 mean and std -> violations.
+
+    x = fl(mean + fl(eps std)) and x - mean = fl(x - mean) are single correctly rounded fp32
+    operations of exported numbers, so they are reproduced exactly here.  y is held to tanh x
+    within SAC_TANH_ULPS.  logp is held to the formula in float64 on (x - mean, std, y):
+        logp = sum_k -A_k - log std_k - log sqrt(2 pi) - L_k,   A = (x - mean)^2 / (2 std^2),
+        L = log z,  z = 1 - y^2 + 1e-6.
+    The kernel's z takes three roundings: fl(y y) errs by at most u y^2 <= u; 1 - fl(y y) is exact
+    where fl(y y) >= 1/2 (Sterbenz) and errs by at most u otherwise; adding 1e-6f errs by u z (the
+    constant itself by 1e-6 u).  So |dz| <= 2 u + u z: RELATIVE to z that is 2 u / z + u, which at
+    z = 1e-6 (y one spacing from 1) is 0.12 -- this is the ill-conditioning, in torch as much as
+    here -- and at y = +-1 exactly is 0 (1 - 1 = 0 and 0 + 1e-6f are exact).  Through the
+    logarithm: |dL| <= -log(1 - |dz| / z) + 2 u |L| (logf within 2 ulp).  The other terms:
+    A takes four roundings (4 u A), log std 2 u |log std|; the 4 K subtractions and additions that
+    build logp err by at most u S each, S = sum_k (A + |log std| + log sqrt(2 pi) + |L|).  The
+    bound is the sum; `share` scales it (1/4 for the stand-in)."""
+    u = SAC_U
+    m32, s32, e32 = (np.asarray(v, np.float32) for v in (mean, std, eps))
+    x32 = (m32 + e32 * s32).astype(np.float32)
+    xm = (x32 - m32).astype(np.float64)
+    sd, yy = s32.astype(np.float64), np.asarray(y, np.float64)
+    bad = []
+    if not all(np.isfinite(np.asarray(v, np.float64)).all() for v in (mean, std, y, logp)):
+        return ["policy: not finite"]
+    dy = float(np.max(np.abs(yy - np.tanh(x32.astype(np.float64)))))
+    z = (1.0 - yy * yy) + 1e-6
+    A, L = xm * xm / (2.0 * sd * sd), np.log(z)
+    want = (-A - np.log(sd) - math.log(math.sqrt(2 * math.pi)) - L).sum(-1)
+    dz = np.where(np.abs(yy) == 1.0, 0.0, 2 * u + u * z)
+    S = (A + np.abs(np.log(sd)) + math.log(math.sqrt(2 * math.pi)) + np.abs(L)).sum(-1)
+    bound = (-np.log1p(-dz / z) + 2 * u * np.abs(L) + 4 * u * A + 2 * u * np.abs(np.log(sd))).sum(-1) \
+        + 4 * yy.shape[1] * u * S
+    w = float(np.max(np.abs(np.asarray(logp, np.float64) - want) / bound))
+    print(f"{label} |x| max {np.abs(x32).max():.2f}, y == +-1 in {int(np.sum(np.abs(yy) == 1.0))} elements, "
+          f"smallest z {z.min():.2e}; |y - tanh x| max {dy / u:.2f} x 2^-24; logp |d| / bound {w:.3f} "
+          f"(bounds {bound.min():.1e} .. {bound.max():.1e})")
+    if not np.abs(x32).max() > 9 or not np.any(np.abs(yy) == 1.0):
+        bad.append("policy: the case does not reach |x| > 9 and y == +-1")
+    if not dy <= SAC_TANH_ULPS * u:
+        bad.append(f"policy: |y - tanh x| {dy / u:.2f} x 2^-24")
+    if not w <= share:
+        bad.append(f"policy: logp bound x{w:.3f}")
     return bad

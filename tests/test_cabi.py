@@ -93,6 +93,7 @@ def test_kernel_entry_points_validate_before_launch():
     assert lib.impala_debug_read(None, 0, None, 4, None) == 1001
     assert lib.dqn_debug_read(None, 0, 0, None, 4, None) == 1001
     assert lib.iqn_debug_read(None, 0, None, 4, None) == 1001
+    assert lib.sac_debug_read(None, 0, None, 4, None) == 1001
     assert lib.dqn_compute_grads(None, None, None) == 1001
 
 
