@@ -434,6 +434,24 @@ def stream_ptr(stream) -> int:
     return int(stream.cuda_stream)
 
 
+def read_debug(read, kind: str, shape, rows: int, bf16: bool, device, stream=None):
+    """The tail the handles' ``debug_tensor`` methods share: ``rows`` rows of ``shape`` with
+    elements of ``kind`` ("T": the compute type, "f32", "u32"), read into a device buffer by
+    ``read(dst pointer, bytes, stream pointer)`` -- the handle's ``*_debug_read`` call with its
+    leading arguments bound and its status checked -- then, after a host sync, a numpy array:
+    the compute type as float32 (exact for bf16), "u32" as uint32."""
+    import numpy as np
+    import torch
+    dt = {"T": torch.bfloat16 if bf16 else torch.float32, "f32": torch.float32,
+          "u32": torch.int32}[kind]
+    buf = torch.empty((rows,) + tuple(shape), dtype=dt, device=device)
+    read(ptr(buf), buf.numel() * buf.element_size(), stream_ptr(stream))
+    (torch.cuda.current_stream() if stream is None else stream).synchronize()
+    if kind == "u32":
+        return buf.cpu().numpy().view(np.uint32)
+    return buf.float().cpu().numpy()
+
+
 def param_count(num_actions: int = 15) -> int:
     return int(lib().impala_param_count(num_actions))
 

@@ -78,11 +78,48 @@ int dqn_check(dqn_learner* h, bool train, bool target) {
   return 0;
 }
 
-int dqn_check_frames(dqn_learner* h, const uint8_t* obs, int n) {
+// ---- shared by the Q-learner handles: dqn_learner, and iqn_learner (iqn.h) ----
+int check_frames(int core_N, const uint8_t* obs, int n) {
   if (!obs) return fail(IMPALA_E_INVALID, "null pointer");
-  if (n < 1 || n > h->core->N) return fail(IMPALA_E_INVALID, "n must be in [1, batch_size]");
+  if (n < 1 || n > core_N) return fail(IMPALA_E_INVALID, "n must be in [1, batch_size]");
   if (((uintptr_t)obs & 15) != 0) return fail(IMPALA_E_INVALID, "obs must be 16-byte aligned");
   return 0;
+}
+
+int check_optim(float lr, float b1, float b2, float eps, float max_norm, float is_exponent) {
+  if (!(lr >= 0.f) || !(eps > 0.f) || !(max_norm > 0.f) || !(b1 >= 0.f && b1 < 1.f) || !(b2 >= 0.f && b2 < 1.f))
+    return fail(IMPALA_E_INVALID, "bad optimizer settings");
+  if (!(is_exponent >= 0.f)) return fail(IMPALA_E_INVALID, "importance_sampling_exponent must be >= 0");
+  return 0;
+}
+
+// The core of a Q-learner: an impala_learner on flat transitions at the 512-wide projection.
+// optim: the handle's optimizer settings, or null where they arrive later (iqn_bind_state).
+int create_q_core(int batch_size, int num_actions, int dtype, const dqn_config* optim, int device,
+                  impala_learner** out) {
+  impala_config ic;
+  impala_config_default(&ic);
+  ic.batch_size = batch_size;
+  ic.rollout_length = 1;
+  ic.num_actions = num_actions;
+  ic.dtype = dtype;
+  if (optim) {
+    ic.lr = optim->lr; ic.adam_beta1 = optim->adam_beta1; ic.adam_beta2 = optim->adam_beta2;
+    ic.adam_eps = optim->adam_eps;
+    ic.max_grad_norm = optim->max_grad_norm;
+  }
+  ic.entropy_coeff = 0.f;
+  ic.world_size = 1;
+  ic.algo = ALGO_DQN;
+  return impala_internal::create_learner(&ic, device, net::HID_DQN, out);
+}
+
+// destroys the core (null: nothing) and leaves its device current for the handle's own frees
+void destroy_q_core(impala_learner* core) {
+  if (!core) return;
+  const int device = core->device;
+  impala_destroy(core);  // (synchronises the device)
+  (void)hipSetDevice(device);
 }
 
 // forward, loss and backward of one batch: the pre-clip gradient in the bound grads, the
@@ -132,58 +169,41 @@ int dqn_create(const dqn_config* cfg, int device, dqn_learner** out) {
     return fail(IMPALA_E_UNSUPPORTED, "num_actions must be in [1, 15]");
   if (cfg->dtype != IMPALA_DTYPE_F32 && cfg->dtype != IMPALA_DTYPE_BF16)
     return fail(IMPALA_E_INVALID, "unknown dtype");
-  if (!(cfg->lr >= 0.f) || !(cfg->adam_eps > 0.f) || !(cfg->max_grad_norm > 0.f) ||
-      !(cfg->adam_beta1 >= 0.f && cfg->adam_beta1 < 1.f) ||
-      !(cfg->adam_beta2 >= 0.f && cfg->adam_beta2 < 1.f))
-    return fail(IMPALA_E_INVALID, "bad optimizer settings");
-  if (!(cfg->importance_sampling_exponent >= 0.f))
-    return fail(IMPALA_E_INVALID, "importance_sampling_exponent must be >= 0");
-  impala_config ic;
-  impala_config_default(&ic);
-  ic.batch_size = cfg->batch_size;
-  ic.rollout_length = 1;
-  ic.num_actions = cfg->num_actions;
-  ic.dtype = cfg->dtype;
-  ic.lr = cfg->lr; ic.adam_beta1 = cfg->adam_beta1; ic.adam_beta2 = cfg->adam_beta2;
-  ic.adam_eps = cfg->adam_eps;
-  ic.max_grad_norm = cfg->max_grad_norm;
-  ic.entropy_coeff = 0.f;
-  ic.world_size = 1;
-  ic.algo = ALGO_DQN;
+  if (int r = check_optim(cfg->lr, cfg->adam_beta1, cfg->adam_beta2, cfg->adam_eps, cfg->max_grad_norm,
+                          cfg->importance_sampling_exponent))
+    return r;
   dqn_learner* h = new (std::nothrow) dqn_learner();
   if (!h) return fail(IMPALA_E_INVALID, "out of host memory");
   h->cfg = *cfg;
-  if (int r = impala_internal::create_learner(&ic, device, HID_DQN, &h->core)) {
+  if (int r = create_q_core(cfg->batch_size, cfg->num_actions, cfg->dtype, cfg, device, &h->core)) {
     delete h;
     return r;
   }
   h->core->dqn_beta = cfg->importance_sampling_exponent;
   const size_t es = h->core->bf16 ? 2 : 4;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   h->shadow_bytes = h->core->sh.total * es;
   h->vecs_bytes = VecsDqn::total * 4;
-  const size_t o_v = al(h->shadow_bytes), o_h = o_v + al(h->vecs_bytes);
-  const size_t total = o_h + al((size_t)h->core->N * HEADS * 4);
+  auto carve = [&](Arena a) {
+    h->t_shadow = a.take(h->shadow_bytes);
+    h->t_vecs = (float*)a.take(h->vecs_bytes);
+    h->t_heads = (float*)a.take((size_t)h->core->N * HEADS * 4);
+    return Arena::align(a.used);
+  };
+  const size_t total = carve(Arena{});
   hipError_t e = hipMalloc(&h->tws, total);
   if (e == hipSuccess) e = hipMemset(h->tws, 0, total);
   if (e != hipSuccess) {
     dqn_destroy(h);
     return fail((int)e, std::string("dqn_create (target net workspace): ") + hipGetErrorString(e));
   }
-  h->t_shadow = h->tws;
-  h->t_vecs = (float*)(h->tws + o_v);
-  h->t_heads = (float*)(h->tws + o_h);
+  carve(Arena{h->tws});
   *out = h;
   return 0;
 }
 
 int dqn_destroy(dqn_learner* h) {
   if (!h) return 0;
-  if (h->core) {
-    const int device = h->core->device;
-    impala_destroy(h->core);  // (synchronises the device)
-    (void)hipSetDevice(device);
-  }
+  destroy_q_core(h->core);
   if (h->tws) (void)hipFree(h->tws);
   delete h;
   return 0;
@@ -240,7 +260,7 @@ int dqn_forward(dqn_learner* h, const uint8_t* obs, int n, int which, float* q, 
   if (which != 0 && which != 1) return fail(IMPALA_E_INVALID, "which must be 0 (online) or 1 (target)");
   if (int r = dqn_check(h, false, which == 1)) return r;
   if (!q) return fail(IMPALA_E_INVALID, "null pointer");
-  if (int r = dqn_check_frames(h, obs, n)) return r;
+  if (int r = check_frames(h->core->N, obs, n)) return r;
   impala_learner* c = h->core;
   CK(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
@@ -259,7 +279,7 @@ int dqn_act(dqn_learner* h, const uint8_t* obs, int n, const float* eps, float e
             int64_t* greedy, void* stream) {
   if (int r = dqn_check(h, false, true)) return r;
   if (!actions || !q_pi || !q_star) return fail(IMPALA_E_INVALID, "null pointer");
-  if (int r = dqn_check_frames(h, obs, n)) return r;
+  if (int r = check_frames(h->core->N, obs, n)) return r;
   impala_learner* c = h->core;
   if (c->A < 2) return fail(IMPALA_E_UNSUPPORTED, "dqn_act needs num_actions >= 2 (eps / (A - 1))");
   if (!eps && !(eps_all >= 0.f && eps_all <= 1.f)) return fail(IMPALA_E_INVALID, "eps must be in [0, 1]");

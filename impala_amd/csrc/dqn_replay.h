@@ -43,13 +43,6 @@ namespace {
 
 constexpr size_t kObsRowBytes = 3 * 64 * 64;
 
-#define CK_KERNEL(name, call)                                                          \
-  do {                                                                                 \
-    hipError_t e_ = (call);                                                            \
-    if (e_ != hipSuccess)                                                              \
-      return fail((int)e_, std::string("launch ") + name + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 // the first null pointer's argument name, or nullptr
 struct NamedPtr {
   const char* name;
@@ -111,17 +104,18 @@ int replay_ensure_gather(dqn_replay* r, int n) {
   if (r->gbuf) CK(hipFree(r->gbuf));  // (synchronises: no launch still reads it)
   r->gbuf = nullptr;
   r->g_rows = 0;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_act = al((size_t)n * kObsRowBytes), o_keys = o_act + al((size_t)n * 8);
-  const size_t o_tgt = o_keys + al((size_t)n * 8), o_prob = o_tgt + al((size_t)n * 4);
-  const size_t o_prio = o_prob + al((size_t)n * 4), total = o_prio + al((size_t)n * 4);
+  auto carve = [&](Arena a) {
+    r->g_obs = (uint8_t*)a.take((size_t)n * kObsRowBytes);
+    r->g_act = (int64_t*)a.take((size_t)n * 8);
+    r->g_keys = (int64_t*)a.take((size_t)n * 8);
+    r->g_tgt = (float*)a.take((size_t)n * 4);
+    r->g_prob = (float*)a.take((size_t)n * 4);
+    r->g_prio = (float*)a.take((size_t)n * 4);
+    return Arena::align(a.used);
+  };
+  const size_t total = carve(Arena{});
   CK(hipMalloc((void**)&r->gbuf, total));
-  r->g_obs = (uint8_t*)r->gbuf;
-  r->g_act = (int64_t*)(r->gbuf + o_act);
-  r->g_keys = (int64_t*)(r->gbuf + o_keys);
-  r->g_tgt = (float*)(r->gbuf + o_tgt);
-  r->g_prob = (float*)(r->gbuf + o_prob);
-  r->g_prio = (float*)(r->gbuf + o_prio);
+  carve(Arena{r->gbuf});
   r->g_rows = n;
   return 0;
 }
@@ -131,12 +125,15 @@ int replay_ensure_scratch(dqn_replay* r, int n) {
   if (r->sbuf) CK(hipFree(r->sbuf));  // (synchronises: no launch still reads it)
   r->sbuf = nullptr;
   r->s_rows = 0;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_prob = al((size_t)n * 8), o_prio = o_prob + al((size_t)n * 4);
-  CK(hipMalloc((void**)&r->sbuf, o_prio + al((size_t)n * 4)));
-  r->s_keys = (int64_t*)r->sbuf;
-  r->s_prob = (float*)(r->sbuf + o_prob);
-  r->s_prio = (float*)(r->sbuf + o_prio);
+  auto carve = [&](Arena a) {
+    r->s_keys = (int64_t*)a.take((size_t)n * 8);
+    r->s_prob = (float*)a.take((size_t)n * 4);
+    r->s_prio = (float*)a.take((size_t)n * 4);
+    return Arena::align(a.used);
+  };
+  const size_t total = carve(Arena{});
+  CK(hipMalloc((void**)&r->sbuf, total));
+  carve(Arena{r->sbuf});
   r->s_rows = n;
   return 0;
 }
@@ -158,23 +155,24 @@ int dqn_replay_create(int64_t capacity, double priority_exponent, int device, dq
   r->ring.cap = capacity;
   r->alpha = priority_exponent;
   r->device = device;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_bsum = al((size_t)capacity * 8);
-  const size_t o_max = o_bsum + al((size_t)dqn_replay_host::blocks(capacity) * 8);
-  const size_t total = o_max + 256;
+  auto carve = [&](Arena a) {
+    r->weights = (double*)a.take((size_t)capacity * 8);
+    r->bsum = (double*)a.take((size_t)dqn_replay_host::blocks(capacity) * 8);
+    r->maxp = (float*)a.take(4);
+    return Arena::align(a.used);
+  };
+  const size_t total = carve(Arena{});
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipMalloc((void**)&r->state, total);
   if (e == hipSuccess) e = hipMemset(r->state, 0, total);
+  carve(Arena{r->state});
   const float one = 1.f;
-  if (e == hipSuccess) e = hipMemcpy(r->state + o_max, &one, 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(r->maxp, &one, 4, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     if (r->state) (void)hipFree(r->state);
     delete r;
     return fail((int)e, std::string("dqn_replay_create: ") + hipGetErrorString(e));
   }
-  r->weights = (double*)r->state;
-  r->bsum = (double*)(r->state + o_bsum);
-  r->maxp = (float*)(r->state + o_max);
   *out = r;
   return 0;
 }

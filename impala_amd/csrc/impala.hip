@@ -27,6 +27,7 @@
 #include "dqn_head.h"
 #include "dqn_inplace_launch.h"
 #include "head.h"
+#include "host.h"
 #include "hostpool.h"
 #include "kernels.h"
 #include "lnc3.h"
@@ -34,19 +35,16 @@
 #include "ppo_replay_launch.h"
 
 namespace {
-
 thread_local std::string g_err;
+}  // namespace
 
-int fail(int code, const std::string& msg) {
+// shared with the SAC translation unit (sac.hip) through csrc/host.h's fail: one last-error slot
+// per thread for the library
+namespace impala_internal {
+int set_error(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-
-}  // namespace
-
-// shared with the SAC translation unit (sac.hip): one last-error slot per thread for the library
-namespace impala_internal {
-int set_error(int code, const std::string& msg) { return fail(code, msg); }
 // cfg->algo of the handle behind a dqn_learner (never accepted by impala_create)
 constexpr int ALGO_DQN = 2;
 int create_learner(const impala_config* cfg, int device, int hid, impala_learner** out);
@@ -55,21 +53,6 @@ using impala_internal::ALGO_DQN;
 
 namespace {
 
-#define CK(x)                                                                          \
-  do {                                                                                 \
-    hipError_t e_ = (x);                                                               \
-    if (e_ != hipSuccess)                                                              \
-      return fail((int)e_, std::string(#x) + ": " + hipGetErrorString(e_));           \
-  } while (0)
-
-#define CK_LAUNCH(name)                                                                \
-  do {                                                                                 \
-    hipError_t e_ = hipGetLastError();                                                 \
-    if (e_ != hipSuccess)                                                              \
-      return fail((int)e_, std::string("launch ") + name + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 inline int next_pow2(int x) {
   int p = 1;
   while (p < x) p <<= 1;
@@ -114,6 +97,12 @@ const char* const kKernelNames[K_COUNT] = {
     "conv3_wgrad", "conv2_wgrad", "conv2_dgrad_conv1_wgrad", "reduce_grads", "sumsq", "adam",
     "fc_wgrad_fc_dgrad", "conv3_wgrad_conv2_wgrad", "conv1_conv2_conv3_fwd",
     "ln_conv3_conv2_dgrad_conv1_wgrad"};
+
+// the graph cache's key equality (GraphCache, host.h): a batch is its five addresses
+static bool same_key(const impala_batch& a, const impala_batch& b) {
+  return a.obs == b.obs && a.actions == b.actions && a.rewards == b.rewards &&
+         a.discounts == b.discounts && a.behaviour_logits == b.behaviour_logits;
+}
 
 struct impala_learner {
   impala_config cfg;
@@ -177,18 +166,10 @@ struct impala_learner {
   unsigned long long* clock_buf = nullptr;
   int clock_n = 0, clock_i = 0;
   // hipGraph replay of whole steps: the launch sequence of a step is captured once per batch
-  // address set (on a private capture stream) and replayed with one hipGraphLaunch
-  struct GraphSlot {
-    hipGraphExec_t exec = nullptr;
-    int kind = -1;  // G_GRADS, G_UPDATE, G_STEP
-    impala_batch key{};
-    uint64_t used = 0;
-  };
-  static constexpr int kGraphSlots = 8;
-  GraphSlot graphs[kGraphSlots];
-  hipStream_t cap = nullptr;
+  // address set (on a private capture stream) and replayed with one hipGraphLaunch; the kinds
+  // are G_GRADS, G_UPDATE, G_STEP, G_GRADS0 + part
+  GraphCache<impala_batch, 8> graphs;
   bool use_graph = false;
-  uint64_t graph_tick = 0;
   StageRing stage;  // host staging ring (impala_stage*, impala_slot_*): csrc/stage.h
   // native data-parallel step (impala_dp_*): the library's own RCCL communicator, so the
   // gradient all-reduces are enqueued with no host round trip and no c10d bookkeeping; the FC +
@@ -521,13 +502,6 @@ int launch_pack(impala_learner* h, hipStream_t st) {
   return 0;
 }
 
-void drop_graphs(impala_learner* h) {
-  for (auto& g : h->graphs) {
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    g = impala_learner::GraphSlot{};
-  }
-}
-
 int check_bound(impala_learner* h, bool train = true) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
   if (!h->params) return fail(IMPALA_E_STATE, "impala_bind_state() not called");
@@ -673,74 +647,57 @@ int impala_internal::create_learner(const impala_config* cfg, int device, int hi
   h->c1_wg = cdiv(N, h->c1_fpw);
   h->sp1.S = h->c1_wg;  // slab splits of conv1 (one per workgroup)
 
-  // ---- one workspace allocation, 256-byte aligned carve ----
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
+  // ---- one workspace allocation, 256-byte aligned carve (arena.h: sized on a null base) ----
+  auto carve = [&](Arena a) {
+    auto F = [&](size_t bytes) { return (float*)a.take(bytes); };
+    h->shadow = a.take(h->sh.total * es);
+    h->vecs = F((hid == HID_DQN ? VecsDqn::total : Vecs::total) * 4);
+    h->act1 = a.take((size_t)N * P1 * OC1 * es);
+    h->act2 = a.take((size_t)N * P2 * OC2 * es);
+    h->act3 = a.take((size_t)N * FLAT * es);
+    h->y = a.take((size_t)N * YLD * es);
+    h->h = a.take((size_t)N * HID * es);
+    h->dz = a.take((size_t)N * HID * es);
+    h->dact3 = a.take((size_t)N * FLAT * es);
+    h->dact2 = a.take((size_t)N * P2 * OC2 * es);
+    h->mask1 = (uint32_t*)a.take((size_t)N * P1 * 4);
+    h->lnstat = F((size_t)N * 2 * 4);
+    h->zg = F((size_t)N * HID * 4);
+    h->heads = F((size_t)N * HEADS * 4);
+    h->dy = F((size_t)N * FLAT * 4);
+    h->s_w1 = F((size_t)h->sp1.S * OC1 * K1 * 4);
+    h->s_b1 = F((size_t)h->sp1.S * OC1 * 4);
+    h->s_w2 = F((size_t)h->sp2.S * OC2 * K2 * 4);
+    h->s_b2 = F((size_t)h->sp2.S * OC2 * 4);
+    h->s_w3 = F((size_t)h->sp3.S * OC3 * K3 * 4);
+    h->s_b3 = F((size_t)h->sp3.S * OC3 * 4);
+    h->s_ln = F((size_t)h->n_ln_wg * 2 * FLAT * 4);
+    h->s_fc = F((size_t)h->spfc.S * HID * FLAT * 4);
+    h->s_bfc = F((size_t)h->spfc.S * HID * 4);
+    h->s_h = F((size_t)h->sph.S * HEADS * HID * 4);
+    h->s_bh = F((size_t)h->sph.S * HEADS * 4);
+    h->loss_part = F((size_t)h->n_loss_wg * 8 * 4);
+    h->sumsq_part = F((size_t)(h->n_red_wg + 3) / 4 * 16);  // zero tail: float4 reads
+    h->adam_sc = F(2 * 4);
+    h->step = (int64_t*)a.take(8);
+    return Arena::align(a.used);
   };
-  const size_t o_shadow = take(h->sh.total * es);
-  const size_t o_vecs = take((hid == HID_DQN ? VecsDqn::total : Vecs::total) * 4);
-  const size_t o_act1 = take((size_t)N * P1 * OC1 * es);
-  const size_t o_act2 = take((size_t)N * P2 * OC2 * es);
-  const size_t o_act3 = take((size_t)N * FLAT * es);
-  const size_t o_y = take((size_t)N * YLD * es);
-  const size_t o_h = take((size_t)N * HID * es);
-  const size_t o_dz = take((size_t)N * HID * es);
-  const size_t o_dact3 = take((size_t)N * FLAT * es);
-  const size_t o_dact2 = take((size_t)N * P2 * OC2 * es);
-  const size_t o_mask1 = take((size_t)N * P1 * 4);
-  const size_t o_lnstat = take((size_t)N * 2 * 4);
-  const size_t o_z = take((size_t)N * HID * 4);
-  const size_t o_heads = take((size_t)N * HEADS * 4);
-  const size_t o_dy = take((size_t)N * FLAT * 4);
-  const size_t o_sw1 = take((size_t)h->sp1.S * OC1 * K1 * 4);
-  const size_t o_sb1 = take((size_t)h->sp1.S * OC1 * 4);
-  const size_t o_sw2 = take((size_t)h->sp2.S * OC2 * K2 * 4);
-  const size_t o_sb2 = take((size_t)h->sp2.S * OC2 * 4);
-  const size_t o_sw3 = take((size_t)h->sp3.S * OC3 * K3 * 4);
-  const size_t o_sb3 = take((size_t)h->sp3.S * OC3 * 4);
-  const size_t o_sln = take((size_t)h->n_ln_wg * 2 * FLAT * 4);
-  const size_t o_sfc = take((size_t)h->spfc.S * HID * FLAT * 4);
-  const size_t o_sbfc = take((size_t)h->spfc.S * HID * 4);
-  const size_t o_sh = take((size_t)h->sph.S * HEADS * HID * 4);
-  const size_t o_sbh = take((size_t)h->sph.S * HEADS * 4);
-  const size_t o_lpart = take((size_t)h->n_loss_wg * 8 * 4);
-  const size_t o_spart = take((size_t)(h->n_red_wg + 3) / 4 * 16);  // zero tail: float4 reads
-  const size_t o_adsc = take(2 * 4);
-  const size_t o_step = take(8);
-  h->ws_bytes = off;
-  hipError_t e = hipMalloc(&h->ws, off);
+  h->ws_bytes = carve(Arena{});
+  hipError_t e = hipMalloc(&h->ws, h->ws_bytes);
   if (e != hipSuccess) {
     delete h;
     return fail((int)e, std::string("hipMalloc workspace: ") + hipGetErrorString(e));
   }
-  e = hipMemset(h->ws, 0, off);
+  e = hipMemset(h->ws, 0, h->ws_bytes);
   if (e != hipSuccess) {
     (void)hipFree(h->ws);
     delete h;
     return fail((int)e, std::string("hipMemset workspace: ") + hipGetErrorString(e));
   }
-  char* w = h->ws;
-  h->shadow = w + o_shadow;
-  h->vecs = (float*)(w + o_vecs);
-  h->act1 = w + o_act1; h->act2 = w + o_act2; h->act3 = w + o_act3; h->y = w + o_y;
-  h->h = w + o_h; h->dz = w + o_dz; h->dact3 = w + o_dact3;
-  h->dact2 = w + o_dact2; h->mask1 = (uint32_t*)(w + o_mask1);
-  h->lnstat = (float*)(w + o_lnstat); h->zg = (float*)(w + o_z); h->heads = (float*)(w + o_heads);
-  h->dy = (float*)(w + o_dy);
-  h->s_w1 = (float*)(w + o_sw1); h->s_b1 = (float*)(w + o_sb1);
-  h->s_w2 = (float*)(w + o_sw2); h->s_b2 = (float*)(w + o_sb2);
-  h->s_w3 = (float*)(w + o_sw3); h->s_b3 = (float*)(w + o_sb3);
-  h->s_ln = (float*)(w + o_sln); h->s_fc = (float*)(w + o_sfc); h->s_bfc = (float*)(w + o_sbfc);
-  h->s_h = (float*)(w + o_sh); h->s_bh = (float*)(w + o_sbh);
-  h->loss_part = (float*)(w + o_lpart); h->sumsq_part = (float*)(w + o_spart);
-  h->adam_sc = (float*)(w + o_adsc);
-  h->step = (int64_t*)(w + o_step);
+  carve(Arena{h->ws});
   // the capture stream exists only for graph replay: every stream a process creates takes a
   // share of its GPU_MAX_HW_QUEUES hardware queues (profiles/r06w)
-  if (h->use_graph && hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking) != hipSuccess) {
+  if (h->use_graph && hipStreamCreateWithFlags(&h->graphs.cap, hipStreamNonBlocking) != hipSuccess) {
     impala_destroy(h);
     return fail(IMPALA_E_STATE, "hipStreamCreate (capture stream) failed");
   }
@@ -849,13 +806,13 @@ int impala_destroy(impala_learner* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();  // replays may still be in flight on the caller's streams
-  drop_graphs(h);
+  h->graphs.drop();
   stage_destroy(h->stage);
   for (auto& t : h->timers) {
     for (int i = 0; i < 2 * t.cap; ++i) (void)hipEventDestroy(t.ev[i]);
     delete[] t.ev;
   }
-  if (h->cap) (void)hipStreamDestroy(h->cap);
+  if (h->graphs.cap) (void)hipStreamDestroy(h->graphs.cap);
   dp_release(h);
   if (h->ws) (void)hipFree(h->ws);
   delete h;
@@ -868,7 +825,7 @@ int impala_bind_state(impala_learner* h, float* params, float* grads, float* exp
   if (!params) return fail(IMPALA_E_INVALID, "null params pointer");
   h->params = params; h->grads = grads; h->exp_avg = exp_avg; h->exp_avg_sq = exp_avg_sq;
   h->metrics = metrics;
-  drop_graphs(h);  // captured launches hold the previous state pointers
+  h->graphs.drop();  // captured launches hold the previous state pointers
   h->red.grads = grads;
   h->red.metrics = metrics;
   return impala_refresh_weights(h, stream);
@@ -880,7 +837,7 @@ int impala_set_metrics(impala_learner* h, float* metrics) {
   if (h->metrics != metrics) {
     h->metrics = metrics;
     h->red.metrics = metrics;
-    if (h->use_graph) drop_graphs(h);  // captured launches hold the previous pointer
+    if (h->use_graph) h->graphs.drop();  // captured launches hold the previous pointer
   }
   return 0;
 }
@@ -897,14 +854,14 @@ int impala_set_metrics_host(impala_learner* h, float* host) {
   }
   if (h->metrics_host != host) {
     h->metrics_host = host;
-    if (h->use_graph) drop_graphs(h);  // captured launches hold the previous pointer
+    if (h->use_graph) h->graphs.drop();  // captured launches hold the previous pointer
   }
   return 0;
 }
 
 int impala_set_debug_vtrace(impala_learner* h, float* out) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
-  if (h->vt_dbg != out) drop_graphs(h);  // captured launches hold the previous pointer
+  if (h->vt_dbg != out) h->graphs.drop();  // captured launches hold the previous pointer
   h->vt_dbg = out;
   return 0;
 }
@@ -1017,46 +974,13 @@ int enqueue_update(impala_learner* h, hipStream_t st) {
   return BY_NET(h, launch_adam, h, st);
 }
 
-bool same_batch(const impala_batch& a, const impala_batch& b) {
-  return a.obs == b.obs && a.actions == b.actions && a.rewards == b.rewards &&
-         a.discounts == b.discounts && a.behaviour_logits == b.behaviour_logits;
-}
-
-// Run `body` (which enqueues a step's launches on the stream it is given) through the graph
-// cache: replay a graph captured for the same kind and batch addresses, or capture one on the
-// private capture stream, instantiate it and launch it on `st`.  With the live timer armed
-// (its events must be recorded per launch) or IMPALA_GRAPH=0 the launches go straight to `st`.
+// A step's launches through the handle's graph cache (GraphCache::run, host.h).  With the live
+// timer armed (its events must be recorded per launch), the step clock armed or IMPALA_GRAPH=0 the
+// launches go straight to `st`.
 template <class Body>
 int run_graphed(impala_learner* h, int kind, const impala_batch* b, hipStream_t st, Body&& body) {
-  if (!h->use_graph || h->timers_armed > 0 || h->clock_buf) return body(st);
-  const impala_batch key = b ? *b : impala_batch{};
-  for (auto& g : h->graphs)
-    if (g.exec && g.kind == kind && same_batch(g.key, key)) {
-      g.used = ++h->graph_tick;
-      CK(hipGraphLaunch(g.exec, st));
-      return 0;
-    }
-  CK(hipStreamBeginCapture(h->cap, hipStreamCaptureModeThreadLocal));
-  const int r = body(h->cap);
-  hipGraph_t graph = nullptr;
-  const hipError_t ee = hipStreamEndCapture(h->cap, &graph);
-  if (r || ee != hipSuccess) {
-    if (graph) (void)hipGraphDestroy(graph);
-    return r ? r : fail((int)ee, std::string("hipStreamEndCapture: ") + hipGetErrorString(ee));
-  }
-  hipGraphExec_t exec = nullptr;
-  const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  if (ei != hipSuccess) return fail((int)ei, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei));
-  auto* slot = &h->graphs[0];
-  for (auto& g : h->graphs) {
-    if (!g.exec) { slot = &g; break; }
-    if (g.used < slot->used) slot = &g;
-  }
-  if (slot->exec) (void)hipGraphExecDestroy(slot->exec);
-  *slot = impala_learner::GraphSlot{exec, kind, key, ++h->graph_tick};
-  CK(hipGraphLaunch(exec, st));
-  return 0;
+  const bool bypass = !h->use_graph || h->timers_armed > 0 || h->clock_buf;
+  return h->graphs.run(!bypass, kind, b ? *b : impala_batch{}, st, body);
 }
 enum { G_GRADS = 0, G_UPDATE = 1, G_STEP = 2, G_GRADS0 = 3 };  // G_GRADS0 + part (0..4, 6)
 }  // namespace

@@ -142,35 +142,35 @@ int iqn_alloc_step(iqn_learner* h) {
     ra.wg_start[i + 1] = ra.wg_start[i] + cdiv(ra.seg[i].count / 4, 256 / sg);
   }
   const int n_red_wg = ra.wg_start[RS_END], n_part = n_red_wg + iqn_dev::ins_wgs();
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
   const size_t Rz = (size_t)R, nh = (size_t)h->n_head_wg;
-  const size_t o_st = take(Rz * 2 * 4), o_e = take(Rz * IQN_COS * es), o_dz = take(Rz * HID_DQN * es);
-  const size_t o_dy = take(Rz * FLAT * 4), o_dpre = take(Rz * FLAT * es), o_dx = take((size_t)N * FLAT * 4);
-  const size_t o_sln = take((size_t)s.ln_wgs * 2 * FLAT * 4);
-  const size_t o_sfc = take((size_t)s.fc_S * HID_DQN * FLAT * 4), o_sbfc = take((size_t)s.fc_S * HID_DQN * 4);
-  const size_t o_sh = take(nh * HEADS * HID_DQN * 4), o_sbh = take(nh * HEADS * 4);
-  const size_t o_swq = take((size_t)s.wq_S * FLAT * IQN_COS * 4), o_sbq = take((size_t)s.wq_S * FLAT * 4);
-  const size_t o_lp = take(nh * 8 * 4), o_sq = take((size_t)(n_part + 3) / 4 * 16);  // zero tail: float4 reads
-  hipError_t e = hipMalloc(&h->tws, off);
-  if (e == hipSuccess) e = hipMemset(h->tws, 0, off);
+  auto carve = [&](Arena a) {  // (every size is of the plan above, none of a pointer set here)
+    auto F = [&](size_t bytes) { return (float*)a.take(bytes); };
+    s.stats = F(Rz * 2 * 4);
+    s.e = a.take(Rz * IQN_COS * es);
+    s.dz = a.take(Rz * HID_DQN * es);
+    s.dy = F(Rz * FLAT * 4);
+    s.dpre = a.take(Rz * FLAT * es);
+    s.dx = F((size_t)N * FLAT * 4);
+    s.s_ln = F((size_t)s.ln_wgs * 2 * FLAT * 4);
+    s.s_fc = F((size_t)s.fc_S * HID_DQN * FLAT * 4);
+    s.s_bfc = F((size_t)s.fc_S * HID_DQN * 4);
+    s.s_h = F(nh * HEADS * HID_DQN * 4);
+    s.s_bh = F(nh * HEADS * 4);
+    s.s_wq = F((size_t)s.wq_S * FLAT * IQN_COS * 4);
+    s.s_bq = F((size_t)s.wq_S * FLAT * 4);
+    s.loss_part = F(nh * 8 * 4);
+    h->sumsq = F((size_t)(n_part + 3) / 4 * 16);  // zero tail: float4 reads
+    return Arena::align(a.used);
+  };
+  const size_t total = carve(Arena{});
+  hipError_t e = hipMalloc(&h->tws, total);
+  if (e == hipSuccess) e = hipMemset(h->tws, 0, total);
   if (e != hipSuccess) {
     if (h->tws) (void)hipFree(h->tws);
     h->tws = nullptr;
     return fail((int)e, std::string("iqn_bind_state (workspace): ") + hipGetErrorString(e));
   }
-  char* w = h->tws;
-  s.stats = (float*)(w + o_st); s.e = w + o_e; s.dz = w + o_dz; s.dy = (float*)(w + o_dy);
-  s.dpre = w + o_dpre; s.dx = (float*)(w + o_dx);
-  s.s_ln = (float*)(w + o_sln); s.s_fc = (float*)(w + o_sfc); s.s_bfc = (float*)(w + o_sbfc);
-  s.s_h = (float*)(w + o_sh); s.s_bh = (float*)(w + o_sbh);
-  s.s_wq = (float*)(w + o_swq); s.s_bq = (float*)(w + o_sbq);
-  s.loss_part = (float*)(w + o_lp);
-  h->sumsq = (float*)(w + o_sq);
+  carve(Arena{h->tws});
   s.fw = h->work;
   ra.seg[RS_LN].slab = s.s_ln;
   ra.seg[RS_FC].slab = s.s_fc;
@@ -267,13 +267,6 @@ int iqn_enqueue_update(iqn_learner* h, hipStream_t st) {
   return 0;
 }
 
-int iqn_check_frames(iqn_learner* h, const uint8_t* obs, int n) {
-  if (!obs) return fail(IMPALA_E_INVALID, "null pointer");
-  if (n < 1 || n > h->cfg.batch_size) return fail(IMPALA_E_INVALID, "n must be in [1, batch_size]");
-  if (((uintptr_t)obs & 15) != 0) return fail(IMPALA_E_INVALID, "obs must be 16-byte aligned");
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -305,19 +298,10 @@ int iqn_create(const iqn_config* cfg, int device, iqn_learner** out) {
     return fail(IMPALA_E_INVALID, "batch_size must be >= 1 and batch_size * n_tau <= 16384");
   if (cfg->dtype != IMPALA_DTYPE_F32 && cfg->dtype != IMPALA_DTYPE_BF16)
     return fail(IMPALA_E_INVALID, "unknown dtype");
-  impala_config ic;
-  impala_config_default(&ic);
-  ic.batch_size = cfg->batch_size;
-  ic.rollout_length = 1;
-  ic.num_actions = cfg->num_actions;
-  ic.dtype = cfg->dtype;
-  ic.entropy_coeff = 0.f;
-  ic.world_size = 1;
-  ic.algo = ALGO_DQN;
   iqn_learner* h = new (std::nothrow) iqn_learner();
   if (!h) return fail(IMPALA_E_INVALID, "out of host memory");
   h->cfg = *cfg;
-  if (int r = impala_internal::create_learner(&ic, device, HID_DQN, &h->core)) {
+  if (int r = create_q_core(cfg->batch_size, cfg->num_actions, cfg->dtype, nullptr, device, &h->core)) {
     delete h;
     return r;
   }
@@ -331,35 +315,34 @@ int iqn_create(const iqn_config* cfg, int device, iqn_learner** out) {
   h->shadow_bytes = c->sh.total * es;
   h->vecs_bytes = VecsDqn::total * 4;
   h->wq_bytes = (size_t)FLAT * IQN_COS * es;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
+  auto carve = [&](Arena a) {
+    auto F = [&](size_t bytes) { return (float*)a.take(bytes); };
+    h->stage = h->target_params = F(c->cn.total * 4);
+    h->t_shadow = a.take(h->shadow_bytes);
+    h->t_vecs = F(h->vecs_bytes);
+    h->wq[0] = a.take(h->wq_bytes);
+    h->wq[1] = a.take(h->wq_bytes);
+    h->bq[0] = F(FLAT * 4);
+    h->bq[1] = F(FLAT * 4);
+    h->work.y = a.take(R * YLD * es);
+    h->work.zg = F(R * HID_DQN * 4);
+    h->work.h = a.take(R * HID_DQN * es);
+    h->work.heads = F(R * HEADS * 4);
+    h->taus[0] = F(R * 4);
+    h->taus[1] = F(R * 4);
+    h->q[0] = F(R * A * 4);
+    h->q[1] = F(R * A * 4);
+    return Arena::align(a.used);
   };
-  const size_t o_stage = take(c->cn.total * 4), o_tsh = take(h->shadow_bytes), o_tv = take(h->vecs_bytes);
-  const size_t o_wq0 = take(h->wq_bytes), o_wq1 = take(h->wq_bytes);
-  const size_t o_bq0 = take(FLAT * 4), o_bq1 = take(FLAT * 4);
-  const size_t o_y = take(R * YLD * es), o_zg = take(R * HID_DQN * 4), o_h = take(R * HID_DQN * es);
-  const size_t o_heads = take(R * HEADS * 4);
-  const size_t o_t0 = take(R * 4), o_t1 = take(R * 4), o_q0 = take(R * A * 4), o_q1 = take(R * A * 4);
-  hipError_t e = hipMalloc(&h->ws, off);
-  if (e == hipSuccess) e = hipMemset(h->ws, 0, off);
+  const size_t total = carve(Arena{});
+  hipError_t e = hipMalloc(&h->ws, total);
+  if (e == hipSuccess) e = hipMemset(h->ws, 0, total);
   if (e != hipSuccess) {
     iqn_destroy(h);
     return fail((int)e, std::string("iqn_create (workspace): ") + hipGetErrorString(e));
   }
-  char* w = h->ws;
-  h->stage = h->target_params = (float*)(w + o_stage);
-  h->t_shadow = w + o_tsh;
-  h->t_vecs = (float*)(w + o_tv);
+  carve(Arena{h->ws});
   h->t_heads = c->heads;
-  h->wq[0] = w + o_wq0; h->wq[1] = w + o_wq1;
-  h->bq[0] = (float*)(w + o_bq0); h->bq[1] = (float*)(w + o_bq1);
-  h->work.y = w + o_y; h->work.zg = (float*)(w + o_zg); h->work.h = w + o_h;
-  h->work.heads = (float*)(w + o_heads);
-  h->taus[0] = (float*)(w + o_t0); h->taus[1] = (float*)(w + o_t1);
-  h->q[0] = (float*)(w + o_q0); h->q[1] = (float*)(w + o_q1);
   c->params = h->stage;  // what the core packs from (iqn_pack_net)
   *out = h;
   return 0;
@@ -367,11 +350,7 @@ int iqn_create(const iqn_config* cfg, int device, iqn_learner** out) {
 
 int iqn_destroy(iqn_learner* h) {
   if (!h) return 0;
-  if (h->core) {
-    const int device = h->core->device;
-    impala_destroy(h->core);  // (synchronises the device)
-    (void)hipSetDevice(device);
-  }
+  destroy_q_core(h->core);
   if (h->ws) (void)hipFree(h->ws);
   if (h->tws) (void)hipFree(h->tws);
   delete h;
@@ -411,7 +390,7 @@ int iqn_forward(iqn_learner* h, const uint8_t* obs, int n, int which, const floa
   if (which != 0 && which != 1) return fail(IMPALA_E_INVALID, "which must be 0 (online) or 1 (target)");
   if (int r = iqn_check(h)) return r;
   if (!q) return fail(IMPALA_E_INVALID, "null pointer");
-  if (int r = iqn_check_frames(h, obs, n)) return r;
+  if (int r = check_frames(h->core->N, obs, n)) return r;
   CK(hipSetDevice(h->core->device));
   return iqn_run_net(h, obs, n, which, taus, seed, counter, q, taus_out, (hipStream_t)stream);
 }
@@ -421,7 +400,7 @@ int iqn_act(iqn_learner* h, const uint8_t* obs, int n, const float* eps, float e
             float* q_pi, float* q_star, int64_t* greedy, void* stream) {
   if (int r = iqn_check(h)) return r;
   if (!actions || !q_pi || !q_star) return fail(IMPALA_E_INVALID, "null pointer");
-  if (int r = iqn_check_frames(h, obs, n)) return r;
+  if (int r = check_frames(h->core->N, obs, n)) return r;
   impala_learner* c = h->core;
   if (c->A < 2) return fail(IMPALA_E_UNSUPPORTED, "iqn_act needs num_actions >= 2 (eps / (A - 1))");
   if (!eps && !(eps_all >= 0.f && eps_all <= 1.f)) return fail(IMPALA_E_INVALID, "eps must be in [0, 1]");
@@ -458,11 +437,9 @@ int iqn_bind_state(iqn_learner* h, float* params, float* grads, float* exp_avg, 
   iqn_optim o;
   iqn_optim_default(&o);
   if (optim) o = *optim;
-  if (!(o.lr >= 0.f) || !(o.adam_eps > 0.f) || !(o.max_grad_norm > 0.f) ||
-      !(o.adam_beta1 >= 0.f && o.adam_beta1 < 1.f) || !(o.adam_beta2 >= 0.f && o.adam_beta2 < 1.f))
-    return fail(IMPALA_E_INVALID, "bad optimizer settings");
-  if (!(o.importance_sampling_exponent >= 0.f))
-    return fail(IMPALA_E_INVALID, "importance_sampling_exponent must be >= 0");
+  if (int r = check_optim(o.lr, o.adam_beta1, o.adam_beta2, o.adam_eps, o.max_grad_norm,
+                          o.importance_sampling_exponent))
+    return r;
   if (!(o.huber_param >= 0.f)) return fail(IMPALA_E_INVALID, "huber_param must be >= 0");
   impala_learner* c = h->core;
   CK(hipSetDevice(c->device));

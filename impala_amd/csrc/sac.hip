@@ -24,34 +24,13 @@
 #include <vector>
 
 #include "../../include/sac_hip.h"
+#include "host.h"
 #include "sac.h"
 #include "sac_fused.h"
-
-namespace impala_internal {
-int set_error(int code, const std::string& msg);
-}
 
 namespace {
 using namespace sac;
 
-int fail(int code, const std::string& msg) { return impala_internal::set_error(code, msg); }
-
-#define SCK(x)                                                                         \
-  do {                                                                                 \
-    hipError_t e_ = (x);                                                               \
-    if (e_ != hipSuccess)                                                              \
-      return fail((int)e_, std::string(#x) + ": " + hipGetErrorString(e_));           \
-  } while (0)
-
-#define SCK_LAUNCH(name)                                                               \
-  do {                                                                                 \
-    hipError_t e_ = hipGetLastError();                                                 \
-    if (e_ != hipSuccess)                                                              \
-      return fail((int)e_, std::string("launch ") + (name) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 // The decimal constant a float config value was written as: x rounded to 7 significant digits.
 // (An eighth digit is below a float's resolution: it turned 0.999f, 0.99900001287..., into
 // 0.99900001 and 0.9f into 0.89999998, so that Adam ran with 1 - beta2 = 0.00099999.)
@@ -113,6 +92,9 @@ __global__ void fill_row_kernel(T* p, int n, float v) {
 
 }  // namespace
 
+// the graph cache's key equality (GraphCache, host.h)
+static bool same_key(const sac_batch& a, const sac_batch& b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
+
 struct sac_learner {
   sac_config cfg{};
   int device = 0;
@@ -123,7 +105,7 @@ struct sac_learner {
   sac_state st{};
   bool bound = false;
   void* arena = nullptr;
-  size_t arena_used = 0, arena_size = 0;
+  size_t arena_size = 0;
   // operands (T)
   void *xs = nullptr, *xs1 = nullptr, *xc = nullptr, *xt = nullptr, *xp = nullptr, *xi = nullptr;
   void* xi2 = nullptr;  // [obs | act] rows of sac_q_forward
@@ -140,34 +122,22 @@ struct sac_learner {
   int64_t* steps = nullptr;  // critic, actor, alpha, learner
   MlpK ka{}, kta{}, kq[2]{}, ktq[2]{};
   bool fused = true;  // per-row-block chain kernels (SAC_FUSED=0: one launch per layer)
-  // graph cache
+  // graph cache (host.h; one kind)
   bool use_graph = true;
-  hipStream_t cap = nullptr;
-  struct GraphSlot {
-    hipGraphExec_t exec = nullptr;
-    sac_batch key{};
-    unsigned long long used = 0;
-  } graphs[4];
-  unsigned long long tick = 0;
+  GraphCache<sac_batch, 4> graphs;
   // live launch timer
   int timer_phase = -1, timer_max = 0, timer_n = 0;
   std::vector<hipEvent_t> ev;
-
-  void* take(size_t bytes) {
-    const size_t a = (arena_used + 255) & ~(size_t)255;
-    arena_used = a + bytes;
-    return arena ? (char*)arena + a : nullptr;
-  }
 };
 
 namespace {
 
-void carve(sac_learner* h) {
-  h->arena_used = 0;
+// the arena's pieces (arena.h: run on a null base to size it, then on the allocation); the bytes used
+size_t carve(sac_learner* h, Arena a) {
   const size_t E = h->esz;
   const int N = h->N, Np = h->Np;
-  auto T2 = [&](long long rows, long long cols) { return h->take((size_t)rows * cols * E); };
-  auto F = [&](long long n) { return (float*)h->take((size_t)n * 4); };
+  auto T2 = [&](long long rows, long long cols) { return a.take((size_t)rows * cols * E); };
+  auto F = [&](long long n) { return (float*)a.take((size_t)n * 4); };
   h->xs = T2(Np, h->Dp);
   h->xs1 = T2(Np, h->Dp);
   h->xi = T2(Np, h->Dp);
@@ -224,7 +194,7 @@ void carve(sac_learner* h) {
   h->nsq_a = t_w2 + 2 * t_head + t_w1a;
   h->sq_c = F(h->nsq_c);
   h->sq_a = F(h->nsq_a);
-  h->steps = (int64_t*)h->take(4 * sizeof(int64_t));
+  h->steps = (int64_t*)a.take(4 * sizeof(int64_t));
   auto mk = [&](int ld1, bool tr) {
     MlpK k;
     k.w1 = T2(H, ld1);
@@ -238,12 +208,13 @@ void carve(sac_learner* h) {
     h->kq[q] = mk(h->Cp, true);
     h->ktq[q] = mk(h->Cp, false);
   }
+  return a.used;
 }
 
 template <typename T>
 int fill_ones(sac_learner* h, void* base, int row, int ld) {
   fill_row_kernel<T><<<cdiv(h->N, 256), 256>>>((T*)base + (size_t)row * ld, h->N, 1.f);
-  SCK_LAUNCH("fill_ones");
+  CK_LAUNCH("fill_ones");
   return 0;
 }
 
@@ -296,7 +267,7 @@ int launch_gemm(sac_learner* h, int ph, std::initializer_list<GJob> jobs, hipStr
   timer_begin(h, ph, st);
   gemm_jobs<T><<<cdiv(t, 4), 256, 0, st>>>(g);
   timer_end(h, ph, st);
-  SCK_LAUNCH(pname(ph));
+  CK_LAUNCH(pname(ph));
   return 0;
 }
 
@@ -327,7 +298,7 @@ int launch_heads(sac_learner* h, int ph, std::initializer_list<HeadJob> jobs, in
   timer_begin(h, ph, st);
   heads_kernel<T><<<dim3(cdiv(n, 4), nj), 256, 0, st>>>(a);
   timer_end(h, ph, st);
-  SCK_LAUNCH(pname(ph));
+  CK_LAUNCH(pname(ph));
   return 0;
 }
 
@@ -377,7 +348,7 @@ int launch_adam(sac_learner* h, bool critic, int update, hipStream_t st) {
   timer_begin(h, ph, st);
   adam_net_kernel<T><<<cdiv(a.n, 256), 256, 0, st>>>(a);
   timer_end(h, ph, st);
-  SCK_LAUNCH(pname(ph));
+  CK_LAUNCH(pname(ph));
   return 0;
 }
 
@@ -404,7 +375,7 @@ int enqueue_step(sac_learner* h, const sac_batch* b, hipStream_t st) {
     timer_begin(h, P_PACK, st);
     pack_kernel<T><<<std::max(1, std::min(256, cdiv(std::max((long long)N * h->DK, 3 * NK), 256))), 256, 0, st>>>(p);
     timer_end(h, P_PACK, st);
-    SCK_LAUNCH("pack");
+    CK_LAUNCH("pack");
   }
   // ---------------- critic step (learning.py:195-211, critic_loss :233-248) ----------------
   if ((r = launch_gemm<T>(h, P_FWD1, {
@@ -455,7 +426,7 @@ int enqueue_step(sac_learner* h, const sac_batch* b, hipStream_t st) {
     timer_begin(h, P_CLOSS, st);
     critic_loss_kernel<T><<<cdiv(N, 4), 256, 0, st>>>(a);
     timer_end(h, P_CLOSS, st);
-    SCK_LAUNCH("critic_loss");
+    CK_LAUNCH("critic_loss");
   }
   float* cg = S.critic_grad;
   if ((r = launch_gemm<T>(h, P_CBWD2, {
@@ -499,7 +470,7 @@ int enqueue_step(sac_learner* h, const sac_batch* b, hipStream_t st) {
     timer_begin(h, P_ALOSS, st);
     actor_loss_kernel<T><<<cdiv(N, 4), 256, 0, st>>>(a);
     timer_end(h, P_ALOSS, st);
-    SCK_LAUNCH("actor_loss");
+    CK_LAUNCH("actor_loss");
   }
   if ((r = launch_gemm<T>(h, P_ABWD2, {
            dgrad_job(h->kq[0].w2t, h->dhp2[0], h->hp1[0], h->dhp1[0], nullptr, Np, N),
@@ -518,7 +489,7 @@ int enqueue_step(sac_learner* h, const sac_batch* b, hipStream_t st) {
     timer_begin(h, P_AHEAD, st);
     actor_head_bwd_kernel<T><<<cdiv(N, 4), 256, 0, st>>>(a);
     timer_end(h, P_AHEAD, st);
-    SCK_LAUNCH("actor_head_bwd");
+    CK_LAUNCH("actor_head_bwd");
   }
   float* ag = S.actor_grad;
   {
@@ -555,7 +526,7 @@ int enqueue_step(sac_learner* h, const sac_batch* b, hipStream_t st) {
     timer_begin(h, P_FIN, st);
     finalize_kernel<<<1, 256, 0, st>>>(f);
     timer_end(h, P_FIN, st);
-    SCK_LAUNCH("finalize");
+    CK_LAUNCH("finalize");
   }
   return 0;
 }
@@ -580,7 +551,7 @@ int launch_chain(sac_learner* h, int ph, std::initializer_list<ChainJob> jobs, i
   timer_begin(h, ph, st);
   chain_fwd_kernel<T><<<dim3(cdiv(n, 16), nj), 64 * FW, 0, st>>>(a);
   timer_end(h, ph, st);
-  SCK_LAUNCH(pname(ph));
+  CK_LAUNCH(pname(ph));
   return 0;
 }
 
@@ -608,7 +579,7 @@ int enqueue_step_fused(sac_learner* h, const sac_batch* b, hipStream_t st) {
     timer_begin(h, P_PACK, st);
     pack_kernel<T><<<std::max(1, std::min(256, cdiv(std::max((long long)N * h->DK, 3 * NK), 256))), 256, 0, st>>>(p);
     timer_end(h, P_PACK, st);
-    SCK_LAUNCH("pack");
+    CK_LAUNCH("pack");
   }
   // critic step: forward chains (target actor -> a1, Q1, Q2, actor -> pi) ...
   {
@@ -653,7 +624,7 @@ int enqueue_step_fused(sac_learner* h, const sac_batch* b, hipStream_t st) {
     timer_begin(h, P_CCHAIN, st);
     critic_chain_kernel<T><<<dim3(cdiv(N, 16), 2), 64 * FW, 0, st>>>(c);
     timer_end(h, P_CCHAIN, st);
-    SCK_LAUNCH("critic_loss_chain");
+    CK_LAUNCH("critic_loss_chain");
   }
   float* cg = S.critic_grad;
   {  // ... every critic weight gradient, clip + Adam + Polyak
@@ -692,7 +663,7 @@ int enqueue_step_fused(sac_learner* h, const sac_batch* b, hipStream_t st) {
     timer_begin(h, P_ACHAIN, st);
     actor_chain_kernel<T><<<cdiv(N, 16), 64 * FW, 0, st>>>(c);
     timer_end(h, P_ACHAIN, st);
-    SCK_LAUNCH("actor_chain");
+    CK_LAUNCH("actor_chain");
   }
   float* ag = S.actor_grad;
   {
@@ -721,7 +692,7 @@ int enqueue_step_fused(sac_learner* h, const sac_batch* b, hipStream_t st) {
     timer_begin(h, P_FIN, st);
     finalize_kernel<<<1, 256, 0, st>>>(f);
     timer_end(h, P_FIN, st);
-    SCK_LAUNCH("finalize");
+    CK_LAUNCH("finalize");
   }
   return 0;
 }
@@ -731,7 +702,7 @@ int enqueue_forward(sac_learner* h, const float* obs, int n, hipStream_t st, Hea
   const Offs& o = h->off;
   pack_obs_kernel<T><<<std::max(1, std::min(256, cdiv((long long)n * h->D, 256))), 256, 0, st>>>(
       obs, n, h->D, h->Dp, (T*)h->xi);
-  SCK_LAUNCH("pack_obs");
+  CK_LAUNCH("pack_obs");
   if (h->fused)
     return launch_chain<T>(h, -1, {chain_job(h->xi, h->Dp, h->Dp, h->ka, h->st.actor + o.a_b1,
                                              h->st.actor + o.a_b2, job)}, n, st);
@@ -755,7 +726,7 @@ int enqueue_q_forward(sac_learner* h, const float* obs, const float* act, int n,
   const MlpK* k = target ? h->ktq : h->kq;
   pack_sa_kernel<T><<<std::max(1, std::min(256, cdiv((long long)n * h->DK, 256))), 256, 0, st>>>(
       obs, act, n, h->D, h->K, h->Cp, (T*)h->xi2);
-  SCK_LAUNCH("pack_sa");
+  CK_LAUNCH("pack_sa");
   if (h->fused)
     return launch_chain<T>(h, -1, {
         chain_job(h->xi2, h->Cp, h->Cp, k[0], P + o.q_b1, P + o.q_b2, q_job(nullptr, P, 0, o, q1)),
@@ -773,51 +744,14 @@ int enqueue_q_forward(sac_learner* h, const float* obs, const float* act, int n,
   return launch_heads<T>(h, -1, {q_job(h->hp2[0], P, 0, o, q1), q_job(h->hp2[1], P, o.q_per, o, q2)}, n, st);
 }
 
-bool same_batch(const sac_batch& a, const sac_batch& b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
-
 int run_step(sac_learner* h, const sac_batch* b, hipStream_t st) {
   auto body = [&](hipStream_t s) {
     if (h->fused)
       return h->bf16 ? enqueue_step_fused<__bf16>(h, b, s) : enqueue_step_fused<float>(h, b, s);
     return h->bf16 ? enqueue_step<__bf16>(h, b, s) : enqueue_step<float>(h, b, s);
   };
-  if (!h->use_graph || h->timer_phase >= 0) return body(st);
-  for (auto& g : h->graphs)
-    if (g.exec && same_batch(g.key, *b)) {
-      g.used = ++h->tick;
-      SCK(hipGraphLaunch(g.exec, st));
-      return 0;
-    }
-  SCK(hipStreamBeginCapture(h->cap, hipStreamCaptureModeThreadLocal));
-  const int r = body(h->cap);
-  hipGraph_t graph = nullptr;
-  const hipError_t ee = hipStreamEndCapture(h->cap, &graph);
-  if (r || ee != hipSuccess) {
-    if (graph) (void)hipGraphDestroy(graph);
-    return r ? r : fail((int)ee, std::string("hipStreamEndCapture: ") + hipGetErrorString(ee));
-  }
-  hipGraphExec_t exec = nullptr;
-  const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  if (ei != hipSuccess) return fail((int)ei, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei));
-  auto* slot = &h->graphs[0];
-  for (auto& g : h->graphs) {
-    if (!g.exec) { slot = &g; break; }
-    if (g.used < slot->used) slot = &g;
-  }
-  if (slot->exec) (void)hipGraphExecDestroy(slot->exec);
-  slot->exec = exec;
-  slot->key = *b;
-  slot->used = ++h->tick;
-  SCK(hipGraphLaunch(exec, st));
-  return 0;
-}
-
-void drop_graphs(sac_learner* h) {
-  for (auto& g : h->graphs) {
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    g = sac_learner::GraphSlot{};
-  }
+  const bool bypass = !h->use_graph || h->timer_phase >= 0;
+  return h->graphs.run(!bypass, 0, *b, st, body);
 }
 
 int check_bound(sac_learner* h) {
@@ -941,19 +875,18 @@ int sac_create(const sac_config* cfg, int device, sac_learner** out) {
   h->fused = !(fz && fz[0] == '0') && h->Cp <= H;  // the chain kernels stage K1 <= 256
   auto cleanup = [&](int code) {
     if (h->arena) (void)hipFree(h->arena);
-    if (h->cap) (void)hipStreamDestroy(h->cap);
+    if (h->graphs.cap) (void)hipStreamDestroy(h->graphs.cap);
     delete h;
     return code;
   };
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return cleanup(fail((int)e, std::string("hipSetDevice: ") + hipGetErrorString(e)));
-  carve(h);  // size pass
-  h->arena_size = h->arena_used;
+  h->arena_size = carve(h, Arena{});
   e = hipMalloc(&h->arena, h->arena_size);
   if (e != hipSuccess) return cleanup(fail((int)e, std::string("hipMalloc: ") + hipGetErrorString(e)));
-  carve(h);
+  carve(h, Arena{(char*)h->arena});
   e = hipMemset(h->arena, 0, h->arena_size);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->graphs.cap, hipStreamNonBlocking);
   if (e != hipSuccess) return cleanup(fail((int)e, std::string("sac_create: ") + hipGetErrorString(e)));
   // rows of ones (bias gradients) after the last feature of every weight-gradient operand
   int r = 0;
@@ -981,10 +914,10 @@ int sac_destroy(sac_learner* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
-  drop_graphs(h);
+  h->graphs.drop();
   for (auto& e : h->ev) (void)hipEventDestroy(e);
   if (h->arena) (void)hipFree(h->arena);
-  if (h->cap) (void)hipStreamDestroy(h->cap);
+  if (h->graphs.cap) (void)hipStreamDestroy(h->graphs.cap);
   delete h;
   return 0;
 }
@@ -995,8 +928,8 @@ int sac_bind_state(sac_learner* h, const sac_state* s, void* stream) {
       !s->critic_grad || !s->critic_m || !s->critic_v || !s->target_critic || !s->log_alpha ||
       !s->metrics)
     return fail(IMPALA_E_INVALID, "sac_bind_state: every buffer is required");
-  SCK(hipSetDevice(h->device));
-  drop_graphs(h);
+  CK(hipSetDevice(h->device));
+  h->graphs.drop();
   h->st = *s;
   h->bound = true;
   return sac_refresh_weights(h, stream);
@@ -1004,24 +937,24 @@ int sac_bind_state(sac_learner* h, const sac_state* s, void* stream) {
 
 int sac_refresh_weights(sac_learner* h, void* stream) {
   if (int r = check_bound(h)) return r;
-  SCK(hipSetDevice(h->device));
+  CK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   for (int c = 0; c < 2; ++c) {
     const AdamNetArgs a = adam_args(h, c == 1, 0);
     if (h->bf16) adam_net_kernel<__bf16><<<cdiv(a.n, 256), 256, 0, st>>>(a);
     else adam_net_kernel<float><<<cdiv(a.n, 256), 256, 0, st>>>(a);
-    SCK_LAUNCH("sac_refresh_weights");
+    CK_LAUNCH("sac_refresh_weights");
   }
   return 0;
 }
 
 int sac_set_steps(sac_learner* h, int64_t cs, int64_t as, int64_t ls, void* stream) {
   if (!h) return fail(IMPALA_E_INVALID, "sac_set_steps: null handle");
-  SCK(hipSetDevice(h->device));
+  CK(hipSetDevice(h->device));
   static thread_local int64_t v[4];
   v[0] = cs; v[1] = as; v[2] = ls; v[3] = cs;
-  SCK(hipMemcpyAsync(h->steps, v, sizeof(v), hipMemcpyHostToDevice, (hipStream_t)stream));
-  SCK(hipStreamSynchronize((hipStream_t)stream));
+  CK(hipMemcpyAsync(h->steps, v, sizeof(v), hipMemcpyHostToDevice, (hipStream_t)stream));
+  CK(hipStreamSynchronize((hipStream_t)stream));
   return 0;
 }
 
@@ -1029,7 +962,7 @@ int sac_train_step(sac_learner* h, const sac_batch* b, void* stream) {
   if (int r = check_bound(h)) return r;
   if (!b || !b->s || !b->a || !b->r || !b->s1 || !b->done)
     return fail(IMPALA_E_INVALID, "sac_train_step: s, a, r, s1, done are required");
-  SCK(hipSetDevice(h->device));
+  CK(hipSetDevice(h->device));
   return run_step(h, b, (hipStream_t)stream);
 }
 
@@ -1038,7 +971,7 @@ int sac_act(sac_learner* h, const float* obs, int n, const float* noise, float n
   if (int r = check_bound(h)) return r;
   if (!obs || !action || n < 1 || n > h->N)
     return fail(IMPALA_E_INVALID, "sac_act: need obs/action and 1 <= n <= batch_size");
-  SCK(hipSetDevice(h->device));
+  CK(hipSetDevice(h->device));
   HeadJob j = policy_job(nullptr, h->st.actor, h->off, noise);
   j.kind = HK_ACT;
   j.noise_scale = noise_scale;
@@ -1054,7 +987,7 @@ int sac_policy(sac_learner* h, const float* obs, int n, const float* noise, floa
   if (int r = check_bound(h)) return r;
   if (!obs || n < 1 || n > h->N)
     return fail(IMPALA_E_INVALID, "sac_policy: need obs and 1 <= n <= batch_size");
-  SCK(hipSetDevice(h->device));
+  CK(hipSetDevice(h->device));
   HeadJob j = policy_job(nullptr, h->st.actor, h->off, noise);
   j.act = action;
   j.logp = log_prob;
@@ -1070,7 +1003,7 @@ int sac_q_forward(sac_learner* h, const float* obs, const float* act, int n, int
   if (int r = check_bound(h)) return r;
   if (!obs || !act || !q1 || !q2 || n < 1 || n > h->N)
     return fail(IMPALA_E_INVALID, "sac_q_forward: need obs/act/q1/q2 and 1 <= n <= batch_size");
-  SCK(hipSetDevice(h->device));
+  CK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   return h->bf16 ? enqueue_q_forward<__bf16>(h, obs, act, n, target != 0, q1, q2, st)
                  : enqueue_q_forward<float>(h, obs, act, n, target != 0, q1, q2, st);
@@ -1092,10 +1025,10 @@ int sac_debug_read(sac_learner* h, int which, void* dst, size_t bytes, void* str
   if (bytes != want)
     return fail(IMPALA_E_INVALID, "sac_debug_read: " + std::string(b.name) + " holds " +
                                       std::to_string(want) + " bytes, not " + std::to_string(bytes));
-  SCK(hipSetDevice(h->device));
+  CK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  SCK(hipMemcpyAsync(dst, b.p, bytes, hipMemcpyDeviceToHost, st));
-  SCK(hipStreamSynchronize(st));
+  CK(hipMemcpyAsync(dst, b.p, bytes, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
   return 0;
 }
 
@@ -1105,10 +1038,10 @@ const char* sac_phase_name(int p) { return (p >= 0 && p < P_COUNT) ? kPhase[p] :
 int sac_timer_start(sac_learner* h, int phase, int max_launches) {
   if (!h || phase < 0 || phase >= P_COUNT || max_launches < 1)
     return fail(IMPALA_E_INVALID, "sac_timer_start: bad argument");
-  SCK(hipSetDevice(h->device));
+  CK(hipSetDevice(h->device));
   while ((int)h->ev.size() < 2 * max_launches) {
     hipEvent_t e;
-    SCK(hipEventCreate(&e));
+    CK(hipEventCreate(&e));
     h->ev.push_back(e);
   }
   h->timer_phase = phase;
@@ -1119,12 +1052,12 @@ int sac_timer_start(sac_learner* h, int phase, int max_launches) {
 
 int sac_timer_read(sac_learner* h, float* total_ms, int* launches) {
   if (!h || !total_ms || !launches) return fail(IMPALA_E_INVALID, "sac_timer_read: null argument");
-  SCK(hipSetDevice(h->device));
+  CK(hipSetDevice(h->device));
   float tot = 0.f;
   for (int i = 0; i < h->timer_n; ++i) {
-    SCK(hipEventSynchronize(h->ev[2 * i + 1]));
+    CK(hipEventSynchronize(h->ev[2 * i + 1]));
     float ms = 0.f;
-    SCK(hipEventElapsedTime(&ms, h->ev[2 * i], h->ev[2 * i + 1]));
+    CK(hipEventElapsedTime(&ms, h->ev[2 * i], h->ev[2 * i + 1]));
     tot += ms;
   }
   *total_ms = tot;
@@ -1142,7 +1075,7 @@ int sac_sample(uint64_t seed, uint64_t counter, int64_t size, int n, int64_t* id
     return fail(IMPALA_E_INVALID, "sac_sample: nfields must be 0..8 with src/dst/row_bytes");
   hipStream_t st = (hipStream_t)stream;
   sample_kernel<<<1, 256, 0, st>>>(seed, counter, size, n, idx, probabilities);
-  SCK_LAUNCH("sample");
+  CK_LAUNCH("sample");
   if (nfields == 0) return 0;
   SGather g{};
   for (int f = 0; f < nfields; ++f) {
@@ -1155,7 +1088,7 @@ int sac_sample(uint64_t seed, uint64_t counter, int64_t size, int n, int64_t* id
   g.n = n;
   g.idx = idx;
   sample_gather_kernel<<<dim3(n, nfields), 64, 0, st>>>(g);
-  SCK_LAUNCH("sample_gather");
+  CK_LAUNCH("sample_gather");
   return 0;
 }
 

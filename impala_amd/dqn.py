@@ -86,23 +86,67 @@ def dqn_loss_head(adv, v, actions, targets, probabilities=None,
     return out
 
 
-class DqnEngine(_lib.NativeHandle):
-    """One ``dqn_learner`` handle bound to an ``AtariDQNModel``'s flat buffers."""
-    _destroy, _last_error = "dqn_destroy", _ERR
+class QEngine(_lib.NativeHandle):
+    """What the handles of the two Q-learners share, ``DqnEngine`` and ``IqnEngine``
+    (impala_amd/iqn.py): a subclass names its C-symbol prefix ``_abi`` and its error accessor;
+    their entry points ``<abi>_refresh_weights``, ``_set_metrics``, ``_set_step`` and
+    ``_sync_target`` take the same arguments."""
+    _abi: str
 
-    def __init__(self, model: "AtariDQNModel", batch_size: int = 512, dtype: Optional[str] = None,
-                 lr: float = 6.25e-5, eps: float = 1e-4, betas=(0.9, 0.999),
-                 max_grad_norm: float = 40.0, importance_sampling_exponent: float = 0.4,
-                 inference_only: bool = False):
+    def _call(self, entry: str, *args) -> None:
+        """``<abi>_<entry>(handle, *args)``, checked."""
+        name = f"{self._abi}_{entry}"
+        check(getattr(lib(), name)(self._h, *args), name, self._last_error)
+
+    def _begin(self, model, batch_size: int, dtype: Optional[str], default_config):
+        """The start of ``__init__``: the model, its device and the compute type; -> the ABI's
+        default configuration with batch size, action count and dtype filled in."""
         self.model = model
         self.device = model.flat.device
         if self.device.type != "cuda":
-            raise RuntimeError("the DQN engine runs on the HIP path only (cuda device)")
+            raise RuntimeError(f"the {self._abi.upper()} engine runs on the HIP path only (cuda device)")
         self.N, self.A = int(batch_size), model.action_dim
         cfg = default_config()
         cfg.batch_size, cfg.num_actions = self.N, self.A
         self.bf16 = (dtype or model.compute_dtype) == "bf16"
         cfg.dtype = _lib.IMPALA_DTYPE_BF16 if self.bf16 else _lib.IMPALA_DTYPE_F32
+        return cfg
+
+    def _fresh(self):
+        if self._version != self.model._version:  # the flat buffers were written from outside
+            self._call("refresh_weights", _lib.stream_ptr(None))
+            self._version = self.model._version
+
+    def bind_metrics(self, m: torch.Tensor) -> None:
+        self.metrics = m
+        self._call("set_metrics", _lib.ptr(m))
+
+    def set_step(self, step: int) -> None:
+        self._call("set_step", int(step), _lib.stream_ptr(None))
+
+    def sync_target(self) -> None:
+        self._fresh()
+        self._call("sync_target", _lib.stream_ptr(None))
+
+    def _eps_args(self, eps, n: int):
+        """``act``'s exploration rate -> (eps_t [n] on the device or None, eps_all)."""
+        if isinstance(eps, torch.Tensor) and eps.numel() > 1:
+            eps_t = eps.reshape(-1).to(self.device, torch.float32).contiguous()
+            if eps_t.numel() != n:
+                raise ValueError("eps: one value, or one per frame")
+            return eps_t, 0.0
+        return None, float(eps.reshape(-1)[0]) if isinstance(eps, torch.Tensor) else float(eps)
+
+
+class DqnEngine(QEngine):
+    """One ``dqn_learner`` handle bound to an ``AtariDQNModel``'s flat buffers."""
+    _abi, _destroy, _last_error = "dqn", "dqn_destroy", _ERR
+
+    def __init__(self, model: "AtariDQNModel", batch_size: int = 512, dtype: Optional[str] = None,
+                 lr: float = 6.25e-5, eps: float = 1e-4, betas=(0.9, 0.999),
+                 max_grad_norm: float = 40.0, importance_sampling_exponent: float = 0.4,
+                 inference_only: bool = False):
+        cfg = self._begin(model, batch_size, dtype, default_config)
         cfg.lr, cfg.adam_eps = lr, eps
         cfg.adam_beta1, cfg.adam_beta2 = betas
         cfg.max_grad_norm = max_grad_norm
@@ -121,18 +165,6 @@ class DqnEngine(_lib.NativeHandle):
         check(lib().dqn_bind_target(self._h, _lib.ptr(model.target_flat), sp), "dqn_bind_target", _ERR)
         self._version = model._version
 
-    def _fresh(self):
-        if self._version != self.model._version:  # the flat buffers were written from outside
-            check(lib().dqn_refresh_weights(self._h, _lib.stream_ptr(None)), "dqn_refresh_weights", _ERR)
-            self._version = self.model._version
-
-    def bind_metrics(self, m: torch.Tensor) -> None:
-        self.metrics = m
-        check(lib().dqn_set_metrics(self._h, _lib.ptr(m)), "dqn_set_metrics", _ERR)
-
-    def set_step(self, step: int) -> None:
-        check(lib().dqn_set_step(self._h, int(step), _lib.stream_ptr(None)), "dqn_set_step", _ERR)
-
     def forward(self, obs: torch.Tensor, target: bool = False) -> torch.Tensor:
         self._fresh()
         obs = obs.contiguous()
@@ -147,13 +179,7 @@ class DqnEngine(_lib.NativeHandle):
         self._fresh()
         obs = obs.contiguous()
         n = obs.shape[0]
-        eps_t, eps_all = None, 0.0
-        if isinstance(eps, torch.Tensor) and eps.numel() > 1:
-            eps_t = eps.reshape(-1).to(self.device, torch.float32).contiguous()
-            if eps_t.numel() != n:
-                raise ValueError("eps: one value, or one per frame")
-        else:
-            eps_all = float(eps.reshape(-1)[0]) if isinstance(eps, torch.Tensor) else float(eps)
+        eps_t, eps_all = self._eps_args(eps, n)
         a = torch.empty(n, dtype=torch.int64, device=self.device)
         g = torch.empty(n, dtype=torch.int64, device=self.device)
         q_pi, q_star = torch.empty(n, device=self.device), torch.empty(n, device=self.device)
@@ -161,10 +187,6 @@ class DqnEngine(_lib.NativeHandle):
                             int(counter), _lib.ptr(a), _lib.ptr(q_pi), _lib.ptr(q_star),
                             _lib.ptr(g), _lib.stream_ptr(None)), "dqn_act", _ERR)
         return a, q_pi, q_star, g
-
-    def sync_target(self) -> None:
-        self._fresh()
-        check(lib().dqn_sync_target(self._h, _lib.stream_ptr(None)), "dqn_sync_target", _ERR)
 
     def train_step(self, obs, actions, targets, probabilities=None) -> torch.Tensor:
         """One learner step; returns the new priorities |err| [N] (device)."""
@@ -197,16 +219,10 @@ class DqnEngine(_lib.NativeHandle):
         n = self.N if frames is None else int(frames)
         if not 1 <= n <= self.N:
             raise ValueError(f"frames must be in [1, {self.N}]")
-        dt = {"T": torch.bfloat16 if self.bf16 else torch.float32, "f32": torch.float32,
-              "u32": torch.int32}[kind]
-        buf = torch.empty((n,) + shape, dtype=dt, device=self.device)
-        check(lib().dqn_debug_read(self._h, 1 if target else 0, which, _lib.ptr(buf),
-                                   buf.numel() * buf.element_size(), _lib.stream_ptr(None)),
-              "dqn_debug_read", _ERR)
-        torch.cuda.current_stream().synchronize()
-        if kind == "u32":
-            return buf.cpu().numpy().view(np.uint32)
-        return buf.float().cpu().numpy()
+        return _lib.read_debug(
+            lambda dst, nbytes, sp: check(lib().dqn_debug_read(self._h, 1 if target else 0, which, dst,
+                                                               nbytes, sp), "dqn_debug_read", _ERR),
+            kind, shape, n, self.bf16, self.device)
 
     def _step(self, entry: str, obs, actions, targets, probabilities) -> torch.Tensor:
         self._fresh()
@@ -253,13 +269,13 @@ class DqnEngine(_lib.NativeHandle):
         return keys, prio
 
 
-class AtariDQNModel(FlatModule):
-    """Drop-in for ``models.distributed_models.AtariDQNModel`` on an MI355X: the online and the
-    target net are one flat fp32 buffer each, exposed as ``nn.Parameter`` views under the
-    reference's ``state_dict`` names (``target_net.*`` with ``requires_grad=False``)."""
+class QModel(FlatModule):
+    """What ``AtariDQNModel`` and ``DistributionalAtariDQN`` (impala_amd/iqn.py) share: an online
+    and a target net of the same ``specs``, one flat fp32 buffer each, and the lazily made
+    inference engine.  A subclass gives ``_init_flat`` and ``_make_infer_engine``, and ends its
+    ``__init__`` with ``reset_parameters(seed)``."""
 
-    def __init__(self, observation_space: Tuple[int, ...] = OBS_SHAPE, action_dim: int = 15,
-                 device="cuda", seed: Optional[int] = None, dtype: str = "fp32"):
+    def __init__(self, observation_space, action_dim: int, specs, device, dtype: str):
         super().__init__()
         if tuple(observation_space) != OBS_SHAPE:
             raise ValueError(f"AtariBody requires observations of shape {OBS_SHAPE}")
@@ -267,27 +283,33 @@ class AtariDQNModel(FlatModule):
             raise ValueError("action_dim must be in [1, 15]")
         self.action_dim = action_dim
         self.compute_dtype = dtype
-        device = torch.device(device)
-        self._specs = net_specs(action_dim)
-        self._attach_segments(device)
+        self._specs = specs
+        self._attach_segments(torch.device(device))
         self._train_engine = None
         self._infer_engine = None
         self._act_seed = int.from_bytes(os.urandom(8), "little") >> 2
         self._act_calls = 0
-        self.reset_parameters(seed)
 
     def _segment_table(self):
         return [("online_net", self._specs, "flat", "flat_grad"),
                 ("target_net", self._specs, "target_flat", None)]
 
+    def _init_flat(self) -> torch.Tensor:
+        """Hook: the reference init of one net as a flat CPU tensor (consumes the global RNG)."""
+        raise NotImplementedError
+
+    def _make_infer_engine(self):
+        """Hook: the engine ``forward`` / ``act`` run on while no learner has attached its own."""
+        raise NotImplementedError
+
     # ---------------------------------------------------------------- parameters
     def reset_parameters(self, seed: Optional[int] = None) -> None:
-        """Reference init (``trunk_init_flat``, after seeding the global torch RNG with ``seed``);
-        the target net is a copy of the online net (distributed_models.py:77)."""
+        """Reference init (``_init_flat``, after seeding the global torch RNG with ``seed``); the
+        target net is a copy of the online net."""
         if seed is not None:
             torch.manual_seed(int(seed))
         with torch.no_grad():
-            self.flat.copy_(trunk_init_flat(HIDDEN, self.action_dim).to(self.flat.device))
+            self.flat.copy_(self._init_flat().to(self.flat.device))
             self.target_flat.copy_(self.flat)
         self.params_changed()
 
@@ -300,13 +322,37 @@ class AtariDQNModel(FlatModule):
         self.params_changed()
 
     # ---------------------------------------------------------------- compute
-    def _engine(self) -> DqnEngine:
+    def _engine(self):
         if self._train_engine is not None:
             return self._train_engine
         if self._infer_engine is None:
-            # the reference serves act() in batches of <= 128 (distributed_models.py:84)
-            self._infer_engine = DqnEngine(self, batch_size=128, inference_only=True)
+            self._infer_engine = self._make_infer_engine()
         return self._infer_engine
+
+    def sync_target_net(self) -> None:
+        if self.flat.device.type == "cuda":
+            self._engine().sync_target()
+        else:
+            with torch.no_grad():
+                self.target_flat.copy_(self.flat)
+
+
+class AtariDQNModel(QModel):
+    """Drop-in for ``models.distributed_models.AtariDQNModel`` on an MI355X: the online and the
+    target net are one flat fp32 buffer each, exposed as ``nn.Parameter`` views under the
+    reference's ``state_dict`` names (``target_net.*`` with ``requires_grad=False``)."""
+
+    def __init__(self, observation_space: Tuple[int, ...] = OBS_SHAPE, action_dim: int = 15,
+                 device="cuda", seed: Optional[int] = None, dtype: str = "fp32"):
+        super().__init__(observation_space, action_dim, net_specs(action_dim), device, dtype)
+        self.reset_parameters(seed)
+
+    def _init_flat(self) -> torch.Tensor:  # (the target a copy: distributed_models.py:77)
+        return trunk_init_flat(HIDDEN, self.action_dim)
+
+    def _make_infer_engine(self) -> DqnEngine:
+        # the reference serves act() in batches of <= 128 (distributed_models.py:84)
+        return DqnEngine(self, batch_size=128, inference_only=True)
 
     def forward(self, obs: torch.Tensor) -> torch.Tensor:
         """distributed_models.py:81-82 -> q [N, A] of the online net."""
@@ -325,13 +371,6 @@ class AtariDQNModel(FlatModule):
         self._act_calls += 1
         a, q_pi, q_star, _ = self._engine().act(x, eps, seed=self._act_seed, counter=self._act_calls)
         return a.unsqueeze(-1).cpu(), q_pi.unsqueeze(-1).cpu(), q_star.unsqueeze(-1).cpu()
-
-    def sync_target_net(self) -> None:  # distributed_models.py:103-104
-        if self.flat.device.type == "cuda":
-            self._engine().sync_target()
-        else:
-            with torch.no_grad():
-                self.target_flat.copy_(self.flat)
 
     def clone_to(self, device) -> "AtariDQNModel":
         return self._frozen_clone(AtariDQNModel(OBS_SHAPE, self.action_dim, device=device,

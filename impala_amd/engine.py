@@ -165,20 +165,10 @@ class Engine(_lib.NativeHandle):
         n = self.frames if frames is None else int(frames)
         if not 1 <= n <= self.frames:
             raise ValueError(f"frames must be in [1, {self.frames}]")
-        bf16 = DTYPES[self.dtype] == _lib.IMPALA_DTYPE_BF16
-        dt = {"T": torch.bfloat16 if bf16 else torch.float32, "f32": torch.float32,
-              "u32": torch.int32}[kind]
-        buf = torch.empty((n,) + shape, dtype=dt, device=self.device)
-        check(_lib.lib().impala_debug_read(self._h, which, ptr(buf), buf.numel() * buf.element_size(),
-                                           stream_ptr(stream)), "impala_debug_read")
-        if stream is None:
-            torch.cuda.current_stream().synchronize()
-        else:
-            stream.synchronize()
-        if kind == "u32":
-            import numpy as np
-            return buf.cpu().numpy().view(np.uint32)
-        return buf.float().cpu().numpy()
+        return _lib.read_debug(
+            lambda dst, nbytes, sp: check(_lib.lib().impala_debug_read(self._h, which, dst, nbytes, sp),
+                                          "impala_debug_read"),
+            kind, shape, n, DTYPES[self.dtype] == _lib.IMPALA_DTYPE_BF16, self.device, stream)
 
     # ------------------------------------------------------------------ compute
     def forward(self, obs: torch.Tensor, stream=None):

@@ -14,10 +14,8 @@ compute path is the HIP library only.  The learner samples from the torch
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Dict, List, Optional, Tuple
 
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -25,8 +23,8 @@ from impala_amd import _lib
 from impala_amd._lib import check, lib
 from impala_amd.core import Actor
 from impala_amd.dqn import (ApexActor, ApexDQNBuilder, ApexLearner, ConstantEpsFunc,
-                            FlexibleEpsFunc, PrioritizedReplay)
-from impala_amd.flat import FlatModule, layer_init_truncated, spec_count
+                            FlexibleEpsFunc, PrioritizedReplay, QEngine, QModel)
+from impala_amd.flat import layer_init_truncated, spec_count
 from impala_amd.model import OBS_SHAPE
 
 HIDDEN = 512
@@ -125,23 +123,16 @@ def iqn_loss_head(adv, v, actions, taus, targets, probabilities=None, huber_para
     return out
 
 
-class IqnEngine(_lib.NativeHandle):
+class IqnEngine(QEngine):
     """One ``iqn_learner`` handle bound to a ``DistributionalAtariDQN``'s flat buffers."""
-    _destroy, _last_error = "iqn_destroy", _ERR
+    _abi, _destroy, _last_error = "iqn", "iqn_destroy", _ERR
 
     def __init__(self, model: "DistributionalAtariDQN", batch_size: int = 128,
                  dtype: Optional[str] = None, train: bool = False, lr: float = 6.25e-5,
                  eps: float = 1e-4, betas=(0.9, 0.999), max_grad_norm: float = 40.0,
                  importance_sampling_exponent: float = 0.4, huber_param: float = 1.0):
-        self.model = model
-        self.device = model.flat.device
-        if self.device.type != "cuda":
-            raise RuntimeError("the IQN engine runs on the HIP path only (cuda device)")
-        self.N, self.A, self.W = int(batch_size), model.action_dim, model.n_tau_samples
-        cfg = default_config()
-        cfg.batch_size, cfg.num_actions, cfg.n_tau = self.N, self.A, self.W
-        self.bf16 = (dtype or model.compute_dtype) == "bf16"
-        cfg.dtype = _lib.IMPALA_DTYPE_BF16 if self.bf16 else _lib.IMPALA_DTYPE_F32
+        cfg = self._begin(model, batch_size, dtype, default_config)
+        self.W = cfg.n_tau = model.n_tau_samples
         self._open("iqn_create", C.byref(cfg), self.device_index(self.device))
         check(lib().iqn_bind_params(self._h, _lib.ptr(model.flat), _lib.ptr(model.target_flat),
                                     _lib.stream_ptr(None)), "iqn_bind_params", _ERR)
@@ -158,11 +149,6 @@ class IqnEngine(_lib.NativeHandle):
                                        _lib.ptr(self.metrics), C.byref(opt), _lib.stream_ptr(None)),
                   "iqn_bind_state", _ERR)
         self._version = model._version
-
-    def _fresh(self):
-        if self._version != self.model._version:  # the flat buffers were written from outside
-            check(lib().iqn_refresh_weights(self._h, _lib.stream_ptr(None)), "iqn_refresh_weights", _ERR)
-            self._version = self.model._version
 
     def _taus(self, taus, n):
         if taus is None:
@@ -192,13 +178,7 @@ class IqnEngine(_lib.NativeHandle):
         self._fresh()
         obs = obs.contiguous()
         n = obs.shape[0]
-        eps_t, eps_all = None, 0.0
-        if isinstance(eps, torch.Tensor) and eps.numel() > 1:
-            eps_t = eps.reshape(-1).to(self.device, torch.float32).contiguous()
-            if eps_t.numel() != n:
-                raise ValueError("eps: one value, or one per frame")
-        else:
-            eps_all = float(eps.reshape(-1)[0]) if isinstance(eps, torch.Tensor) else float(eps)
+        eps_t, eps_all = self._eps_args(eps, n)
         t_on, t_tg = self._taus(taus_online, n), self._taus(taus_target, n)
         a = torch.empty(n, dtype=torch.int64, device=self.device)
         g = torch.empty(n, dtype=torch.int64, device=self.device)
@@ -209,18 +189,7 @@ class IqnEngine(_lib.NativeHandle):
               "iqn_act", _ERR)
         return a, q_pi, q_star, g
 
-    def sync_target(self) -> None:
-        self._fresh()
-        check(lib().iqn_sync_target(self._h, _lib.stream_ptr(None)), "iqn_sync_target", _ERR)
-
     # ---------------------------------------------------------------- training
-    def bind_metrics(self, m: torch.Tensor) -> None:
-        self.metrics = m
-        check(lib().iqn_set_metrics(self._h, _lib.ptr(m)), "iqn_set_metrics", _ERR)
-
-    def set_step(self, step: int) -> None:
-        check(lib().iqn_set_step(self._h, int(step), _lib.stream_ptr(None)), "iqn_set_step", _ERR)
-
     def train_step(self, obs, actions, targets, probabilities=None, taus=None, seed: int = 0,
                    counter: int = 0):
         """One learner step (``iqn_train_step``) -> (priorities [N], taus [N, W]) on the device;
@@ -283,18 +252,13 @@ class IqnEngine(_lib.NativeHandle):
         n = self.N if frames is None else int(frames)
         if not 1 <= n <= self.N:
             raise ValueError(f"frames must be in [1, {self.N}]")
-        dt = {"T": torch.bfloat16 if self.bf16 else torch.float32, "f32": torch.float32,
-              "u32": torch.int32}[kind]
-        buf = torch.empty((n * self.W if per_row else n,) + shape, dtype=dt, device=self.device)
-        check(lib().iqn_debug_read(self._h, which, _lib.ptr(buf), buf.numel() * buf.element_size(),
-                                   _lib.stream_ptr(None)), "iqn_debug_read", _ERR)
-        torch.cuda.current_stream().synchronize()
-        if kind == "u32":
-            return buf.cpu().numpy().view(np.uint32)
-        return buf.float().cpu().numpy()
+        return _lib.read_debug(
+            lambda dst, nbytes, sp: check(lib().iqn_debug_read(self._h, which, dst, nbytes, sp),
+                                          "iqn_debug_read", _ERR),
+            kind, shape, n * self.W if per_row else n, self.bf16, self.device)
 
 
-class DistributionalAtariDQN(FlatModule):
+class DistributionalAtariDQN(QModel):
     """Drop-in for ``models.distributed_models.DistributionalAtariDQN`` on an MI355X: the online
     and the target net are one flat fp32 buffer each, exposed as ``nn.Parameter`` views under the
     reference's ``state_dict`` names (``target_net.*`` with ``requires_grad=False``), with the
@@ -303,59 +267,22 @@ class DistributionalAtariDQN(FlatModule):
     def __init__(self, observation_space: Tuple[int, ...] = OBS_SHAPE, action_dim: int = 15,
                  n_tau_samples: int = 32, device="cuda", seed: Optional[int] = None,
                  dtype: str = "fp32"):
-        super().__init__()
-        if tuple(observation_space) != OBS_SHAPE:
-            raise ValueError(f"AtariBody requires observations of shape {OBS_SHAPE}")
-        if not 1 <= action_dim <= 15:
-            raise ValueError("action_dim must be in [1, 15]")
+        super().__init__(observation_space, action_dim, net_specs(action_dim), device, dtype)
         if not 1 <= n_tau_samples <= _lib.IQN_MAX_TAU:
             raise ValueError(f"n_tau_samples must be in [1, {_lib.IQN_MAX_TAU}]")
-        self.action_dim = action_dim
         self.n_tau_samples = int(n_tau_samples)
-        self.compute_dtype = dtype
-        device = torch.device(device)
-        self._specs = net_specs(action_dim)
-        self._attach_segments(device)
         for net in (self.online_net, self.target_net):  # QuantileLayer's buffer (int64, (1, 1, 64))
             net.q.quantile_layer.register_buffer(
-                "embedding_range", torch.arange(1, N_COS + 1, device=device).reshape(1, 1, N_COS))
-        self._train_engine = None
-        self._infer_engine = None
-        self._act_seed = int.from_bytes(os.urandom(8), "little") >> 2
-        self._act_calls = 0
+                "embedding_range",
+                torch.arange(1, N_COS + 1, device=self.flat.device).reshape(1, 1, N_COS))
         self.reset_parameters(seed)
 
-    def _segment_table(self):
-        return [("online_net", self._specs, "flat", "flat_grad"),
-                ("target_net", self._specs, "target_flat", None)]
+    def _init_flat(self) -> torch.Tensor:  # (the target a copy: distributed_models.py:40)
+        return iqn_init_flat(self.action_dim)
 
-    # ---------------------------------------------------------------- parameters
-    def reset_parameters(self, seed: Optional[int] = None) -> None:
-        """Reference init (``iqn_init_flat``, after seeding the global torch RNG with ``seed``);
-        the target net is a copy of the online net (distributed_models.py:40)."""
-        if seed is not None:
-            torch.manual_seed(int(seed))
-        with torch.no_grad():
-            self.flat.copy_(iqn_init_flat(self.action_dim).to(self.flat.device))
-            self.target_flat.copy_(self.flat)
-        self.params_changed()
-
-    def load_flat(self, flat, target=None) -> None:
-        with torch.no_grad():
-            self.flat.copy_(torch.as_tensor(np.asarray(flat, dtype=np.float32)).to(self.flat.device))
-            if target is not None:
-                self.target_flat.copy_(torch.as_tensor(np.asarray(target, dtype=np.float32)).to(
-                    self.flat.device))
-        self.params_changed()
-
-    # ---------------------------------------------------------------- compute
-    def _engine(self) -> IqnEngine:
-        if self._train_engine is not None:
-            return self._train_engine
-        if self._infer_engine is None:
-            # the reference serves act() in batches of <= 128 (distributed_models.py:47)
-            self._infer_engine = IqnEngine(self, batch_size=128)
-        return self._infer_engine
+    def _make_infer_engine(self) -> IqnEngine:
+        # the reference serves act() in batches of <= 128 (distributed_models.py:47)
+        return IqnEngine(self, batch_size=128)
 
     def _next_draw(self) -> Tuple[int, int]:
         self._act_calls += 1
@@ -380,13 +307,6 @@ class DistributionalAtariDQN(FlatModule):
         seed, counter = self._next_draw()
         a, q_pi, q_star, _ = self._engine().act(x, eps, seed=seed, counter=counter)
         return a.unsqueeze(-1).cpu(), q_pi.unsqueeze(-1).cpu(), q_star.cpu()
-
-    def sync_target_net(self) -> None:  # distributed_models.py:68-69
-        if self.flat.device.type == "cuda":
-            self._engine().sync_target()
-        else:
-            with torch.no_grad():
-                self.target_flat.copy_(self.flat)
 
     def clone_to(self, device) -> "DistributionalAtariDQN":
         return self._frozen_clone(DistributionalAtariDQN(

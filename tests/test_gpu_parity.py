@@ -360,6 +360,37 @@ def test_launch_modes_agree(env, exact, monkeypatch):
         np.testing.assert_allclose(base[1], alt[1], rtol=1e-2, atol=3e-3)
 
 
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_graph_cache_evicts_and_recaptures(dtype, monkeypatch):
+    """The step graph cache (IMPALA_GRAPH=1) past its eight slots and past one kind, against a
+    direct-launch engine fed the same calls: ten batches held in ten distinct tensor sets, each
+    stepped once (the ninth and tenth captures evict the first two); compute_grads and
+    apply_update on the first set (two more kinds, two more evictions); then train_step on the
+    first set again, whose graph was evicted and is captured anew.  Parameters and metrics are
+    bitwise equal after every call."""
+    dev = _dev()
+    B, T, A = 2, 3, 3
+    sets = [[_t(x, dev) for x in ref_cpu.synthetic_batch(B, T, A, seed=40 + i)] for i in range(10)]
+    assert len({s[0].data_ptr() for s in sets}) == len(sets)
+    direct_m = _model(dev, dtype, A=A, seed=0)
+    direct = _engine(direct_m, B, T)
+    monkeypatch.setenv("IMPALA_GRAPH", "1")  # (read when a handle is created)
+    graphed_m = _model(dev, dtype, A=A, seed=0)
+    graphed = _engine(graphed_m, B, T)
+
+    calls = [("train_step", s) for s in sets]
+    calls += [("compute_grads", sets[0]), ("apply_update", ()), ("train_step", sets[0])]
+    for i, (name, args) in enumerate(calls):
+        for e in (direct, graphed):
+            getattr(e, name)(*args)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(direct_m.flat.cpu().numpy(), graphed_m.flat.cpu().numpy(),
+                                      err_msg=f"params after call {i} ({name})")
+        np.testing.assert_array_equal(direct.metrics.cpu().numpy(), graphed.metrics.cpu().numpy(),
+                                      err_msg=f"metrics after call {i} ({name})")
+    assert np.isfinite(direct.metrics.cpu().numpy()).all()
+
+
 @pytest.mark.parametrize("env", [{"IMPALA_GRAPH": "1"}, {"IMPALA_FC_MERGED": "0"},
                                  {"IMPALA_WG23_MERGED": "0"}, {"IMPALA_C3_TAIL": "0"},
                                  {"IMPALA_LC12": "0"}],
