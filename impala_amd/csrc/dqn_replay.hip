@@ -194,6 +194,11 @@ __global__ __launch_bounds__(256) void replay_draw_kernel(const double* __restri
   }
 }
 
+// priority ** alpha in float64.  alpha == 1 is the priority itself: the device pow(x, 1.0) is
+// within 1e-14 rel of x but not always x, and at that exponent the weights are exact numbers whose
+// sums do not depend on the order (tests/test_gpu_dqn_replay_scale.py draws on that).
+DEV double replay_weight(float p, double alpha) { return alpha == 1.0 ? (double)p : pow((double)p, alpha); }
+
 DEV float block_max_256(float m, float* red) {  // every thread of a 256-multiple workgroup calls it
   m = wave_max(m);
   const int nw = blockDim.x >> 6;
@@ -226,7 +231,7 @@ __global__ __launch_bounds__(256) void replay_update_kernel(const int64_t* __res
     const long long k = keys[j];
     if (k < 0 || k >= cap) continue;
     const float p = *(volatile const float*)(prio + k);
-    w[k] = pow((double)p, alpha);
+    w[k] = replay_weight(p, alpha);
   }
   if (threadIdx.x == 0) *maxp = fmaxf(*maxp, m);
 }
@@ -249,7 +254,7 @@ __global__ __launch_bounds__(256) void replay_extend_kernel(const int64_t* __res
   r_tgt[k] = tgt[i];
   const float p = pin ? pin[i] : *maxp;
   r_prio[k] = p;
-  w[k] = pow((double)p, alpha);
+  w[k] = replay_weight(p, alpha);
   if (keys_out) keys_out[i] = k;
 }
 
@@ -277,7 +282,7 @@ __global__ __launch_bounds__(256) void replay_rollout_kernel(const int64_t* __re
   r_act[k] = act[t];
   r_tgt[k] = acc;
   r_prio[k] = p;
-  w[k] = pow((double)p, alpha);
+  w[k] = replay_weight(p, alpha);
   if (keys_out) keys_out[t] = k;
 }
 

@@ -148,6 +148,7 @@ int dqn_loss_head(const float* adv, const float* v, const int64_t* actions, cons
  * dqn_train_step_replay).  Cursor and size live on the host.  Invariant, for every row i written
  * since dqn_replay_bind (i < size):
  *   weights[i] == pow((double)priorities[i], priority_exponent)      (the exponent is a double)
+ * (at priority_exponent == 1 the priority itself, exactly: the device pow(x, 1.0) is not always x)
  * kept where a priority is written (extend, extend_rollout, update); a sample calls no pow.
  * dqn_replay_bind zeroes the weights and leaves the caller's arrays as they are; a sample never
  * reads rows >= size.

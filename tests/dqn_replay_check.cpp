@@ -1,7 +1,9 @@
 // CPU check of impala_amd/csrc/dqn_replay_host.h (tests/test_dqn_replay_host.py): the ring's
 // cursor / size / wrap arithmetic against a plain per-row model, the spans of an append, the
 // launch shape of the block-sum scan and the argument checks.  Built with
-// -fsanitize=address,undefined; no GPU involved.
+// -fsanitize=address,undefined; no GPU involved.  With the argument "scan_chunk" it prints
+// scan_chunk(nb) for every legal nb instead, one per line: the table the Python mirror
+// (tests/dqn_replay_oracle.py) is compared with.
 #include "../impala_amd/csrc/dqn_replay_host.h"
 
 #include <cstdio>
@@ -16,8 +18,12 @@
     }                                                                  \
   } while (0)
 
-int main() {
+int main(int argc, char** argv) {
   using namespace dqn_replay_host;
+  if (argc > 1 && std::strcmp(argv[1], "scan_chunk") == 0) {
+    for (int64_t nb = 1; nb <= kMaxBlocks; ++nb) std::printf("%d\n", scan_chunk(nb));
+    return 0;
+  }
   // appends of every size at every cursor against a per-row model: the spans cover the input
   // once, in order, inside the ring
   for (int64_t cap : {1, 2, 7, 8, 64}) {

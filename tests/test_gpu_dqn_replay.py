@@ -3,8 +3,11 @@
 ingest, and dqn_train_step_replay against its three parts.
 
 Tolerances: keys exact (the inputs are first shown, on the reference alone, to keep every
-u * total 1e-9 * total away from a prefix boundary -- float64 summation order moves a boundary by
-~1e-13 * total at these sizes); probabilities 1e-6 rel (a float32 rounding of a float64 quotient);
+u * total 1e-9 * total away from a prefix boundary -- the kernels' summation order, np.cumsum and an
+80-bit prefix differ by at most 1.8e-15 * total at these sizes, 1 to 1535 rows, as
+dqn_replay_oracle.prefix_discrepancy measures it: 4.3e-16 at 600 rows, 5.3e-16 at 513 and 777,
+1.8e-15 at 1535; the rings of tests/test_gpu_dqn_replay_scale.py, 2567 to 360 000 rows, measure 9.2e-16 to
+2.0e-14 and derive their condition from it); probabilities 1e-6 rel (a float32 rounding of a float64 quotient);
 weights 1e-14 rel (device pow against numpy's, both within a few ulp of 2.2e-16); n-step targets
 rtol 1e-6 + atol 1e-6 (<= 16 fp32 multiply-adds against float64)."""
 import numpy as np
