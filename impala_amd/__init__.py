@@ -7,12 +7,13 @@ Drop-in for the learner path of d3sm0/impala: ``agents/core.py`` Learner/Builder
 from impala_amd.model import AtariPPOModel, param_count, param_specs  # noqa: F401
 
 __all__ = ["AtariPPOModel", "param_count", "param_specs", "DistributionalAtariDQN",
-           "ApexDistributionalActor", "ApexDistributionalBuilder", "IqnEngine"]
+           "ApexDistributionalActor", "ApexDistributionalBuilder", "IqnEngine",
+           "NativeQuantileReplay"]
 
 
 def __getattr__(name):  # the IQN names, imported on first use (impala_amd.iqn imports impala_amd.dqn)
     if name in ("DistributionalAtariDQN", "ApexDistributionalActor", "ApexDistributionalBuilder",
-                "IqnEngine"):
+                "IqnEngine", "NativeQuantileReplay"):
         from impala_amd import iqn
         return getattr(iqn, name)
     raise AttributeError(name)

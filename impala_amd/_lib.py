@@ -92,8 +92,11 @@ IQN_EXPORTS = (
     "iqn_act", "iqn_nstep_targets", "iqn_loss_head", "iqn_debug_read", "iqn_optim_default",
     "iqn_bind_state", "iqn_set_metrics", "iqn_set_step", "iqn_train_step", "iqn_compute_grads",
     "iqn_apply_update",
+    "iqn_replay_create", "iqn_replay_destroy", "iqn_replay_bind", "iqn_replay_state",
+    "iqn_replay_extend", "iqn_replay_extend_rollout", "iqn_replay_sample", "iqn_replay_update",
+    "iqn_replay_weights", "iqn_train_step_replay",
 )
-IQN_ABI_VERSION = 2
+IQN_ABI_VERSION = 3
 IQN_DBG_DPRE, IQN_DBG_DX, IQN_DBG_COS = 100, 101, 102
 IQN_MAX_TAU = 32
 IQN_MAX_ROWS = 16384
@@ -343,6 +346,18 @@ def _declare(lib):
     lib.iqn_train_step.argtypes = [_P, C.POINTER(IqnBatch), _P]
     lib.iqn_compute_grads.argtypes = [_P, C.POINTER(IqnBatch), _P]
     lib.iqn_apply_update.argtypes = [_P, _P]
+    lib.iqn_replay_create.argtypes = [C.c_int64, C.c_int, C.c_double, C.c_int, C.POINTER(_P)]
+    lib.iqn_replay_destroy.argtypes = [_P]
+    lib.iqn_replay_bind.argtypes = [_P, _P, _P, _P, _P, _P]
+    lib.iqn_replay_state.argtypes = [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.iqn_replay_extend.argtypes = [_P, _P, _P, _P, _P, C.c_int64, _P, _P]
+    lib.iqn_replay_extend_rollout.argtypes = [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int,
+                                              C.c_float, _P, _P]
+    lib.iqn_replay_sample.argtypes = [_P, C.c_uint64, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]
+    lib.iqn_replay_update.argtypes = [_P, _P, _P, C.c_int64, _P]
+    lib.iqn_replay_weights.argtypes = [_P, _P, _P, _P]
+    lib.iqn_train_step_replay.argtypes = [_P, _P, C.c_uint64, C.c_uint64, _P, C.c_uint64,
+                                          C.c_uint64, _P, _P, _P, _P]
     for name in IQN_EXPORTS:
         getattr(lib, name).restype = (C.c_char_p if name == "iqn_last_error" else
                                       C.c_size_t if name == "iqn_param_count" else C.c_int)

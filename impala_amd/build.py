@@ -1,6 +1,6 @@
 """Build the HIP extension in-tree: ``python -m impala_amd.build``.
 
-Compiles ``impala_amd/csrc/{impala,sac,dqn_replay,ppo_replay,dqn_inplace,iqn}.hip`` for gfx950 into ``impala_amd/libimpala_hip.so`` with
+Compiles ``impala_amd/csrc/{impala,sac,dqn_replay,ppo_replay,dqn_inplace,iqn,iqn_replay}.hip`` for gfx950 into ``impala_amd/libimpala_hip.so`` with
 hipcc (cross-compiles without a GPU).  The .so is git-ignored and travels with the tree.
 """
 from __future__ import annotations
@@ -28,10 +28,11 @@ def hip_units():
     code object; ppo_replay.hip: the PPO actor's lambda-return ingest kernel, kept out likewise;
     dqn_inplace.hip: the DQN step's three batch-reading kernels instantiated for a replay ring read in
     place, kept out likewise; iqn.hip: the kernels of the distributional (IQN) actor path and
-    training step, kept out likewise)."""
+    training step, kept out likewise; iqn_replay.hip: the two ingest kernels of the IQN learner's
+    device-side replay, kept out likewise)."""
     return [os.path.join(SRC_DIR, f)
             for f in ("impala.hip", "sac.hip", "dqn_replay.hip", "ppo_replay.hip", "dqn_inplace.hip",
-                      "iqn.hip")]
+                      "iqn.hip", "iqn_replay.hip")]
 
 
 # Per-unit flags.  impala.hip's kernels start on 1 KB boundaries of the code object (the

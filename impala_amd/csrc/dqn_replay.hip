@@ -344,4 +344,10 @@ hipError_t launch_rollout(const int64_t* act, const float* rew, const uint8_t* d
   return hipGetLastError();
 }
 
+hipError_t launch_raise_max(const float* r_prio, long long n, long long cursor, long long cap, float* maxp,
+                            hipStream_t st) {
+  replay_raise_max_kernel<<<1, 1024, 0, st>>>(r_prio, n, cursor, cap, maxp);
+  return hipGetLastError();
+}
+
 }  // namespace dqn_replay_dev

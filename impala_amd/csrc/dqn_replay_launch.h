@@ -20,5 +20,9 @@ hipError_t launch_rollout(const int64_t* act, const float* rew, const uint8_t* d
                           const float* q_star, long long K, int n_step, float gamma, long long cursor,
                           long long cap, double alpha, int64_t* r_act, float* r_tgt, float* r_prio, double* w,
                           float* maxp, int64_t* keys_out, hipStream_t st);
+// *maxp = max(*maxp, the n ring priorities at (cursor + i) % cap): what launch_extend and
+// launch_rollout end with, for an ingest kernel of another unit (csrc/iqn_replay.hip)
+hipError_t launch_raise_max(const float* r_prio, long long n, long long cursor, long long cap, float* maxp,
+                            hipStream_t st);
 
 }  // namespace dqn_replay_dev

@@ -1530,3 +1530,4 @@ int impala_ppo_loss_head(const float* logits, const float* values, const int64_t
 #include "dqn.h"
 #include "dqn_replay.h"
 #include "iqn.h"
+#include "iqn_replay.h"

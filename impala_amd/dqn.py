@@ -238,11 +238,18 @@ class DqnEngine(QEngine):
         check(getattr(lib(), entry)(self._h, C.byref(b), _lib.stream_ptr(None)), entry, _ERR)
         return prio
 
+    @staticmethod
+    def _own_replay(replay) -> None:
+        """A ``dqn_replay`` handle and no other (a ``NativeQuantileReplay``'s is an ``iqn_replay``)."""
+        if getattr(replay, "_abi", None) != "dqn_replay":
+            raise TypeError("the DQN step samples a NativePrioritizedReplay (scalar targets)")
+
     def train_step_replay(self, replay: "NativePrioritizedReplay", seed: int, counter: int):
         """Sample ``batch_size`` rows of ``replay`` keyed by (seed, counter), one learner step on
         them and the priority update, as one ``dqn_train_step_replay`` call; returns the sampled
         keys [N] i64 and the new priorities [N] (device)."""
         global REPLAY_STEP_CALLS
+        self._own_replay(replay)
         self._fresh()
         keys = torch.empty(self.N, dtype=torch.int64, device=self.device)
         prio = torch.empty(self.N, device=self.device)
@@ -258,6 +265,7 @@ class DqnEngine(QEngine):
         bit.  Until the current stream reaches the call's end, do not write ``replay``'s rows
         from another stream.  Raises ``_lib.Unsupported`` off the default kernel path."""
         global REPLAY_ROWS_STEP_CALLS
+        self._own_replay(replay)
         self._fresh()
         keys = torch.empty(self.N, dtype=torch.int64, device=self.device)
         prio = torch.empty(self.N, device=self.device)
@@ -518,6 +526,12 @@ class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
     (``dqn_train_step_replay_rows``) instead of on a gathered copy.
     """
     _destroy, _last_error = "dqn_replay_destroy", _ERR
+    _abi = "dqn_replay"  # the C-symbol prefix of the entry points shared with NativeQuantileReplay
+
+    def _call(self, entry: str, *args) -> None:
+        """``<abi>_<entry>(handle, *args)``, checked."""
+        name = f"{self._abi}_{entry}"
+        check(getattr(lib(), name)(self._h, *args), name, self._last_error)
 
     def __init__(self, capacity: int, priority_exponent: float = 0.6, device="cuda",
                  seed: Optional[int] = None, obs_shape=OBS_SHAPE, in_place: bool = False,
@@ -550,7 +564,7 @@ class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
 
     def _state(self) -> Tuple[int, int]:
         size, cursor = C.c_int64(), C.c_int64()
-        check(lib().dqn_replay_state(self._h, C.byref(size), C.byref(cursor)), "dqn_replay_state", _ERR)
+        self._call("state", C.byref(size), C.byref(cursor))
         return size.value, cursor.value
 
     def next_draw(self) -> Tuple[int, int]:
@@ -608,8 +622,7 @@ class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
     def _weights_and_max(self):
         w = torch.empty(self.capacity, dtype=torch.float64, device=self.device)
         m = torch.empty(1, dtype=torch.float32, device=self.device)
-        check(lib().dqn_replay_weights(self._h, _lib.ptr(w), _lib.ptr(m), self._stream()),
-              "dqn_replay_weights", _ERR)
+        self._call("weights", _lib.ptr(w), _lib.ptr(m), self._stream())
         return w, m
 
     def probabilities(self) -> torch.Tensor:
@@ -643,8 +656,7 @@ class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
             raise ValueError("one priority per key")
         for i in range(0, k.numel(), _lib.DQN_MAX_BATCH):  # one workgroup per call: <= 4096 keys
             kc, pc = k[i:i + _lib.DQN_MAX_BATCH], p[i:i + _lib.DQN_MAX_BATCH]
-            check(lib().dqn_replay_update(self._h, _lib.ptr(kc), _lib.ptr(pc), kc.numel(),
-                                          self._stream()), "dqn_replay_update", _ERR)
+            self._call("update", _lib.ptr(kc), _lib.ptr(pc), kc.numel(), self._stream())
 
 
 class ApexLearner(Learner):

@@ -8,8 +8,14 @@ a standalone head (``iqn_loss_head``).
 The network is the dueling DQN's trunk and heads with a quantile embedding multiplied into the
 trunk's features before the LayerNorm: W = ``n_tau_samples`` quantiles per frame, so one call on
 n frames runs the head on n W rows.  Every compute entry is one call of include/iqn_hip.h; the
-compute path is the HIP library only.  The learner samples from the torch
-``PrioritizedReplay(target_width=W)``; a native replay with ``[W]`` targets is not built.
+compute path is the HIP library only.
+
+``NativeQuantileReplay`` is the replay in the library (``iqn_replay``): ``PrioritizedReplay
+(target_width=W)``'s ring with ``dqn_replay``'s float64 sampler.  Over it the actor hands a whole
+rollout to ``extend_rollout`` (one fused ingest launch for the ``[L-1, W]`` targets, priorities and
+weights) and one learner step is one ``iqn_train_step_replay`` call: sample, gather, step and
+priority update.  Over the torch ``PrioritizedReplay(target_width=W)`` the learner samples, steps
+and updates in three parts, as before.
 """
 from __future__ import annotations
 
@@ -23,13 +29,16 @@ from impala_amd import _lib
 from impala_amd._lib import check, lib
 from impala_amd.core import Actor
 from impala_amd.dqn import (ApexActor, ApexDQNBuilder, ApexLearner, ConstantEpsFunc,
-                            FlexibleEpsFunc, PrioritizedReplay, QEngine, QModel)
+                            FlexibleEpsFunc, NativePrioritizedReplay, PrioritizedReplay, QEngine,
+                            QModel, _replay_columns)
 from impala_amd.flat import layer_init_truncated, spec_count
 from impala_amd.model import OBS_SHAPE
 
 HIDDEN = 512
 N_COS = 64  # QuantileLayer.n_cos_embedding
 _ERR = "iqn_last_error"
+# calls of iqn_train_step_replay made through IqnEngine.train_step_replay (this process)
+REPLAY_STEP_CALLS = 0
 
 
 def net_specs(num_actions: int = 15) -> List[Tuple[str, Tuple[int, ...]]]:
@@ -225,6 +234,31 @@ class IqnEngine(QEngine):
         check(getattr(lib(), entry)(self._h, C.byref(b), _lib.stream_ptr(None)), entry, _ERR)
         return prio, used
 
+    def train_step_replay(self, replay: "NativeQuantileReplay", seed: int, counter: int, taus=None,
+                          tau_seed: int = 0, tau_counter: int = 0):
+        """Sample ``batch_size`` rows of ``replay`` keyed by (seed, counter), one learner step on
+        them and the priority update, as one ``iqn_train_step_replay`` call; ``taus`` None: the
+        online net's quantiles are drawn from (tau_seed, tau_counter).  Returns the sampled keys
+        [N] i64, the new priorities [N] and the taus used [N, W] (device)."""
+        global REPLAY_STEP_CALLS
+        if not self.train:
+            raise RuntimeError("an inference engine: construct IqnEngine(train=True)")
+        if getattr(replay, "_abi", None) != "iqn_replay":
+            raise TypeError("the IQN step samples a NativeQuantileReplay ([W] targets)")
+        if replay.target_width != self.W:
+            raise ValueError("the replay's target_width must equal the model's n_tau_samples")
+        self._fresh()
+        taus = self._taus(taus, self.N)
+        keys = torch.empty(self.N, dtype=torch.int64, device=self.device)
+        prio = torch.empty(self.N, device=self.device)
+        used = torch.empty(self.N, self.W, device=self.device)
+        REPLAY_STEP_CALLS += 1
+        check(lib().iqn_train_step_replay(self._h, replay._h, int(seed), int(counter),
+                                          _lib.ptr(taus), int(tau_seed), int(tau_counter),
+                                          _lib.ptr(keys), _lib.ptr(prio), _lib.ptr(used),
+                                          _lib.stream_ptr(None)), "iqn_train_step_replay", _ERR)
+        return keys, prio, used
+
     # name -> (debug tensor id, element kind, shape of one row, rows per frame: 1 or W)
     DEBUG_TENSORS = {
         "act1": (0, "T", (15, 15, 32), False), "act2": (1, "T", (6, 6, 64), False),
@@ -313,11 +347,113 @@ class DistributionalAtariDQN(QModel):
             OBS_SHAPE, self.action_dim, self.n_tau_samples, device=device, dtype=self.compute_dtype))
 
 
+class NativeQuantileReplay(NativePrioritizedReplay):
+    """``PrioritizedReplay(target_width=W)`` on the library's ``iqn_replay`` (include/iqn_hip.h):
+    the same attributes and methods, every one through an ``iqn_replay_*`` entry point.  The
+    tensors ``s``, ``a``, ``target`` ([capacity, W]) and ``priorities`` are the bound ring arrays;
+    the float64 weights, their block sums and the running maximum priority belong to the library,
+    and sampling, ``update``, ``weights``, ``max_priority``, ``probabilities``, ``next_draw`` and
+    ``reset`` are ``NativePrioritizedReplay``'s on this handle.  ``extend_rollout`` is the
+    distributional actor's ``_make_replay`` (agents/dqn/learning.py:69-84) as one fused ingest."""
+    _destroy, _last_error, _abi = "iqn_replay_destroy", _ERR, "iqn_replay"
+    in_place = False  # (the IQN step reads a gathered batch; there is no in-place step)
+
+    def __init__(self, capacity: int, target_width: int, priority_exponent: float = 0.6,
+                 device="cuda", seed: Optional[int] = None, obs_shape=OBS_SHAPE):
+        if not 1 <= int(target_width) <= _lib.IQN_MAX_TAU:
+            raise ValueError(f"target_width must be in [1, {_lib.IQN_MAX_TAU}]")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("NativeQuantileReplay lives on the HIP path only (cuda device)")
+        if tuple(obs_shape) != OBS_SHAPE:
+            raise ValueError(f"NativeQuantileReplay stores observations of shape {OBS_SHAPE}")
+        idx = self.device_index(device)
+        self._open("iqn_replay_create", int(capacity), int(target_width), float(priority_exponent), idx)
+        PrioritizedReplay.__init__(self, capacity, priority_exponent, torch.device("cuda", idx), seed,
+                                   target_width=int(target_width))
+        # (a [capacity, 1] ring at W = 1: rows of W targets at every width)
+        self.target = self.target.reshape(self.capacity, self.target_width)
+        self._call("bind", _lib.ptr(self.s), _lib.ptr(self.a), _lib.ptr(self.target),
+                   _lib.ptr(self.priorities), self._stream())
+
+    def extend(self, items, priorities=None) -> torch.Tensor:
+        W = self.target_width
+        s, a, t = _replay_columns(items, W)
+        n = s.shape[0]
+        if n > self.capacity:
+            raise ValueError("more items than the ring holds")
+        s = s.to(self.device, torch.uint8).contiguous()
+        a = a.reshape(-1).to(self.device, torch.int64).contiguous()
+        t = t.to(self.device, torch.float32).contiguous()
+        p = None
+        if priorities is not None:
+            p = torch.as_tensor(priorities, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+            if p.numel() != n:
+                raise ValueError("one priority per item")
+        if a.numel() != n or t.numel() != n * W:
+            raise ValueError(f"s, a, target: one row per item, target [n, {W}]")
+        keys = torch.empty(n, dtype=torch.int64, device=self.device)
+        self._call("extend", _lib.ptr(s), _lib.ptr(a), _lib.ptr(t), _lib.ptr(p), n, _lib.ptr(keys),
+                   self._stream())
+        return keys
+
+    @staticmethod
+    def _rollout_shapes(W: int, s, a, r, done, q_pi, q_star) -> int:
+        """The steps L of one rollout whose fields agree (no device needed)."""
+        L = int(s.shape[0])
+        if L < 2:
+            raise ValueError("extend_rollout: a rollout needs L >= 2 steps")
+        if tuple(s.shape[1:]) != OBS_SHAPE:
+            raise ValueError(f"extend_rollout: s [L, {', '.join(map(str, OBS_SHAPE))}]")
+        if not all(x.numel() == L for x in (a, r, done, q_pi)):
+            raise ValueError("extend_rollout: every field has one entry per step")
+        if tuple(q_star.shape) != (L, W):
+            raise ValueError(f"extend_rollout: q_star [L, {W}]")
+        return L
+
+    def extend_rollout(self, s, a, r, done, q_pi, q_star, n_step: int = 3,
+                       gamma: float = 0.99) -> torch.Tensor:
+        """One actor rollout of L steps (``q_star [L, W]``) -> L - 1 transitions with their
+        per-quantile n-step targets and initial priorities, bit for bit ``iqn_nstep_targets``'
+        (``iqn_replay_extend_rollout``).  Returns the keys written."""
+        L = self._rollout_shapes(self.target_width, s, a, r, done, q_pi, q_star)
+        f32 = lambda x: x.reshape(-1).to(self.device, torch.float32).contiguous()
+        s = s.to(self.device, torch.uint8).contiguous()
+        a = a.reshape(-1).to(self.device, torch.int64).contiguous()
+        d = done.reshape(-1).to(self.device).ne(0).to(torch.uint8).contiguous()
+        r, q_pi, q_star = f32(r), f32(q_pi), f32(q_star)
+        keys = torch.empty(L - 1, dtype=torch.int64, device=self.device)
+        self._call("extend_rollout", _lib.ptr(s), _lib.ptr(a), _lib.ptr(r), _lib.ptr(d),
+                   _lib.ptr(q_pi), _lib.ptr(q_star), L, int(n_step), float(gamma), _lib.ptr(keys),
+                   self._stream())
+        return keys
+
+    def sample(self, n: int, gather: bool = True):
+        """-> (keys [n] i64, (s, a, target [n, W]), probabilities [n]); with ``gather=False`` the
+        middle element is None and only keys and probabilities are produced."""
+        if self._size == 0:
+            raise RuntimeError("sample from an empty replay")
+        n = int(n)
+        keys = torch.empty(n, dtype=torch.int64, device=self.device)
+        probs = torch.empty(n, dtype=torch.float32, device=self.device)
+        rows = None
+        if gather:
+            rows = (torch.empty((n,) + OBS_SHAPE, dtype=torch.uint8, device=self.device),
+                    torch.empty(n, dtype=torch.int64, device=self.device),
+                    torch.empty(n, self.target_width, dtype=torch.float32, device=self.device))
+        seed, counter = self.next_draw()
+        out = rows or (None, None, None)
+        self._call("sample", seed, counter, n, _lib.ptr(keys), _lib.ptr(probs), _lib.ptr(out[0]),
+                   _lib.ptr(out[1]), _lib.ptr(out[2]), self._stream())
+        return keys, rows, probs
+
+
 class ApexDistributionalActor(ApexActor):
     """``ApexDistributionalActor`` (agents/dqn/learning.py:68-84) for in-process actors: as
-    ``ApexActor``, with ``q_star`` a row of W quantiles per step; ``update`` computes the
-    per-quantile n-step targets and the initial priorities with ``iqn_nstep_targets`` and extends
-    a ``PrioritizedReplay(target_width=W)`` with ``(obs, action, target [W])`` rows."""
+    ``ApexActor``, with ``q_star`` a row of W quantiles per step.  Where the replay has
+    ``extend_rollout`` (``NativeQuantileReplay``) the whole rollout goes to it; otherwise ``update``
+    computes the per-quantile n-step targets and the initial priorities with ``iqn_nstep_targets``
+    and extends a ``PrioritizedReplay(target_width=W)`` with ``(obs, action, target [W])`` rows."""
 
     @staticmethod
     def _star(v) -> torch.Tensor:
@@ -328,6 +464,10 @@ class ApexDistributionalActor(ApexActor):
             return
         s, a, r, d, q_pi, q_star = (torch.stack(x) for x in zip(*self._trajectory))
         self._trajectory = []
+        if hasattr(self._replay_buffer, "extend_rollout"):
+            self._replay_buffer.extend_rollout(s, a.to(torch.int64), r, d, q_pi, q_star,
+                                               self._n_step, self._gamma)
+            return
         dev = self._replay_buffer.device
         targets, prio = iqn_nstep_targets(r, d, q_pi, q_star.to(dev), self._n_step, self._gamma)
         self._replay_buffer.extend((s[:-1], a[:-1].to(torch.int64), targets), prio)
@@ -347,8 +487,11 @@ class DistributionalApexLearner(ApexLearner):
     """``DistributionalApex`` (agents/dqn/learning.py:197-237) over ``ApexLearner``'s loop: sample
     from the ``PrioritizedReplay(target_width=W)``, one ``iqn_train_step`` call, the priorities
     written back at the sampled keys, target sync every ``target_sync_period`` steps; the
-    reference's metric names.  The online net's quantiles of a step are drawn by the library from
-    the model's act seed and call counter (the reference draws ``torch.rand``)."""
+    reference's metric names.  Over a ``NativeQuantileReplay`` the three are one
+    ``iqn_train_step_replay`` call, keyed by the replay's ``next_draw()`` (``last_keys`` /
+    ``last_priorities`` then hold its outputs).  The online net's quantiles of a step are drawn by
+    the library from the model's act seed and call counter (the reference draws ``torch.rand``);
+    ``last_taus`` holds them."""
 
     def __init__(self, model, replay_buffer, *args, huber_param: float = 1.0, **kwargs) -> None:
         if getattr(replay_buffer, "target_width", 1) != model.n_tau_samples:
@@ -362,6 +505,19 @@ class DistributionalApexLearner(ApexLearner):
                          betas=o.betas, max_grad_norm=self._max_grad_norm,
                          importance_sampling_exponent=self._importance_sampling_exponent,
                          huber_param=self._huber_param)
+
+    def _train_step_replay(self) -> Dict[str, torch.Tensor]:
+        e = self._engine
+        m = torch.empty(_lib.DQN_NUM_METRICS, dtype=torch.float32, device=e.device)
+        e.bind_metrics(m)
+        seed, counter = self._replay_buffer.next_draw()
+        tau_seed, tau_counter = self._model._next_draw()
+        self.last_keys, self.last_priorities, self.last_taus = e.train_step_replay(
+            self._replay_buffer, seed, counter, tau_seed=tau_seed, tau_counter=tau_counter)
+        v = m.unbind(0)
+        out = {name: v[i] for name, i in _lib.DQN_METRIC_SLOTS}
+        out["debug/priority_update_time"] = 0
+        return out
 
     def _train_step(self, keys, batch, probabilities) -> Dict[str, torch.Tensor]:  # :199-237
         e = self._engine
@@ -382,14 +538,21 @@ class ApexDistributionalBuilder(ApexDQNBuilder):
     """agents/dqn/builder.py:124-156 on the HIP library: the network, the actor and the learner."""
 
     def make_replay(self, native: bool = False, in_place: bool = False):
-        """A ``PrioritizedReplay`` whose targets are rows of ``n_tau_samples`` quantiles."""
-        if native or in_place:
-            raise NotImplementedError("the native replay holds scalar targets only (target_width 1)")
-        return PrioritizedReplay(self.cfg.agent.replay_buffer_size,
-                                 priority_exponent=float(self.cfg.agent.priority_exponent),
-                                 device=self.cfg.distributed.train_device,
-                                 seed=self.cfg.training.seed,
-                                 target_width=int(self.cfg.agent.n_tau_samples))
+        """A replay whose targets are rows of ``n_tau_samples`` quantiles: the torch
+        ``PrioritizedReplay``, or with ``native=True`` (a cuda ``train_device``) the ring on the
+        library's ``iqn_replay`` (``NativeQuantileReplay``)."""
+        if in_place:
+            raise NotImplementedError("the IQN step has no in-place step (it reads a gathered "
+                                      "batch): make_replay(native=True) without in_place")
+        kw = dict(priority_exponent=float(self.cfg.agent.priority_exponent),
+                  device=self.cfg.distributed.train_device, seed=self.cfg.training.seed,
+                  target_width=int(self.cfg.agent.n_tau_samples))
+        if native:
+            if torch.device(self.cfg.distributed.train_device).type != "cuda":
+                raise NotImplementedError("the native replay lives on the HIP path only "
+                                          "(a cuda train_device)")
+            return NativeQuantileReplay(self.cfg.agent.replay_buffer_size, **kw)
+        return PrioritizedReplay(self.cfg.agent.replay_buffer_size, **kw)
 
     def make_actor(self, model, rb=None, deterministic: bool = False):  # builder.py:140-146
         if deterministic:

@@ -17,6 +17,12 @@
  *                      online net, the importance-weighted quantile-regression loss, the backward
  *                      through heads, projection, LayerNorm, modulation, quantile layer and conv
  *                      trunk, clip_grad_norm_ and Adam; iqn_compute_grads stops before the clip
+ *   iqn_replay_*       the learner's replay (agents/dqn/builder.py:124-156 builds rlmeta's ReplayBuffer
+ *                      with a PrioritizedSampler) as a ring in HBM whose target rows are W floats
+ *                      wide: dqn_replay (dqn_hip.h) with targets [capacity][W], the same sampler
+ *   iqn_replay_extend_rollout  agents/dqn/learning.py:69-84  the actor's whole rollout in one
+ *                      pass: iqn_nstep_targets' numbers written at their ring rows
+ *   iqn_train_step_replay  sample, gather, iqn_train_step and the priority update as one call
  *
  * Network, for n frames and W = n_tau quantiles per frame (R = n W rows, row r = f W + k):
  *   x_f = AtariBody(obs_f / 255); e_r[i] = cos(pi i tau_r), i = 1..64, the argument formed in fp32
@@ -50,7 +56,7 @@
 extern "C" {
 #endif
 
-#define IQN_ABI_VERSION 2
+#define IQN_ABI_VERSION 3
 
 #define IQN_HIDDEN 512
 #define IQN_COS 64 /* cosine features of a quantile */
@@ -186,6 +192,66 @@ int iqn_apply_update(iqn_learner* h, void* stream);
  * fp32, IQN_DBG_DPRE, IQN_DBG_DX, and the trunk's IMPALA_DBG_DACT3 / IMPALA_DBG_DACT2 per frame.
  * Every other id is refused. */
 int iqn_debug_read(iqn_learner* h, int which, void* dst, size_t bytes, void* stream);
+
+/* ---- the learner's replay, device-side: dqn_replay (dqn_hip.h) with W targets per transition ----
+ *
+ * A ring of `capacity` transitions (obs u8 [3][64][64], action i64, targets f32 [W], W = n_tau)
+ * with a priority per transition, in caller-owned device arrays (iqn_replay_bind); the library
+ * owns the float64 weights, their block sums, the running maximum priority, size and cursor.
+ * Sampling, the priority update, the weights invariant and the running maximum are dqn_replay's
+ * contract word for word, computed by the same kernels: weights[i] == (double)priorities[i] **
+ * priority_exponent for every written row after every entry point below; draw j of a call is keyed
+ * by (seed, counter, j) exactly as dqn_replay_sample's.  Refused before any HIP call, in this
+ * order: bad scalars (n_tau outside [1, IQN_MAX_TAU], capacity outside [1, 2097152], a non-finite or
+ * negative exponent, n < 1, L < 2, n_step outside [1, 16], gamma outside [0, 1]), then a null
+ * pointer (named), obs / obs_out not 16-byte aligned and sample's three outputs not all or none,
+ * then a null handle; n > capacity and L - 1 > capacity need the handle and follow it. */
+typedef struct iqn_replay iqn_replay;
+
+int iqn_replay_create(int64_t capacity, int n_tau, double priority_exponent, int device,
+                      iqn_replay** out);
+int iqn_replay_destroy(iqn_replay* r);
+/* The ring's arrays: obs [capacity][3][64][64] (16-byte aligned), actions [capacity], targets
+ * [capacity][W], priorities [capacity].  Empties the ring; the running maximum restarts at 1. */
+int iqn_replay_bind(iqn_replay* r, uint8_t* obs, int64_t* actions, float* targets, float* priorities,
+                    void* stream);
+int iqn_replay_state(const iqn_replay* r, int64_t* size, int64_t* cursor);
+/* n transitions appended at the cursor, across the wrap: targets [n][W]; priorities [n], or NULL:
+ * every row takes the running maximum.  keys_out [n], optional: the ring rows written. */
+int iqn_replay_extend(iqn_replay* r, const uint8_t* obs, const int64_t* actions, const float* targets,
+                      const float* priorities, int64_t n, int64_t* keys_out, void* stream);
+/* One rollout of L steps -> L - 1 transitions appended at the cursor.  Targets [L-1][W] and
+ * priorities [L-1] are bit for bit what iqn_nstep_targets returns on the same inputs (q_pi [L],
+ * q_star [L][W]), computed and written to the ring rows (cursor + t) % capacity, with actions and
+ * weights, by one launch; the running maximum is raised afterwards. */
+int iqn_replay_extend_rollout(iqn_replay* r, const uint8_t* obs, const int64_t* actions,
+                              const float* rewards, const uint8_t* done, const float* q_pi,
+                              const float* q_star, int64_t L, int n_step, float gamma,
+                              int64_t* keys_out, void* stream);
+/* n draws with replacement: keys [n], probabilities [n]; obs_out [n][3][64][64], actions_out [n],
+ * targets_out [n][W]: the gathered rows, all three or none. */
+int iqn_replay_sample(iqn_replay* r, uint64_t seed, uint64_t counter, int64_t n, int64_t* keys,
+                      float* probabilities, uint8_t* obs_out, int64_t* actions_out, float* targets_out,
+                      void* stream);
+/* priorities[keys[j]] = priorities_in[j], n <= DQN_MAX_BATCH (4096) keys per call; duplicate keys
+ * keep the invariant (dqn_replay_update). */
+int iqn_replay_update(iqn_replay* r, const int64_t* keys, const float* priorities, int64_t n,
+                      void* stream);
+/* A copy of the float64 weights [capacity] and, optionally, of the running maximum priority. */
+int iqn_replay_weights(iqn_replay* r, double* weights_out, float* max_priority_out, void* stream);
+/* One learner step from the replay, enqueued on `stream` with no host synchronisation: batch_size
+ * draws keyed by (seed, counter), their rows gathered into a library-owned batch buffer, exactly
+ * iqn_train_step's work on that batch, then the priority update at the drawn keys -- bitwise
+ * iqn_replay_sample + iqn_train_step + iqn_replay_update.  taus [N][W], or NULL: the online net's
+ * quantiles drawn from (tau_seed, tau_counter) as iqn_batch.seed / counter do.  keys_out [N],
+ * priorities_out [N], taus_out [N][W], each optional, take the results directly.  A batch of more
+ * than DQN_MAX_BATCH keys (possible at small n_tau) is updated in chunks of DQN_MAX_BATCH, in
+ * order.  Refused before any launch: null handles, iqn_bind_state not called, iqn_replay_bind not
+ * called, a replay whose n_tau is not the learner's or on another device, an empty replay
+ * (IMPALA_E_STATE). */
+int iqn_train_step_replay(iqn_learner* h, iqn_replay* r, uint64_t seed, uint64_t counter,
+                          const float* taus, uint64_t tau_seed, uint64_t tau_counter,
+                          int64_t* keys_out, float* priorities_out, float* taus_out, void* stream);
 
 #ifdef __cplusplus
 }
