@@ -5,7 +5,10 @@ T=20), on the synthetic rollouts of SURVEY.md §8(d).
 Three CPU yardsticks, all the same oracle step:
 * ``fp64``   -- the step in float64 (oracle ``train_step_fp64``): exact arithmetic for our
   purposes, the truth every fp32 path is measured against;
-* ``native`` -- fp32 with torch's native CPU convolutions (oneDNN off);
+* ``native`` -- fp32 with torch's native CPU convolutions (im2col + GEMM: oneDNN and NNPACK
+  both off.  With oneDNN alone off, torch hands a batch of 16 or more to NNPACK, whose
+  transform kernels depend on the CPU: on some hosts they are as exact as the GEMM path, on
+  others their weight gradients are ~1e-3 rel-L2 from float64, like oneDNN's);
 * ``fp32``   -- fp32 with torch's defaults, i.e. exactly what the reference learner computes.
   At C2 its oneDNN convolution weight gradients are ~1.6e-3 rel-L2 away from float64 (its
   gradient and grad_norm inherit that; C1 is ~1.5e-6), so against it the bound is its own
@@ -64,7 +67,8 @@ _CACHE = {}
 
 def _oracle32(flat0, batch, A, native, mode):
     """fp32 oracle: 3 steps, step 1's intermediates captured."""
-    with torch.backends.mkldnn.flags(enabled=not native):
+    with torch.backends.mkldnn.flags(enabled=not native), \
+            torch.backends.nnpack.flags(enabled=not native):
         ref = ref_cpu.RefModel(A)
         ref_cpu.load_flat(ref, flat0)
         opt = ref_cpu.make_optimizer(ref)

@@ -3,7 +3,7 @@
 For C1 (B=8) and C2 (B=64), T=20, one synthetic batch: the HIP fp32 step (with the fused head's
 own V-trace exported through impala_set_debug_vtrace), the fp32 oracle (torch CPU, op for op
 as agents/impala/learning.py:140-177), the same oracle with torch's native CPU convolutions
-(oneDNN off: at C2 oneDNN's fp32 convolution weight gradients are ~1.6e-3 rel-L2 from float64)
+(oneDNN and NNPACK off: at C2 oneDNN's fp32 convolution weight gradients are ~1.6e-3 rel-L2 from float64)
 and the same oracle in float64.  Prints one JSON line per config with the achieved errors HIP-vs-fp32, HIP-vs-fp64 and fp32-vs-fp64, from which the
 tolerances in tests/test_gpu_parity_full.py are set.  Test infrastructure: uses oracle/.
 """
@@ -54,8 +54,8 @@ def probe(B, T=20, A=15, seed=1234, steps=3):
     for _ in range(steps - 1):
         ref_cpu.train_step(ref, opt, tb, collated=True)
     p32_3 = ref_cpu.flat_params(ref)
-    # fp32 with torch's native CPU convolutions (oneDNN off)
-    with torch.backends.mkldnn.flags(enabled=False):
+    # fp32 with torch's native CPU convolutions (oneDNN and NNPACK off)
+    with torch.backends.mkldnn.flags(enabled=False), torch.backends.nnpack.flags(enabled=False):
         refn = ref_cpu.make_model(0)
         optn = ref_cpu.make_optimizer(refn)
         met_n = {k: float(v) for k, v in ref_cpu.train_step(refn, optn, tb, collated=True).items()}
