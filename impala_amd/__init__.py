@@ -8,10 +8,13 @@ from impala_amd.model import AtariPPOModel, param_count, param_specs  # noqa: F4
 
 __all__ = ["AtariPPOModel", "param_count", "param_specs", "DistributionalAtariDQN",
            "ApexDistributionalActor", "ApexDistributionalBuilder", "IqnEngine",
-           "NativeQuantileReplay"]
+           "NativeQuantileReplay", "ImpalaResNetModel", "ResnetEngine"]
 
 
 def __getattr__(name):  # the IQN names, imported on first use (impala_amd.iqn imports impala_amd.dqn)
+    if name in ("ImpalaResNetModel", "ResnetEngine"):
+        from impala_amd import resnet
+        return getattr(resnet, name)
     if name in ("DistributionalAtariDQN", "ApexDistributionalActor", "ApexDistributionalBuilder",
                 "IqnEngine", "NativeQuantileReplay"):
         from impala_amd import iqn

@@ -96,6 +96,14 @@ IQN_EXPORTS = (
     "iqn_replay_extend", "iqn_replay_extend_rollout", "iqn_replay_sample", "iqn_replay_update",
     "iqn_replay_weights", "iqn_train_step_replay",
 )
+# every symbol declared in include/resnet_hip.h
+RESNET_EXPORTS = (
+    "resnet_abi_version", "resnet_last_error", "resnet_config_default", "resnet_param_count",
+    "resnet_create", "resnet_destroy", "resnet_bind_params", "resnet_refresh_weights",
+    "resnet_forward", "resnet_act", "resnet_debug_read",
+)
+RESNET_ABI_VERSION = 1
+RESNET_DBG_Y, RESNET_DBG_H, RESNET_DBG_HEADS = 15, 16, 17
 IQN_ABI_VERSION = 3
 IQN_DBG_DPRE, IQN_DBG_DX, IQN_DBG_COS = 100, 101, 102
 IQN_MAX_TAU = 32
@@ -176,6 +184,11 @@ class DqnConfig(C.Structure):
 class IqnConfig(C.Structure):
     _fields_ = [("batch_size", C.c_int), ("num_actions", C.c_int), ("n_tau", C.c_int),
                 ("dtype", C.c_int)]
+
+
+class ResnetConfig(C.Structure):
+    _fields_ = [("batch_size", C.c_int), ("num_actions", C.c_int), ("dtype", C.c_int),
+                ("debug", C.c_int)]
 
 
 class IqnOptim(C.Structure):
@@ -361,6 +374,18 @@ def _declare(lib):
     for name in IQN_EXPORTS:
         getattr(lib, name).restype = (C.c_char_p if name == "iqn_last_error" else
                                       C.c_size_t if name == "iqn_param_count" else C.c_int)
+    lib.resnet_config_default.argtypes = [C.POINTER(ResnetConfig)]
+    lib.resnet_param_count.argtypes = [C.c_int]
+    lib.resnet_create.argtypes = [C.POINTER(ResnetConfig), C.c_int, C.POINTER(_P)]
+    lib.resnet_destroy.argtypes = [_P]
+    lib.resnet_bind_params.argtypes = [_P, _P]
+    lib.resnet_refresh_weights.argtypes = [_P, _P]
+    lib.resnet_forward.argtypes = [_P, _P, C.c_int, _P, _P, _P]
+    lib.resnet_act.argtypes = [_P, _P, C.c_int, _P, C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, _P]
+    lib.resnet_debug_read.argtypes = [_P, C.c_int, _P, C.c_size_t, _P]
+    for name in RESNET_EXPORTS:
+        getattr(lib, name).restype = (C.c_char_p if name == "resnet_last_error" else
+                                      C.c_size_t if name == "resnet_param_count" else C.c_int)
     for name in DQN_EXPORTS:
         getattr(lib, name).restype = (C.c_char_p if name == "dqn_last_error" else
                                       C.c_size_t if name == "dqn_param_count" else C.c_int)

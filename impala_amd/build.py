@@ -1,6 +1,6 @@
 """Build the HIP extension in-tree: ``python -m impala_amd.build``.
 
-Compiles ``impala_amd/csrc/{impala,sac,dqn_replay,ppo_replay,dqn_inplace,iqn,iqn_replay}.hip`` for gfx950 into ``impala_amd/libimpala_hip.so`` with
+Compiles ``impala_amd/csrc/{impala,sac,dqn_replay,ppo_replay,dqn_inplace,iqn,iqn_replay,resnet}.hip`` for gfx950 into ``impala_amd/libimpala_hip.so`` with
 hipcc (cross-compiles without a GPU).  The .so is git-ignored and travels with the tree.
 """
 from __future__ import annotations
@@ -29,10 +29,11 @@ def hip_units():
     dqn_inplace.hip: the DQN step's three batch-reading kernels instantiated for a replay ring read in
     place, kept out likewise; iqn.hip: the kernels of the distributional (IQN) actor path and
     training step, kept out likewise; iqn_replay.hip: the two ingest kernels of the IQN learner's
-    device-side replay, kept out likewise)."""
+    device-side replay, kept out likewise; resnet.hip: the IMPALA ResNet actor path, kernels and
+    handle, kept out likewise)."""
     return [os.path.join(SRC_DIR, f)
             for f in ("impala.hip", "sac.hip", "dqn_replay.hip", "ppo_replay.hip", "dqn_inplace.hip",
-                      "iqn.hip", "iqn_replay.hip")]
+                      "iqn.hip", "iqn_replay.hip", "resnet.hip")]
 
 
 # Per-unit flags.  impala.hip's kernels start on 1 KB boundaries of the code object (the
@@ -43,7 +44,9 @@ def hip_units():
 _ALIGN_1K = ["-Xarch_device", "-falign-functions=1024"]
 # (ppo_replay.hip and dqn_inplace.hip hold learner-step kernels too: the PPO head and the DQN
 # step's kernels that read a ring in place)
-UNIT_FLAGS = {"impala.hip": _ALIGN_1K, "ppo_replay.hip": _ALIGN_1K, "dqn_inplace.hip": _ALIGN_1K}
+UNIT_FLAGS = {"impala.hip": _ALIGN_1K, "ppo_replay.hip": _ALIGN_1K, "dqn_inplace.hip": _ALIGN_1K,
+              # resnet.hip: no packed-fp32 VALU instructions (v_pk_{add,mul,fma}_f32)
+              "resnet.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def needs_build(out: str = OUT) -> bool:

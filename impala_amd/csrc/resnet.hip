@@ -1,0 +1,748 @@
+// The IMPALA ResNet actor-critic's actor path (include/resnet_hip.h): kernels, launchers and the
+// handle, a translation unit of its own -- the other units' code objects are the same with or
+// without it.  DESIGN.md §15 has the design and the LDS map.
+//
+// One forward of n frames is four launches:
+//   resnet_trunk_kernel  one frame per workgroup (512 threads, persistent over frames): the 15
+//                        convolutions, three max-pools, the residual adds, ReLU and LayerNorm with
+//                        every activation in LDS; y [n][2048] is its only output
+//   resnet_fc_kernel     Linear(2048, 256) split 16 (N tiles) x 8 (K chunks) over 128 workgroups,
+//                        each streaming its own 1/128 of the weights once; partial sums [8][n][256]
+//   resnet_heads_kernel  one wave per frame: the K chunks summed in order, bias, GELU, h, the heads
+//   act_heads_kernel / split_heads_kernel (kernels.h)
+//
+// Convolutions are implicit GEMMs D[oc][pixel] = sum_k W[oc][k] X[pixel][k], k = tap * Cin + ci:
+// the weights are the A operand (fragment-major in HBM, a wave's fragments in registers for the
+// whole call), the B operand is read straight from the channels-last LDS tensor, whose one-pixel
+// zero halo is the padding.  A lane's four accumulators are four consecutive output channels of
+// one pixel: one vector store to a channels-last tensor.
+#include <hip/hip_runtime.h>
+
+#include <new>
+#include <string>
+
+#include "../../include/resnet_hip.h"
+#include "adam.h"
+#include "common.h"
+#include "conv1.h"
+#include "gemm.h"
+#include "head_math.h"
+#include "host.h"
+#include "net.h"
+#include "ops.h"
+
+namespace {
+// act_heads_kernel and split_heads_kernel, this unit's own copies (what kernels.h includes is
+// included above, at global scope)
+#include "kernels.h"
+
+constexpr int RN_THREADS = 512, RN_WAVES = 8;
+constexpr int RN_FEAT = RESNET_FEATURES, RN_HID = RESNET_HIDDEN;
+constexpr int RN_CONVS = 15;
+constexpr int RN_KSPLIT = 8, RN_KCHUNK = RN_FEAT / RN_KSPLIT;  // the FC's K chunks
+// fp32 side vector (floats): conv biases [15][32], LayerNorm affine in kernel order, bfc, wh, bh
+constexpr int RV_CB = 0, RV_LNG = RN_CONVS * 32, RV_LNB = RV_LNG + RN_FEAT, RV_BFC = RV_LNB + RN_FEAT,
+              RV_WH = RV_BFC + RN_HID, RV_BH = RV_WH + HEADS * RN_HID, RV_TOTAL = RV_BH + HEADS;
+// debug tensors: elements per frame of id 0..14, and the element offset of an id's block (x frames)
+__host__ __device__ constexpr int dbg_size(int id) { return id < 5 ? 32 * 32 * 16 : id < 10 ? 16 * 16 * 32 : 8 * 8 * 32; }
+__host__ __device__ constexpr int dbg_off(int id) {
+  return id < 5 ? id * 16384 : id < 10 ? 81920 + (id - 5) * 8192 : 122880 + (id - 10) * 2048;
+}
+constexpr int RN_DBG_FRAME = 133120;
+
+// geometry of conv `id` (5 per stage: the pooled conv, then conv0, conv1 of the two blocks)
+struct ConvGeo { int cin, cout; };
+constexpr ConvGeo conv_geo(int id) { return id == 0 ? ConvGeo{3, 16} : id < 5 ? ConvGeo{16, 16} : id == 5 ? ConvGeo{16, 32} : ConvGeo{32, 32}; }
+constexpr int kernel_cin(int cin) { return cin == 3 ? 4 : cin; }  // the stem's pixels are 4 bytes
+template <typename T, int CIN> constexpr int conv_nks() { return (9 * CIN + Frag<T>::KSTEP - 1) / Frag<T>::KSTEP; }
+inline int conv_nks_rt(int cin, int kstep) { return (9 * cin + kstep - 1) / kstep; }
+
+// ---- LDS map (bytes) of one frame, T the compute type.  S1..S3: a stage's tensor with its halo.
+template <typename T> struct Lds {
+  static constexpr int S1 = 34 * 34 * 16 * (int)sizeof(T), S2 = 18 * 18 * 32 * (int)sizeof(T),
+                       S3 = 10 * 10 * 32 * (int)sizeof(T);
+  static constexpr int IMG = 66 * 66 * 4;                                  // u8 [66][66][4]
+  static constexpr int STRIP0 = 9 * 64 * 16 * 4, STRIP1 = 5 * 32 * 32 * 4, STRIP2 = 9 * 16 * 32 * 4;
+  // stem: x1 [0, S1), image, strip.  stage 1: x1, t1.  stage 2: conv reads x1, x2 at S1, strip behind
+  // it; blocks: t2 at 0.  stage 3: conv reads x2, x3 at 0, t3, strip; blocks in place.
+  static constexpr int X1 = 0, IMG_AT = S1, STRIP0_AT = S1 + IMG, T1 = S1;
+  static constexpr int X2 = S1, STRIP1_AT = S1 + S2, T2 = 0;
+  static constexpr int X3 = 0, T3 = S3, STRIP2_AT = 2 * S3;
+  static constexpr int m2(int a, int b) { return a > b ? a : b; }
+  static constexpr int RED = m2(m2(2 * S1, STRIP0_AT + STRIP0), STRIP1_AT + STRIP1);
+  static constexpr int TOTAL = RED + 64 * 4;
+  static_assert(STRIP2_AT + STRIP2 <= S1, "stage 3 lives below x2");
+  static_assert(TOTAL <= 160 * 1024, "the CU's LDS");
+  static_assert(S1 % 16 == 0 && S2 % 16 == 0 && S3 % 16 == 0 && IMG % 16 == 0, "16-byte zeroing");
+};
+
+struct TrunkArgs {
+  const uint8_t* obs;
+  int n, B;
+  const void* w[RN_CONVS];  // fragment-major weights of the compute type
+  const float* vecs;
+  void* y;    // [n][2048] compute type, kernel order p*32 + c
+  void* dbg;  // debug only
+};
+
+DEV void lds_zero(char* p, int bytes) {
+  for (int i = threadIdx.x * 16; i < bytes; i += RN_THREADS * 16) *reinterpret_cast<i32x4*>(p + i) = i32x4{0, 0, 0, 0};
+}
+
+DEV f32x4 relu_v(f32x4 v) { return __builtin_elementwise_max(v, f32x4{0.f, 0.f, 0.f, 0.f}); }
+// bf16: a negative value is a negative int16; max with 0 as integers (no NaN in an activation)
+DEV bf16x8 relu_v(bf16x8 v) {
+  typedef short s16x8 __attribute__((ext_vector_type(8)));
+  const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  return __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, v), z));
+}
+
+// element offset, from a pixel's top-left tap, of the lane's slice of K-step s: k0 = s KSTEP + grp KPL
+// lies in tap k0 / CIN at channel k0 % CIN; a tap past the ninth (K padded up to a whole K-step,
+// where the packed weights are zero) reads the ninth again: any finite value
+template <typename T, int CIN, int PITCH> DEV int tap_off(int s, int grp) {
+  const int k0 = s * Frag<T>::KSTEP + grp * Frag<T>::KPL;
+  const int tap = min(k0 / CIN, 8), ci = k0 % CIN;
+  return ((tap / 3) * PITCH + tap % 3) * CIN + ci;
+}
+
+// The tiles of ROWS conv rows (H wide, 16 pixels a tile) over the waves, two tiles in flight per wave
+// so that MFMA e of one never waits on MFMA e - 1 of the same accumulator.  With two N tiles the
+// even waves take output channels 0..15 and the odd ones 16..31.  ld(pixel base, s) returns the B
+// fragment of K-step s; epi(y, x, c0, acc) takes channels c0..c0+3 of pixel (y, x).
+template <typename T, int NKS, int COUT, int H, int ROWS, class Ld, class Epi>
+DEV void conv_tiles(const T* __restrict__ wpk, int y0, Ld ld, Epi epi) {
+  using F = Frag<T>;
+  typedef typename F::vec V;
+  constexpr int NTL = COUT / 16, WSL = RN_WAVES / NTL, NTILES = ROWS * H / 16;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col = lane & 15, grp = lane >> 4;
+  const int nt = NTL == 2 ? (wave & 1) : 0, slot = NTL == 2 ? (wave >> 1) : wave;
+  V wf[NKS];
+#pragma unroll
+  for (int s = 0; s < NKS; ++s) wf[s] = F::load(wpk + ((size_t)(nt * NKS + s) * 64 + lane) * F::KPL);
+  const int c0 = 16 * nt + 4 * grp;
+  for (int t = slot; t < NTILES; t += 2 * WSL) {
+    const bool two = t + WSL < NTILES;  // (uniform)
+    const int pa = 16 * t + col, pb = 16 * (two ? t + WSL : t) + col;
+    const int ya = y0 + pa / H, xa = pa % H, yb = y0 + pb / H, xb = pb % H;
+    f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0;
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) {
+      const V v0 = ld(ya, xa, s), v1 = ld(yb, xb, s);
+#pragma unroll
+      for (int e = 0; e < F::NE; ++e) {
+        a0 = F::mma_e(e, wf[s], v0, a0);
+        a1 = F::mma_e(e, wf[s], v1, a1);
+      }
+    }
+    epi(ya, xa, c0, a0);
+    if (two) epi(yb, xb, c0, a1);
+  }
+}
+
+// a 3x3 pad-1 convolution of the halo tensor `in` [H+2][H+2][CIN] (ReLU on the operand read if RELU)
+template <typename T, int CIN, int COUT, int H, int ROWS, bool RELU, class Epi>
+DEV void conv_lds(const T* __restrict__ in, const T* __restrict__ wpk, int y0, Epi epi) {
+  using F = Frag<T>;
+  typedef typename F::vec V;
+  constexpr int NKS = conv_nks<T, CIN>(), P = H + 2;
+  const int grp = (threadIdx.x & 63) >> 4;
+  int off[NKS];
+#pragma unroll
+  for (int s = 0; s < NKS; ++s) off[s] = tap_off<T, CIN, P>(s, grp);
+  conv_tiles<T, NKS, COUT, H, ROWS>(
+      wpk, y0,
+      [&](int y, int x, int s) {
+        const V v = *reinterpret_cast<const V*>(in + (y * P + x) * CIN + off[s]);
+        return RELU ? relu_v(v) : v;
+      },
+      epi);
+}
+
+// the stem's operand: image pixels as dwords (c0, c1, c2, 0) [66][66], the bytes converted on the
+// read (exact in both types); k = tap * 4 + c
+DEV f32x4 stem_frag(const uint32_t* __restrict__ px, const int (&o)[2], float) {
+  const uint32_t d = px[o[0]];
+  return f32x4{(float)(d & 255u), (float)((d >> 8) & 255u), (float)((d >> 16) & 255u), 0.f};
+}
+DEV bf16x8 stem_frag(const uint32_t* __restrict__ px, const int (&o)[2], __bf16) {
+  const uint32_t d = px[o[0]], e = px[o[1]];
+  bf16x8 v;
+  v[0] = (__bf16)(float)(d & 255u); v[1] = (__bf16)(float)((d >> 8) & 255u);
+  v[2] = (__bf16)(float)((d >> 16) & 255u); v[3] = (__bf16)0.f;
+  v[4] = (__bf16)(float)(e & 255u); v[5] = (__bf16)(float)((e >> 8) & 255u);
+  v[6] = (__bf16)(float)((e >> 16) & 255u); v[7] = (__bf16)0.f;
+  return v;
+}
+template <typename T, int ROWS, class Epi>
+DEV void conv_stem(const uint32_t* __restrict__ img, const T* __restrict__ wpk, int y0, Epi epi) {
+  using F = Frag<T>;
+  constexpr int NKS = conv_nks<T, 4>(), P = 66, TPL = F::KPL / 4;  // taps per lane and K-step
+  const int grp = (threadIdx.x & 63) >> 4;
+  int off[NKS][2];
+#pragma unroll
+  for (int s = 0; s < NKS; ++s)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int tap = min((s * 4 + grp) * TPL + (j < TPL ? j : 0), 8);
+      off[s][j] = (tap / 3) * P + tap % 3;
+    }
+  conv_tiles<T, NKS, 16, 64, ROWS>(
+      wpk, y0, [&](int y, int x, int s) { return stem_frag(img + y * P + x, off[s], T{}); }, epi);
+}
+
+// ---- epilogues.  c0 is fixed per lane within a call: the bias is loaded once.
+// conv row y of a pooled conv -> the fp32 strip ring [RING][W][C]: acc * scale + b
+template <int W, int C, int RING> struct EpiStrip {
+  float* strip;
+  const float* bias;
+  float scale;
+  DEV void operator()(int y, int x, int c0, f32x4 acc) const {
+    const f32x4 b = *reinterpret_cast<const f32x4*>(bias + c0);
+    *reinterpret_cast<f32x4*>(strip + ((y % RING) * W + x) * C + c0) = acc * scale + b;
+  }
+};
+// t = T(acc + b) into the interior of a halo tensor
+template <typename T, int H, int C> struct EpiStore {
+  T* out;
+  const float* bias;
+  DEV void operator()(int y, int x, int c0, f32x4 acc) const {
+    const f32x4 b = *reinterpret_cast<const f32x4*>(bias + c0);
+    const float o[4] = {acc[0] + b[0], acc[1] + b[1], acc[2] + b[2], acc[3] + b[3]};
+    store4(out + ((y + 1) * (H + 2) + x + 1) * C + c0, o);
+  }
+};
+// x = T(fp32(x) + (acc + b)), in place (the convolution reads t only)
+template <typename T, int H, int C> struct EpiResidual {
+  T* x;
+  const float* bias;
+  DEV void operator()(int y, int xx, int c0, f32x4 acc) const {
+    const f32x4 b = *reinterpret_cast<const f32x4*>(bias + c0);
+    T* p = x + ((y + 1) * (H + 2) + xx + 1) * C + c0;
+    float v[4];
+    load4(p, v);
+    const float o[4] = {v[0] + (acc[0] + b[0]), v[1] + (acc[1] + b[1]), v[2] + (acc[2] + b[2]),
+                        v[3] + (acc[3] + b[3])};
+    store4(p, o);
+  }
+};
+
+// max_pool2d(kernel 3, stride 2, padding 1) of conv rows r0 .. r0 + SR - 1 (and row r0 - 1, still in
+// the ring) -> output rows r0/2 .. r0/2 + SR/2 - 1 in the interior of `out`; a tap outside the
+// image is left out (-inf padding).  The max is taken in fp32 and rounded once: rounding is monotone.
+template <typename T, int HC, int C, int SR>
+DEV void pool_rows(const float* __restrict__ strip, T* __restrict__ out, int r0) {
+  constexpr int HO = HC / 2, RING = SR + 1, CV = C / 4, ITEMS = (SR / 2) * HO * CV;
+  for (int i = threadIdx.x; i < ITEMS; i += RN_THREADS) {
+    const int c0 = 4 * (i % CV), ox = (i / CV) % HO, oy = r0 / 2 + i / (CV * HO);
+    f32x4 m = *reinterpret_cast<const f32x4*>(strip + (((2 * oy) % RING) * HC + 2 * ox) * C + c0);
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int r = 2 * oy + dy, cx = 2 * ox + dx;  // (never past HC - 1)
+        if ((dy || dx) && r >= 0 && cx >= 0)
+          m = __builtin_elementwise_max(m, *reinterpret_cast<const f32x4*>(strip + ((r % RING) * HC + cx) * C + c0));
+      }
+    const float o[4] = {m[0], m[1], m[2], m[3]};
+    store4(out + ((oy + 1) * (HO + 2) + ox + 1) * C + c0, o);
+  }
+}
+
+// debug: the interior of a halo tensor -> HBM [H][H][C]
+template <typename T, int H, int C> DEV void dump(const T* __restrict__ t, T* __restrict__ dst) {
+  for (int i = threadIdx.x; i < H * H * C / 4; i += RN_THREADS) {
+    const int c0 = 4 * (i % (C / 4)), p = i / (C / 4);
+    float v[4];
+    load4(t + ((p / H + 1) * (H + 2) + p % H + 1) * C + c0, v);
+    store4(dst + p * C + c0, v);
+  }
+}
+
+// the two residual blocks of a stage on x (halo tensor) with scratch t; ends on a barrier
+template <typename T, bool DEBUG, int C, int H>
+DEV void res_blocks(T* x, T* t, const TrunkArgs& a, int id0, int f) {
+#pragma unroll
+  for (int blk = 0; blk < 2; ++blk) {
+    const int i0 = id0 + 2 * blk, i1 = i0 + 1;
+    conv_lds<T, C, C, H, H, true>(x, reinterpret_cast<const T*>(a.w[i0]), 0,
+                                  EpiStore<T, H, C>{t, a.vecs + RV_CB + 32 * i0});
+    __syncthreads();
+    if constexpr (DEBUG)
+      dump<T, H, C>(t, reinterpret_cast<T*>(a.dbg) + (size_t)a.B * dbg_off(i0) + (size_t)f * dbg_size(i0));
+    conv_lds<T, C, C, H, H, true>(t, reinterpret_cast<const T*>(a.w[i1]), 0,
+                                  EpiResidual<T, H, C>{x, a.vecs + RV_CB + 32 * i1});
+    __syncthreads();
+    if constexpr (DEBUG)
+      dump<T, H, C>(x, reinterpret_cast<T*>(a.dbg) + (size_t)a.B * dbg_off(i1) + (size_t)f * dbg_size(i1));
+  }
+}
+
+template <typename T, bool DEBUG>
+__global__ __launch_bounds__(RN_THREADS) void resnet_trunk_kernel(const TrunkArgs a) {
+  using L = Lds<T>;
+  __shared__ __attribute__((aligned(16))) char lds[L::TOTAL];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  T* const dbg = reinterpret_cast<T*>(a.dbg);
+  float* const red = reinterpret_cast<float*>(lds + L::RED);
+  for (int f = blockIdx.x; f < a.n; f += gridDim.x) {
+    auto dbg_at = [&](int id) { return dbg + (size_t)a.B * dbg_off(id) + (size_t)f * dbg_size(id); };
+    // ---- the image: bytes of three planes -> pixels (c0, c1, c2, 0) inside a zero border
+    T* x1 = reinterpret_cast<T*>(lds + L::X1);
+    uint32_t* img = reinterpret_cast<uint32_t*>(lds + L::IMG_AT);
+    lds_zero(lds + L::X1, L::S1);
+    lds_zero(lds + L::IMG_AT, L::IMG);
+    __syncthreads();
+    if (tid < 256) {
+      const int yy = tid >> 2, x0 = (tid & 3) * 16;
+      const uint8_t* src = a.obs + (size_t)f * 12288 + yy * 64 + x0;
+      const i32x4 p0 = *reinterpret_cast<const i32x4*>(src), p1 = *reinterpret_cast<const i32x4*>(src + 4096),
+                  p2 = *reinterpret_cast<const i32x4*>(src + 8192);
+      uint32_t* dst = img + (yy + 1) * 66 + x0 + 1;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int sh = 8 * (j & 3);
+        dst[j] = (((uint32_t)p0[j >> 2] >> sh) & 255u) | ((((uint32_t)p1[j >> 2] >> sh) & 255u) << 8) |
+                 ((((uint32_t)p2[j >> 2] >> sh) & 255u) << 16);
+      }
+    }
+    __syncthreads();
+    {  // ---- stem: conv 3 -> 16 at 64 x 64 in strips of 8 rows, pooled to x1 [32][32][16]
+      float* strip = reinterpret_cast<float*>(lds + L::STRIP0_AT);
+      for (int r0 = 0; r0 < 64; r0 += 8) {
+        conv_stem<T, 8>(img, reinterpret_cast<const T*>(a.w[0]), r0,
+                        EpiStrip<64, 16, 9>{strip, a.vecs + RV_CB, 1.f / 255.f});
+        __syncthreads();
+        pool_rows<T, 64, 16, 8>(strip, x1, r0);
+        __syncthreads();
+      }
+    }
+    if constexpr (DEBUG) dump<T, 32, 16>(x1, dbg_at(0));
+    T* t1 = reinterpret_cast<T*>(lds + L::T1);
+    lds_zero(lds + L::T1, L::S1);
+    __syncthreads();
+    res_blocks<T, DEBUG, 16, 32>(x1, t1, a, 1, f);
+    // ---- stage 2: conv 16 -> 32 at 32 x 32 in strips of 4 rows, pooled to x2 [16][16][32]
+    T* x2 = reinterpret_cast<T*>(lds + L::X2);
+    lds_zero(lds + L::X2, L::S2);
+    __syncthreads();
+    {
+      float* strip = reinterpret_cast<float*>(lds + L::STRIP1_AT);
+      for (int r0 = 0; r0 < 32; r0 += 4) {
+        conv_lds<T, 16, 32, 32, 4, false>(x1, reinterpret_cast<const T*>(a.w[5]), r0,
+                                          EpiStrip<32, 32, 5>{strip, a.vecs + RV_CB + 32 * 5, 1.f});
+        __syncthreads();
+        pool_rows<T, 32, 32, 4>(strip, x2, r0);
+        __syncthreads();
+      }
+    }
+    if constexpr (DEBUG) dump<T, 16, 32>(x2, dbg_at(5));
+    T* t2 = reinterpret_cast<T*>(lds + L::T2);
+    lds_zero(lds + L::T2, L::S2);
+    __syncthreads();
+    res_blocks<T, DEBUG, 32, 16>(x2, t2, a, 6, f);
+    // ---- stage 3: conv 32 -> 32 at 16 x 16 in strips of 8 rows, pooled to x3 [8][8][32]
+    T* x3 = reinterpret_cast<T*>(lds + L::X3);
+    T* t3 = reinterpret_cast<T*>(lds + L::T3);
+    lds_zero(lds + L::X3, 2 * L::S3);
+    __syncthreads();
+    {
+      float* strip = reinterpret_cast<float*>(lds + L::STRIP2_AT);
+      for (int r0 = 0; r0 < 16; r0 += 8) {
+        conv_lds<T, 32, 32, 16, 8, false>(x2, reinterpret_cast<const T*>(a.w[10]), r0,
+                                          EpiStrip<16, 32, 9>{strip, a.vecs + RV_CB + 32 * 10, 1.f});
+        __syncthreads();
+        pool_rows<T, 16, 32, 8>(strip, x3, r0);
+        __syncthreads();
+      }
+    }
+    if constexpr (DEBUG) dump<T, 8, 32>(x3, dbg_at(10));
+    res_blocks<T, DEBUG, 32, 8>(x3, t3, a, 11, f);
+    // ---- ReLU, LayerNorm over the 2048 features: thread -> pixel tid / 8, channels 4 (tid % 8) ..;
+    // two-pass statistics, lanes by DPP / permlane in a fixed order, the 8 waves in order
+    {
+      const int p = tid >> 3, c0 = 4 * (tid & 7);
+      float v[4];
+      load4(x3 + (((p >> 3) + 1) * 10 + (p & 7) + 1) * 32 + c0, v);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.f);
+      const float s = wave_sum((v[0] + v[1]) + (v[2] + v[3]));
+      if (lane == 0) red[wave] = s;
+      __syncthreads();
+      const float mean = (((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]))) *
+                         (1.f / RN_FEAT);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] -= mean;
+      const float sq = wave_sum((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
+      if (lane == 0) red[8 + wave] = sq;
+      __syncthreads();
+      const float var = (((red[8] + red[9]) + (red[10] + red[11])) + ((red[12] + red[13]) + (red[14] + red[15]))) *
+                        (1.f / RN_FEAT);
+      const float rstd = 1.f / sqrtf(var + LN_EPS);
+      float g[4], b[4], o[4];
+      load4(a.vecs + RV_LNG + p * 32 + c0, g);
+      load4(a.vecs + RV_LNB + p * 32 + c0, b);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) o[q] = v[q] * rstd * g[q] + b[q];
+      store4(reinterpret_cast<T*>(a.y) + (size_t)f * RN_FEAT + p * 32 + c0, o);
+    }
+    __syncthreads();  // x3 and red are rewritten by the next frame
+  }
+}
+
+// Linear(2048, 256) without bias, as partial sums: workgroup (nt, ks) holds the 16 x 256 slab of
+// Wfc (rows 16 nt .., K chunk ks) as A fragments in registers -- every wave the same slab, read from
+// HBM once -- and wave w runs the 16-frame tiles w, w + 4, .. of y against it.  part [8][B][256].
+template <typename T>
+__global__ __launch_bounds__(256) void resnet_fc_kernel(const T* __restrict__ y, const T* __restrict__ wpk,
+                                                        float* __restrict__ part, int n, int B) {
+  using F = Frag<T>;
+  typedef typename F::vec V;
+  constexpr int NKS = RN_KCHUNK / F::KSTEP;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, grp = lane >> 4;
+  const int nt = blockIdx.x & 15, ks = blockIdx.x >> 4;
+  V wf[NKS];
+#pragma unroll
+  for (int s = 0; s < NKS; ++s)
+    wf[s] = F::load(wpk + ((size_t)((nt * RN_KSPLIT + ks) * NKS + s) * 64 + lane) * F::KPL);
+  for (int r0 = wave * 16; r0 < n; r0 += 64) {
+    const int fr = min(r0 + col, n - 1);
+    const T* yr = y + (size_t)fr * RN_FEAT + ks * RN_KCHUNK + grp * F::KPL;
+    f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int s = 0; s < NKS; s += 2) {
+      const V v0 = F::load(yr + s * F::KSTEP), v1 = F::load(yr + (s + 1) * F::KSTEP);
+#pragma unroll
+      for (int e = 0; e < F::NE; ++e) {
+        acc[0] = F::mma_e(e, wf[s], v0, acc[0]);
+        acc[1] = F::mma_e(e, wf[s + 1], v1, acc[1]);
+      }
+    }
+    if (r0 + col < n)
+      *reinterpret_cast<f32x4*>(part + ((size_t)ks * B + fr) * RN_HID + nt * 16 + 4 * grp) = acc[0] + acc[1];
+  }
+}
+
+// One wave per frame: z = (sum of the 8 K chunks, in order) + bfc, h = T(GELU(z)), heads = Wh h + bh
+// in fp32 -- a lane four of the 256 terms per head, the lanes summed in wave_sum's fixed order.
+template <typename T>
+__global__ __launch_bounds__(256) void resnet_heads_kernel(const float* __restrict__ part, const float* __restrict__ vecs,
+                                                           T* __restrict__ h, float* __restrict__ heads, int n, int B) {
+  const int lane = threadIdx.x & 63, f = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (f >= n) return;
+  float acc[HEADS];
+#pragma unroll
+  for (int o = 0; o < HEADS; ++o) acc[o] = 0.f;
+#pragma unroll
+  for (int i = 0; i < RN_HID / 64; ++i) {
+    const int j = lane + 64 * i;
+    float z = part[(size_t)f * RN_HID + j];
+#pragma unroll
+    for (int ks = 1; ks < RN_KSPLIT; ++ks) z += part[((size_t)ks * B + f) * RN_HID + j];
+    z += vecs[RV_BFC + j];
+    const T ht = (T)(0.5f * z * (1.f + erff(z * 0.70710678118654752440f)));
+    h[(size_t)f * RN_HID + j] = ht;
+    const float hf = (float)ht;
+#pragma unroll
+    for (int o = 0; o < HEADS; ++o) acc[o] = fmaf(vecs[RV_WH + o * RN_HID + j], hf, acc[o]);
+  }
+  float mine = 0.f;
+#pragma unroll
+  for (int o = 0; o < HEADS; ++o) {
+    const float s = wave_sum(acc[o]);
+    mine = lane == o ? s : mine;
+  }
+  if (lane < HEADS) heads[(size_t)f * HEADS + lane] = mine + vecs[RV_BH + lane];
+}
+
+// ---- packing (resnet_refresh_weights).  A conv's canonical [COUT][cin][3][3] -> fragment-major
+// [nt][s][lane][j]: row oc = 16 nt + (lane & 15), k = s KSTEP + (lane >> 4) KPL + j = tap * CK + ci
+// (CK the kernel's channel count: 4 for the stem); zero where tap > 8 or ci >= cin.
+template <typename T>
+__global__ __launch_bounds__(256) void resnet_pack_conv_kernel(const float* __restrict__ w, T* __restrict__ dst,
+                                                               int cin, int ck, int nks, int total) {
+  using F = Frag<T>;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int j = e % F::KPL, lane = (e / F::KPL) & 63, s = (e / (F::KPL * 64)) % nks, nt = e / (F::KPL * 64 * nks);
+  const int oc = 16 * nt + (lane & 15), k = s * F::KSTEP + (lane >> 4) * F::KPL + j;
+  const int tap = k / ck, ci = k % ck;
+  dst[e] = (T)(tap < 9 && ci < cin ? w[((size_t)oc * cin + ci) * 9 + tap] : 0.f);
+}
+// Wfc canonical [256][2048] (column c*64 + p) -> [nt][ks][s][lane][j], k' = p*32 + c
+template <typename T>
+__global__ __launch_bounds__(256) void resnet_pack_fc_kernel(const float* __restrict__ w, T* __restrict__ dst) {
+  using F = Frag<T>;
+  constexpr int NKS = RN_KCHUNK / F::KSTEP;
+  const int e = blockIdx.x * 256 + threadIdx.x;  // < 256 * 2048
+  const int j = e % F::KPL, lane = (e / F::KPL) & 63, s = (e / (F::KPL * 64)) % NKS;
+  const int ks = (e / (F::KPL * 64 * NKS)) % RN_KSPLIT, nt = e / (F::KPL * 64 * NKS * RN_KSPLIT);
+  const int o = 16 * nt + (lane & 15), k = ks * RN_KCHUNK + s * F::KSTEP + (lane >> 4) * F::KPL + j;
+  dst[e] = (T)w[(size_t)o * RN_FEAT + (k & 31) * 64 + (k >> 5)];
+}
+struct VecSrc {
+  int cb[RN_CONVS];  // offsets in the flat buffer
+  int lng, lnb, bfc, wa, ba, wc, bc;
+};
+__global__ __launch_bounds__(256) void resnet_pack_vec_kernel(const float* __restrict__ flat, const VecSrc o, int A,
+                                                              float* __restrict__ vecs) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= RV_TOTAL) return;
+  float v = 0.f;
+  if (i < RV_LNG) {
+    const int id = i >> 5, c = i & 31;
+    v = c < conv_geo(id).cout ? flat[o.cb[id] + c] : 0.f;
+  } else if (i < RV_BFC) {  // kernel order p*32 + c <- canonical c*64 + p
+    const int k = (i - RV_LNG) & (RN_FEAT - 1);
+    v = flat[(i < RV_LNB ? o.lng : o.lnb) + (k & 31) * 64 + (k >> 5)];
+  } else if (i < RV_WH) {
+    v = flat[o.bfc + i - RV_BFC];
+  } else if (i < RV_BH) {
+    const int r = (i - RV_WH) / RN_HID, j = (i - RV_WH) % RN_HID;
+    v = r < A ? flat[o.wa + r * RN_HID + j] : r == VCOL ? flat[o.wc + j] : 0.f;
+  } else {
+    const int r = i - RV_BH;
+    v = r < A ? flat[o.ba + r] : r == VCOL ? flat[o.bc] : 0.f;
+  }
+  vecs[i] = v;
+}
+
+size_t body_offsets(int (&w)[RN_CONVS], int (&b)[RN_CONVS]) {
+  size_t o = 0;
+  for (int id = 0; id < RN_CONVS; ++id) {
+    const ConvGeo g = conv_geo(id);
+    w[id] = (int)o; o += (size_t)g.cout * g.cin * 9;
+    b[id] = (int)o; o += g.cout;
+  }
+  return o;
+}
+
+}  // namespace
+
+struct resnet_actor {
+  resnet_config cfg;
+  int device, n_cu;
+  const float* flat = nullptr;
+  bool packed = false;
+  char* ws = nullptr;  // one allocation: everything below
+  void* w[RN_CONVS];
+  void* wfc;
+  float* vecs;
+  void* y;
+  float* part;
+  void* h;
+  float* heads;
+  void* dbg;
+};
+
+namespace {
+
+size_t elt(const resnet_actor* h) { return h->cfg.dtype == IMPALA_DTYPE_BF16 ? 2 : 4; }
+
+int check_ready(resnet_actor* h, const uint8_t* obs, int n) {
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  if (!obs) return fail(IMPALA_E_INVALID, "null pointer");
+  if (n < 1 || n > h->cfg.batch_size) return fail(IMPALA_E_INVALID, "n must be in [1, batch_size]");
+  if (((uintptr_t)obs & 15) != 0) return fail(IMPALA_E_INVALID, "obs must be 16-byte aligned");
+  if (!h->flat) return fail(IMPALA_E_STATE, "resnet_bind_params not called");
+  if (!h->packed) return fail(IMPALA_E_STATE, "resnet_refresh_weights not called since resnet_bind_params");
+  return 0;
+}
+
+template <typename T> int launch_pack(resnet_actor* h, hipStream_t st) {
+  int wo[RN_CONVS], bo[RN_CONVS];
+  size_t o = body_offsets(wo, bo);
+  VecSrc vs;
+  for (int id = 0; id < RN_CONVS; ++id) vs.cb[id] = bo[id];
+  const int A = h->cfg.num_actions;
+  vs.lng = (int)o; o += RN_FEAT;
+  vs.lnb = (int)o; o += RN_FEAT;
+  const size_t wfc = o; o += (size_t)RN_HID * RN_FEAT;
+  vs.bfc = (int)o; o += RN_HID;
+  vs.wa = (int)o; o += (size_t)A * RN_HID;
+  vs.ba = (int)o; o += A;
+  vs.wc = (int)o; o += RN_HID;
+  vs.bc = (int)o;
+  for (int id = 0; id < RN_CONVS; ++id) {
+    const ConvGeo g = conv_geo(id);
+    const int ck = kernel_cin(g.cin), nks = conv_nks_rt(ck, Frag<T>::KSTEP);
+    const int total = g.cout * nks * Frag<T>::KSTEP;
+    resnet_pack_conv_kernel<T><<<cdiv(total, 256), 256, 0, st>>>(h->flat + wo[id], (T*)h->w[id], g.cin, ck, nks, total);
+    CK_LAUNCH("resnet_pack_conv");
+  }
+  resnet_pack_fc_kernel<T><<<RN_HID * RN_FEAT / 256, 256, 0, st>>>(h->flat + wfc, (T*)h->wfc);
+  CK_LAUNCH("resnet_pack_fc");
+  resnet_pack_vec_kernel<<<cdiv(RV_TOTAL, 256), 256, 0, st>>>(h->flat, vs, A, h->vecs);
+  CK_LAUNCH("resnet_pack_vec");
+  return 0;
+}
+
+template <typename T> int launch_forward(resnet_actor* h, const uint8_t* obs, int n, hipStream_t st) {
+  TrunkArgs a;
+  a.obs = obs;
+  a.n = n;
+  a.B = h->cfg.batch_size;
+  for (int id = 0; id < RN_CONVS; ++id) a.w[id] = h->w[id];
+  a.vecs = h->vecs;
+  a.y = h->y;
+  a.dbg = h->dbg;
+  const int grid = n < h->n_cu ? n : h->n_cu;
+  if (h->cfg.debug) resnet_trunk_kernel<T, true><<<grid, RN_THREADS, 0, st>>>(a);
+  else resnet_trunk_kernel<T, false><<<grid, RN_THREADS, 0, st>>>(a);
+  CK_LAUNCH("resnet_trunk");
+  resnet_fc_kernel<T><<<16 * RN_KSPLIT, 256, 0, st>>>((const T*)h->y, (const T*)h->wfc, h->part, n, a.B);
+  CK_LAUNCH("resnet_fc");
+  resnet_heads_kernel<T><<<cdiv(n, 4), 256, 0, st>>>(h->part, h->vecs, (T*)h->h, h->heads, n, a.B);
+  CK_LAUNCH("resnet_heads");
+  return 0;
+}
+
+#define RN_BY_TYPE(h, fn, ...) \
+  ((h)->cfg.dtype == IMPALA_DTYPE_BF16 ? fn<__bf16>(__VA_ARGS__) : fn<float>(__VA_ARGS__))
+
+}  // namespace
+
+extern "C" {
+
+int resnet_abi_version(void) { return RESNET_ABI_VERSION; }
+const char* resnet_last_error(void) { return impala_last_error(); }
+
+int resnet_config_default(resnet_config* cfg) {
+  if (!cfg) return fail(IMPALA_E_INVALID, "null config");
+  *cfg = resnet_config{128, RESNET_MAX_ACTIONS, IMPALA_DTYPE_F32, 0};
+  return 0;
+}
+
+size_t resnet_param_count(int A) {
+  return (size_t)RESNET_BODY_PARAMS + 2 * RN_FEAT + (size_t)RN_HID * RN_FEAT + RN_HID + (size_t)A * RN_HID + A +
+         RN_HID + 1;
+}
+
+int resnet_create(const resnet_config* cfg, int device, resnet_actor** out) {
+  if (!cfg || !out) return fail(IMPALA_E_INVALID, "null pointer");
+  if (cfg->batch_size < 1) return fail(IMPALA_E_INVALID, "batch_size must be >= 1");
+  if (cfg->num_actions < 1 || cfg->num_actions > RESNET_MAX_ACTIONS)
+    return fail(IMPALA_E_INVALID, "num_actions must be in [1, 15]");
+  if (cfg->dtype != IMPALA_DTYPE_F32 && cfg->dtype != IMPALA_DTYPE_BF16) return fail(IMPALA_E_INVALID, "unknown dtype");
+  if (cfg->debug != 0 && cfg->debug != 1) return fail(IMPALA_E_INVALID, "debug must be 0 or 1");
+  CK(hipSetDevice(device));
+  int cu = 0;
+  CK(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device));
+  resnet_actor* h = new (std::nothrow) resnet_actor();
+  if (!h) return fail(IMPALA_E_INVALID, "out of host memory");
+  h->cfg = *cfg;
+  h->device = device;
+  h->n_cu = cu > 0 ? cu : 1;
+  const size_t es = elt(h), B = (size_t)cfg->batch_size;
+  const int kstep = es == 2 ? 32 : 16;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  size_t off = 0, wo[RN_CONVS];
+  for (int id = 0; id < RN_CONVS; ++id) {
+    const ConvGeo g = conv_geo(id);
+    wo[id] = off;
+    off = al(off + (size_t)g.cout * conv_nks_rt(kernel_cin(g.cin), kstep) * kstep * es);
+  }
+  const size_t o_wfc = off; off = al(off + (size_t)RN_HID * RN_FEAT * es);
+  const size_t o_vecs = off; off = al(off + (size_t)RV_TOTAL * 4);
+  const size_t o_y = off; off = al(off + B * RN_FEAT * es);
+  const size_t o_part = off; off = al(off + (size_t)RN_KSPLIT * B * RN_HID * 4);
+  const size_t o_h = off; off = al(off + B * RN_HID * es);
+  const size_t o_heads = off; off = al(off + B * HEADS * 4);
+  const size_t o_dbg = off;
+  if (cfg->debug) off = al(off + B * RN_DBG_FRAME * es);
+  const hipError_t e = hipMalloc((void**)&h->ws, off);
+  if (e != hipSuccess) {
+    delete h;
+    return fail((int)e, std::string("hipMalloc: ") + hipGetErrorString(e));
+  }
+  for (int id = 0; id < RN_CONVS; ++id) h->w[id] = h->ws + wo[id];
+  h->wfc = h->ws + o_wfc;
+  h->vecs = (float*)(h->ws + o_vecs);
+  h->y = h->ws + o_y;
+  h->part = (float*)(h->ws + o_part);
+  h->h = h->ws + o_h;
+  h->heads = (float*)(h->ws + o_heads);
+  h->dbg = cfg->debug ? h->ws + o_dbg : nullptr;
+  *out = h;
+  return 0;
+}
+
+int resnet_destroy(resnet_actor* h) {
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  (void)hipSetDevice(h->device);
+  (void)hipDeviceSynchronize();
+  (void)hipFree(h->ws);
+  delete h;
+  return 0;
+}
+
+int resnet_bind_params(resnet_actor* h, const float* flat) {
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  if (!flat) return fail(IMPALA_E_INVALID, "null pointer");
+  if (((uintptr_t)flat & 15) != 0) return fail(IMPALA_E_INVALID, "the flat buffer must be 16-byte aligned");
+  h->flat = flat;
+  h->packed = false;
+  return 0;
+}
+
+int resnet_refresh_weights(resnet_actor* h, void* stream) {
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  if (!h->flat) return fail(IMPALA_E_STATE, "resnet_bind_params not called");
+  CK(hipSetDevice(h->device));
+  const int r = RN_BY_TYPE(h, launch_pack, h, (hipStream_t)stream);
+  if (r) return r;
+  h->packed = true;
+  return 0;
+}
+
+int resnet_forward(resnet_actor* h, const uint8_t* obs, int n, float* logits, float* values, void* stream) {
+  if (int r = check_ready(h, obs, n)) return r;
+  if (!logits || !values) return fail(IMPALA_E_INVALID, "null pointer");
+  CK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (int r = RN_BY_TYPE(h, launch_forward, h, obs, n, st)) return r;
+  split_heads_kernel<<<cdiv((long)n * HEADS, 256), 256, 0, st>>>(h->heads, n, h->cfg.num_actions, logits, values);
+  CK_LAUNCH("split_heads");
+  return 0;
+}
+
+int resnet_act(resnet_actor* h, const uint8_t* obs, int n, const uint8_t* deterministic, int deterministic_all,
+               uint64_t seed, uint64_t counter, int64_t* actions, float* logits, float* values, void* stream) {
+  if (int r = check_ready(h, obs, n)) return r;
+  if (!actions || !logits || !values) return fail(IMPALA_E_INVALID, "null pointer");
+  CK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (int r = RN_BY_TYPE(h, launch_forward, h, obs, n, st)) return r;
+  act_heads_kernel<<<cdiv(n, 256), 256, 0, st>>>(h->heads, n, h->cfg.num_actions, deterministic, deterministic_all,
+                                                 seed, counter, actions, logits, values);
+  CK_LAUNCH("act_heads");
+  return 0;
+}
+
+int resnet_debug_read(resnet_actor* h, int which, void* dst, size_t bytes, void* stream) {
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  if (!h->cfg.debug) return fail(IMPALA_E_INVALID, "resnet_debug_read needs a handle created with debug = 1");
+  if (!dst) return fail(IMPALA_E_INVALID, "null pointer");
+  const size_t es = elt(h), B = (size_t)h->cfg.batch_size;
+  const char* src;
+  size_t cap;
+  if (which >= 0 && which < RESNET_DBG_STAGES) {
+    src = (const char*)h->dbg + B * dbg_off(which) * es;
+    cap = B * dbg_size(which) * es;
+  } else if (which == RESNET_DBG_Y) {
+    src = (const char*)h->y; cap = B * RN_FEAT * es;
+  } else if (which == RESNET_DBG_H) {
+    src = (const char*)h->h; cap = B * RN_HID * es;
+  } else if (which == RESNET_DBG_HEADS) {
+    src = (const char*)h->heads; cap = B * HEADS * 4;
+  } else {
+    return fail(IMPALA_E_INVALID, "unknown debug tensor");
+  }
+  if (bytes == 0 || bytes > cap) return fail(IMPALA_E_INVALID, "bytes must be in (0, batch_size frames]");
+  CK(hipSetDevice(h->device));
+  CK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"

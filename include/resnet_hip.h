@@ -1,0 +1,106 @@
+/* resnet_hip.h — C-ABI of the MI355X-native IMPALA ResNet actor-critic: the actor path (forward and
+ * act) of the reference's AtariActorCritic over ImpalaCNNLarge (in libimpala_hip.so).
+ *
+ * The reference (paths relative to the d3sm0/impala repository):
+ *   body        models/common.py:11-83   ResidualBlock, ImpalaCNNBlock, ImpalaCNNLarge
+ *   projection  models/models.py:61-76   AtariActorCritic: LayerNorm, Linear + GELU, actor, critic
+ *   act         models/distributed_models.py:21-32  AtariPPOModel.act
+ *
+ * Network, for n frames:
+ *   x = obs_u8 / 255                                              [n][3][64][64]
+ *   for (Cin, C, H) in (3,16,64), (16,32,32), (32,32,16):
+ *     x = conv3x3_pad1(x; Cin->C) + b
+ *     x = max_pool2d(x, kernel 3, stride 2, padding 1)            H -> H/2, padding -inf
+ *     twice: t = conv3x3_pad1(relu(x)) + b; x = x + conv3x3_pad1(relu(t)) + b
+ *   f = flatten_NCHW(relu(x))                                     [n][2048], index c*64 + y*8 + x
+ *   y = LayerNorm(2048, eps 1e-5)(f); h = GELU_erf(Linear(2048, 256)(y))
+ *   logits = Linear(256, A)(h); v = Linear(256, 1)(h)
+ *
+ * Parameters are one flat fp32 buffer in state_dict order:
+ *   model.body.body.{0,1,2}.{conv,res_block0.conv0,res_block0.conv1,res_block1.conv0,
+ *   res_block1.conv1}.{weight,bias}, model.projection.{0,1}.{weight,bias},
+ *   model.actor.{weight,bias}, model.critic.{weight,bias}
+ * 97,600 floats of body, 630,352 in all at A = 15.
+ *
+ * Conventions as iqn_hip.h: plain device pointers, `stream` = hipStream_t as void*, 0 = success
+ * else a hipError_t or IMPALA_E_* code with resnet_last_error() (the library's one last-error slot
+ * per thread) describing it.
+ */
+#ifndef RESNET_HIP_H_
+#define RESNET_HIP_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "impala_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RESNET_ABI_VERSION 1
+
+#define RESNET_FEATURES 2048
+#define RESNET_HIDDEN 256
+#define RESNET_MAX_ACTIONS 15
+#define RESNET_BODY_PARAMS 97600
+
+typedef struct resnet_actor resnet_actor;
+
+typedef struct resnet_config {
+  int batch_size;  /* the most frames of one resnet_forward / resnet_act call */
+  int num_actions; /* 1..15 */
+  int dtype;       /* IMPALA_DTYPE_F32 / IMPALA_DTYPE_BF16 */
+  int debug;       /* 1: the trunk also stores its stage tensors (resnet_debug_read) */
+} resnet_config;
+
+/* Stage tensors of the last forward (resnet_debug_read), per frame.  The body's are channels-last
+ * [H][H][C] of the compute type:
+ *   0            x after the stem's pool                       [32][32][16]
+ *   1..4         stage 1: t, x of res_block0, t, x of res_block1   [32][32][16]
+ *   5, 6..9      stage 2: x after the pool, then t, x, t, x        [16][16][32]
+ *   10, 11..14   stage 3: likewise                                 [8][8][32]
+ * y [2048] of the compute type in the kernel order p*32 + c (p = y*8 + x; canonical c*64 + p),
+ * h [256] of the compute type, heads [16] fp32 (logits 0..A-1, value at 15). */
+#define RESNET_DBG_STAGES 15
+#define RESNET_DBG_Y 15
+#define RESNET_DBG_H 16
+#define RESNET_DBG_HEADS 17
+
+int resnet_abi_version(void);
+const char* resnet_last_error(void);
+int resnet_config_default(resnet_config* cfg);
+/* 630,352 for A = 15 */
+size_t resnet_param_count(int num_actions);
+
+/* Invalid configurations (batch_size < 1, num_actions outside [1, 15], unknown dtype, debug not 0 / 1)
+ * are refused before any HIP call. */
+int resnet_create(const resnet_config* cfg, int device, resnet_actor** out);
+int resnet_destroy(resnet_actor* h);
+
+/* The flat fp32 [resnet_param_count] buffer (caller-owned, device). */
+int resnet_bind_params(resnet_actor* h, const float* flat);
+/* Pack the flat parameters into the kernels' operand layouts (fragment-major weights of the
+ * compute type, fp32 side vectors); call after bind and after every write to the flat buffer. */
+int resnet_refresh_weights(resnet_actor* h, void* stream);
+
+/* logits [n][A], values [n] of 1 <= n <= batch_size frames; obs [n][3][64][64] u8, 16-byte aligned. */
+int resnet_forward(resnet_actor* h, const uint8_t* obs, int n, float* logits, float* values,
+                   void* stream);
+/* impala_act's semantics on this network: per frame argmax (first maximal index) where the
+ * frame's deterministic flag is set (deterministic [n] u8, or NULL: deterministic_all), else a draw
+ * from softmax(logits) on the uniform keyed by (seed, counter, frame).  actions [n] int64. */
+int resnet_act(resnet_actor* h, const uint8_t* obs, int n, const uint8_t* deterministic,
+               int deterministic_all, uint64_t seed, uint64_t counter, int64_t* actions,
+               float* logits, float* values, void* stream);
+
+/* Test / inspection entry, valid on a handle created with debug = 1 only: the tensor `which`
+ * (RESNET_DBG_*) as the last forward / act left it, its leading `bytes` copied to dst (device or
+ * host) on `stream`; bytes in (0, batch_size frames]. */
+int resnet_debug_read(resnet_actor* h, int which, void* dst, size_t bytes, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RESNET_HIP_H_ */
