@@ -100,9 +100,9 @@ IQN_EXPORTS = (
 RESNET_EXPORTS = (
     "resnet_abi_version", "resnet_last_error", "resnet_config_default", "resnet_param_count",
     "resnet_create", "resnet_destroy", "resnet_bind_params", "resnet_refresh_weights",
-    "resnet_forward", "resnet_act", "resnet_debug_read",
+    "resnet_forward", "resnet_act", "resnet_debug_read", "resnet_forward_train", "resnet_backward",
 )
-RESNET_ABI_VERSION = 1
+RESNET_ABI_VERSION = 2
 RESNET_DBG_Y, RESNET_DBG_H, RESNET_DBG_HEADS = 15, 16, 17
 IQN_ABI_VERSION = 3
 IQN_DBG_DPRE, IQN_DBG_DX, IQN_DBG_COS = 100, 101, 102
@@ -188,7 +188,7 @@ class IqnConfig(C.Structure):
 
 class ResnetConfig(C.Structure):
     _fields_ = [("batch_size", C.c_int), ("num_actions", C.c_int), ("dtype", C.c_int),
-                ("debug", C.c_int)]
+                ("debug", C.c_int), ("train", C.c_int)]
 
 
 class IqnOptim(C.Structure):
@@ -383,6 +383,8 @@ def _declare(lib):
     lib.resnet_forward.argtypes = [_P, _P, C.c_int, _P, _P, _P]
     lib.resnet_act.argtypes = [_P, _P, C.c_int, _P, C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, _P]
     lib.resnet_debug_read.argtypes = [_P, C.c_int, _P, C.c_size_t, _P]
+    lib.resnet_forward_train.argtypes = [_P, _P, C.c_int, _P, _P, _P]
+    lib.resnet_backward.argtypes = [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P]
     for name in RESNET_EXPORTS:
         getattr(lib, name).restype = (C.c_char_p if name == "resnet_last_error" else
                                       C.c_size_t if name == "resnet_param_count" else C.c_int)

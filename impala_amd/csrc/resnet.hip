@@ -1,5 +1,5 @@
-// The IMPALA ResNet actor-critic's actor path (include/resnet_hip.h): kernels, launchers and the
-// handle, a translation unit of its own -- the other units' code objects are the same with or
+// The IMPALA ResNet actor-critic (include/resnet_hip.h): the actor path's kernels, the launchers and
+// the handle (the backward pass's kernels: resnet_bwd.h), a translation unit of its own -- the other units' code objects are the same with or
 // without it.  DESIGN.md §15 has the design and the LDS map.
 //
 // One forward of n frames is four launches:
@@ -49,6 +49,7 @@ __host__ __device__ constexpr int dbg_off(int id) {
   return id < 5 ? id * 16384 : id < 10 ? 81920 + (id - 5) * 8192 : 122880 + (id - 10) * 2048;
 }
 constexpr int RN_DBG_FRAME = 133120;
+static_assert(dbg_off(14) + dbg_size(14) == RN_DBG_FRAME, "a frame's stage tensors");
 
 // geometry of conv `id` (5 per stage: the pooled conv, then conv0, conv1 of the two blocks)
 struct ConvGeo { int cin, cout; };
@@ -82,8 +83,16 @@ struct TrunkArgs {
   const void* w[RN_CONVS];  // fragment-major weights of the compute type
   const float* vecs;
   void* y;    // [n][2048] compute type, kernel order p*32 + c
-  void* dbg;  // debug only
+  void* dbg;  // debug / train only
 };
+// train only, behind dbg's B frames: the winning tap of every pooled element, then (mean, rstd) of the
+// LayerNorm per frame
+template <typename T> DEV uint8_t* train_amax(const TrunkArgs& a) {
+  return reinterpret_cast<uint8_t*>(a.dbg) + (size_t)a.B * RN_DBG_FRAME * sizeof(T);
+}
+// the pools' winning taps: bytes per frame, and a stage's offset in a frame's block ([HO][HO][C] each)
+constexpr int RN_AMAX_FRAME = 16384 + 8192 + 2048;
+__host__ __device__ constexpr int amax_off(int stage) { return stage == 0 ? 0 : stage == 1 ? 16384 : 24576; }
 
 DEV void lds_zero(char* p, int bytes) {
   for (int i = threadIdx.x * 16; i < bytes; i += RN_THREADS * 16) *reinterpret_cast<i32x4*>(p + i) = i32x4{0, 0, 0, 0};
@@ -231,8 +240,9 @@ template <typename T, int H, int C> struct EpiResidual {
 // max_pool2d(kernel 3, stride 2, padding 1) of conv rows r0 .. r0 + SR - 1 (and row r0 - 1, still in
 // the ring) -> output rows r0/2 .. r0/2 + SR/2 - 1 in the interior of `out`; a tap outside the
 // image is left out (-inf padding).  The max is taken in fp32 and rounded once: rounding is monotone.
-template <typename T, int HC, int C, int SR>
-DEV void pool_rows(const float* __restrict__ strip, T* __restrict__ out, int r0) {
+// TRAIN: amax [HO][HO][C] also takes the window's winning tap 0..8 (row-major; of equal values the first).
+template <typename T, int HC, int C, int SR, bool TRAIN = false>
+DEV void pool_rows(const float* __restrict__ strip, T* __restrict__ out, int r0, uint8_t* __restrict__ amax = nullptr) {
   constexpr int HO = HC / 2, RING = SR + 1, CV = C / 4, ITEMS = (SR / 2) * HO * CV;
   for (int i = threadIdx.x; i < ITEMS; i += RN_THREADS) {
     const int c0 = 4 * (i % CV), ox = (i / CV) % HO, oy = r0 / 2 + i / (CV * HO);
@@ -247,6 +257,20 @@ DEV void pool_rows(const float* __restrict__ strip, T* __restrict__ out, int r0)
       }
     const float o[4] = {m[0], m[1], m[2], m[3]};
     store4(out + ((oy + 1) * (HO + 2) + ox + 1) * C + c0, o);
+    if constexpr (TRAIN) {
+      uint32_t win = 0;  // taps in reverse order: the first of equal values is written last
+#pragma unroll
+      for (int tap = 8; tap >= 0; --tap) {
+        const int r = 2 * oy + tap / 3 - 1, cx = 2 * ox + tap % 3 - 1;
+        if (r >= 0 && cx >= 0) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(strip + ((r % RING) * HC + cx) * C + c0);
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (v[q] == m[q]) win = (win & ~(255u << (8 * q))) | ((uint32_t)tap << (8 * q));
+        }
+      }
+      *reinterpret_cast<uint32_t*>(amax + (oy * HO + ox) * C + c0) = win;
+    }
   }
 }
 
@@ -279,7 +303,7 @@ DEV void res_blocks(T* x, T* t, const TrunkArgs& a, int id0, int f) {
   }
 }
 
-template <typename T, bool DEBUG>
+template <typename T, bool DEBUG, bool TRAIN = false>
 __global__ __launch_bounds__(RN_THREADS) void resnet_trunk_kernel(const TrunkArgs a) {
   using L = Lds<T>;
   __shared__ __attribute__((aligned(16))) char lds[L::TOTAL];
@@ -314,7 +338,7 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_trunk_kernel(const TrunkArg
         conv_stem<T, 8>(img, reinterpret_cast<const T*>(a.w[0]), r0,
                         EpiStrip<64, 16, 9>{strip, a.vecs + RV_CB, 1.f / 255.f});
         __syncthreads();
-        pool_rows<T, 64, 16, 8>(strip, x1, r0);
+        pool_rows<T, 64, 16, 8, TRAIN>(strip, x1, r0, TRAIN ? train_amax<T>(a) + (size_t)f * RN_AMAX_FRAME + amax_off(0) : nullptr);
         __syncthreads();
       }
     }
@@ -333,7 +357,7 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_trunk_kernel(const TrunkArg
         conv_lds<T, 16, 32, 32, 4, false>(x1, reinterpret_cast<const T*>(a.w[5]), r0,
                                           EpiStrip<32, 32, 5>{strip, a.vecs + RV_CB + 32 * 5, 1.f});
         __syncthreads();
-        pool_rows<T, 32, 32, 4>(strip, x2, r0);
+        pool_rows<T, 32, 32, 4, TRAIN>(strip, x2, r0, TRAIN ? train_amax<T>(a) + (size_t)f * RN_AMAX_FRAME + amax_off(1) : nullptr);
         __syncthreads();
       }
     }
@@ -353,7 +377,7 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_trunk_kernel(const TrunkArg
         conv_lds<T, 32, 32, 16, 8, false>(x2, reinterpret_cast<const T*>(a.w[10]), r0,
                                           EpiStrip<16, 32, 9>{strip, a.vecs + RV_CB + 32 * 10, 1.f});
         __syncthreads();
-        pool_rows<T, 16, 32, 8>(strip, x3, r0);
+        pool_rows<T, 16, 32, 8, TRAIN>(strip, x3, r0, TRAIN ? train_amax<T>(a) + (size_t)f * RN_AMAX_FRAME + amax_off(2) : nullptr);
         __syncthreads();
       }
     }
@@ -380,6 +404,13 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_trunk_kernel(const TrunkArg
       const float var = (((red[8] + red[9]) + (red[10] + red[11])) + ((red[12] + red[13]) + (red[14] + red[15]))) *
                         (1.f / RN_FEAT);
       const float rstd = 1.f / sqrtf(var + LN_EPS);
+      if constexpr (TRAIN) {
+        if (tid == 0) {
+          float* lnstat = reinterpret_cast<float*>(train_amax<T>(a) + (size_t)a.B * RN_AMAX_FRAME);
+          lnstat[2 * f] = mean;
+          lnstat[2 * f + 1] = rstd;
+        }
+      }
       float g[4], b[4], o[4];
       load4(a.vecs + RV_LNG + p * 32 + c0, g);
       load4(a.vecs + RV_LNB + p * 32 + c0, b);
@@ -518,6 +549,8 @@ size_t body_offsets(int (&w)[RN_CONVS], int (&b)[RN_CONVS]) {
   return o;
 }
 
+#include "resnet_bwd.h"
+
 }  // namespace
 
 struct resnet_actor {
@@ -534,6 +567,13 @@ struct resnet_actor {
   void* h;
   float* heads;
   void* dbg;
+  // train = 1 only (fp32): what resnet_forward_train saves beside dbg, and the backward's workspace
+  int trained_n = 0;  // frames of the last resnet_forward_train; 0: none, or the weights were refreshed since
+  int wg_groups = 0;  // frame groups of the weight-gradient kernels
+  uint8_t* amax;
+  float* lnstat;
+  float* wd[RN_CONVS];
+  float *wfct, *gz, *gy, *gws, *slab;
 };
 
 namespace {
@@ -550,20 +590,28 @@ int check_ready(resnet_actor* h, const uint8_t* obs, int n) {
   return 0;
 }
 
+GradOff flat_offsets(int A) {
+  GradOff g;
+  size_t o = body_offsets(g.w, g.b);
+  g.lng = (int)o; o += RN_FEAT;
+  g.lnb = (int)o; o += RN_FEAT;
+  g.wfc = (int)o; o += (size_t)RN_HID * RN_FEAT;
+  g.bfc = (int)o; o += RN_HID;
+  g.wa = (int)o; o += (size_t)A * RN_HID;
+  g.ba = (int)o; o += A;
+  g.wc = (int)o; o += RN_HID;
+  g.bc = (int)o;
+  return g;
+}
+
 template <typename T> int launch_pack(resnet_actor* h, hipStream_t st) {
-  int wo[RN_CONVS], bo[RN_CONVS];
-  size_t o = body_offsets(wo, bo);
-  VecSrc vs;
-  for (int id = 0; id < RN_CONVS; ++id) vs.cb[id] = bo[id];
   const int A = h->cfg.num_actions;
-  vs.lng = (int)o; o += RN_FEAT;
-  vs.lnb = (int)o; o += RN_FEAT;
-  const size_t wfc = o; o += (size_t)RN_HID * RN_FEAT;
-  vs.bfc = (int)o; o += RN_HID;
-  vs.wa = (int)o; o += (size_t)A * RN_HID;
-  vs.ba = (int)o; o += A;
-  vs.wc = (int)o; o += RN_HID;
-  vs.bc = (int)o;
+  const GradOff go = flat_offsets(A);
+  const int* wo = go.w;
+  const size_t wfc = go.wfc;
+  VecSrc vs;
+  for (int id = 0; id < RN_CONVS; ++id) vs.cb[id] = go.b[id];
+  vs.lng = go.lng; vs.lnb = go.lnb; vs.bfc = go.bfc; vs.wa = go.wa; vs.ba = go.ba; vs.wc = go.wc; vs.bc = go.bc;
   for (int id = 0; id < RN_CONVS; ++id) {
     const ConvGeo g = conv_geo(id);
     const int ck = kernel_cin(g.cin), nks = conv_nks_rt(ck, Frag<T>::KSTEP);
@@ -575,10 +623,22 @@ template <typename T> int launch_pack(resnet_actor* h, hipStream_t st) {
   CK_LAUNCH("resnet_pack_fc");
   resnet_pack_vec_kernel<<<cdiv(RV_TOTAL, 256), 256, 0, st>>>(h->flat, vs, A, h->vecs);
   CK_LAUNCH("resnet_pack_vec");
+  if constexpr (sizeof(T) == 4) {
+    if (h->cfg.train) {  // the data gradients' layouts: taps flipped, Cin / Cout swapped; Wfc transposed
+      for (int id = 1; id < RN_CONVS; ++id) {
+        const ConvGeo g = conv_geo(id);
+        const int total = g.cout * g.cin * 9;
+        resnet_pack_dgrad_kernel<<<cdiv(total, 256), 256, 0, st>>>(h->flat + wo[id], h->wd[id], g.cin, g.cout, total);
+        CK_LAUNCH("resnet_pack_dgrad");
+      }
+      resnet_pack_fct_kernel<<<RN_HID * RN_FEAT / 256, 256, 0, st>>>(h->flat + wfc, h->wfct);
+      CK_LAUNCH("resnet_pack_fct");
+    }
+  }
   return 0;
 }
 
-template <typename T> int launch_forward(resnet_actor* h, const uint8_t* obs, int n, hipStream_t st) {
+template <typename T, bool TRAIN = false> int launch_forward(resnet_actor* h, const uint8_t* obs, int n, hipStream_t st) {
   TrunkArgs a;
   a.obs = obs;
   a.n = n;
@@ -587,14 +647,72 @@ template <typename T> int launch_forward(resnet_actor* h, const uint8_t* obs, in
   a.vecs = h->vecs;
   a.y = h->y;
   a.dbg = h->dbg;
+  h->trained_n = 0;  // this call rewrites y and the projection's sums
   const int grid = n < h->n_cu ? n : h->n_cu;
-  if (h->cfg.debug) resnet_trunk_kernel<T, true><<<grid, RN_THREADS, 0, st>>>(a);
+  if (TRAIN) resnet_trunk_kernel<T, true, TRAIN><<<grid, RN_THREADS, 0, st>>>(a);
+  else if (h->cfg.debug) resnet_trunk_kernel<T, true><<<grid, RN_THREADS, 0, st>>>(a);
   else resnet_trunk_kernel<T, false><<<grid, RN_THREADS, 0, st>>>(a);
   CK_LAUNCH("resnet_trunk");
   resnet_fc_kernel<T><<<16 * RN_KSPLIT, 256, 0, st>>>((const T*)h->y, (const T*)h->wfc, h->part, n, a.B);
   CK_LAUNCH("resnet_fc");
   resnet_heads_kernel<T><<<cdiv(n, 4), 256, 0, st>>>(h->part, h->vecs, (T*)h->h, h->heads, n, a.B);
   CK_LAUNCH("resnet_heads");
+  return 0;
+}
+
+int launch_backward(resnet_actor* h, const uint8_t* obs, int n, const float* dl, const float* dv, float* grad, int acc,
+                    hipStream_t st) {
+  const int A = h->cfg.num_actions, B = h->cfg.batch_size;
+  const GradOff go = flat_offsets(A);
+  const float* sav = (const float*)h->dbg;
+  resnet_head_bwd_kernel<<<cdiv(n, 4), 256, 0, st>>>(h->part, h->vecs, dl, dv, h->gz, n, B, A);
+  CK_LAUNCH("resnet_head_bwd");
+  resnet_head_wgrad_kernel<<<HEADS + 1, 256, 0, st>>>((const float*)h->h, h->gz, dl, dv, grad, go, n, A, acc);
+  CK_LAUNCH("resnet_head_wgrad");
+  resnet_fc_wgrad_kernel<<<16 * (RN_FEAT / 256), 256, 0, st>>>(h->gz, (const float*)h->y, grad, go.wfc, n, acc);
+  CK_LAUNCH("resnet_fc_wgrad");
+  resnet_fc_dgrad_kernel<<<RN_FEAT / 16, 256, 0, st>>>(h->gz, h->wfct, h->gy, n);
+  CK_LAUNCH("resnet_fc_dgrad");
+  resnet_ln_affine_kernel<<<RN_FEAT / 256, 256, 0, st>>>(h->gy, sav + (size_t)B * dbg_off(14), h->lnstat, grad, go.lng,
+                                                         go.lnb, n, acc);
+  CK_LAUNCH("resnet_ln_affine");
+  BwdArgs b;
+  b.n = n;
+  b.B = B;
+  for (int id = 0; id < RN_CONVS; ++id) b.wd[id] = h->wd[id];
+  b.vecs = h->vecs;
+  b.sav = sav;
+  b.amax = h->amax;
+  b.lnstat = h->lnstat;
+  b.gy = h->gy;
+  b.gws = h->gws;
+  resnet_trunk_bwd_kernel<<<n < h->n_cu ? n : h->n_cu, RN_THREADS, 0, st>>>(b);
+  CK_LAUNCH("resnet_trunk_bwd");
+  WgArgs w;
+  w.obs = obs;
+  w.n = n;
+  w.B = B;
+  w.sav = sav;
+  w.gws = h->gws;
+  w.amax = h->amax;
+  w.slab = h->slab;
+  w.go = go;
+  const int G = n < h->wg_groups ? n : h->wg_groups;
+  //                  CIN COUT  H  R  pooled relu  stem
+  resnet_wgrad_kernel<4, 16, 64, 8, true, false, true><<<dim3(G, 1), RN_THREADS, 0, st>>>(w, 0);
+  CK_LAUNCH("resnet_wgrad stem");
+  resnet_wgrad_kernel<16, 16, 32, 8, false, true, false><<<dim3(G, 4), RN_THREADS, 0, st>>>(w, 1);
+  CK_LAUNCH("resnet_wgrad stage 1");
+  resnet_wgrad_kernel<16, 32, 32, 8, true, false, false><<<dim3(G, 1), RN_THREADS, 0, st>>>(w, 5);
+  CK_LAUNCH("resnet_wgrad conv 5");
+  resnet_wgrad_kernel<32, 32, 16, 16, false, true, false><<<dim3(G, 4), RN_THREADS, 0, st>>>(w, 6);
+  CK_LAUNCH("resnet_wgrad stage 2");
+  resnet_wgrad_kernel<32, 32, 16, 16, true, false, false><<<dim3(G, 1), RN_THREADS, 0, st>>>(w, 10);
+  CK_LAUNCH("resnet_wgrad conv 10");
+  resnet_wgrad_kernel<32, 32, 8, 8, false, true, false><<<dim3(G, 4), RN_THREADS, 0, st>>>(w, 11);
+  CK_LAUNCH("resnet_wgrad stage 3");
+  resnet_wreduce_kernel<<<cdiv(RESNET_BODY_PARAMS, 256), 256, 0, st>>>(h->slab, G, grad, acc);
+  CK_LAUNCH("resnet_wreduce");
   return 0;
 }
 
@@ -610,7 +728,7 @@ const char* resnet_last_error(void) { return impala_last_error(); }
 
 int resnet_config_default(resnet_config* cfg) {
   if (!cfg) return fail(IMPALA_E_INVALID, "null config");
-  *cfg = resnet_config{128, RESNET_MAX_ACTIONS, IMPALA_DTYPE_F32, 0};
+  *cfg = resnet_config{128, RESNET_MAX_ACTIONS, IMPALA_DTYPE_F32, 0, 0};
   return 0;
 }
 
@@ -626,6 +744,9 @@ int resnet_create(const resnet_config* cfg, int device, resnet_actor** out) {
     return fail(IMPALA_E_INVALID, "num_actions must be in [1, 15]");
   if (cfg->dtype != IMPALA_DTYPE_F32 && cfg->dtype != IMPALA_DTYPE_BF16) return fail(IMPALA_E_INVALID, "unknown dtype");
   if (cfg->debug != 0 && cfg->debug != 1) return fail(IMPALA_E_INVALID, "debug must be 0 or 1");
+  if (cfg->train != 0 && cfg->train != 1) return fail(IMPALA_E_INVALID, "train must be 0 or 1");
+  if (cfg->train && cfg->dtype != IMPALA_DTYPE_F32)
+    return fail(IMPALA_E_INVALID, "train = 1 needs dtype fp32: the backward pass is fp32 only");
   CK(hipSetDevice(device));
   int cu = 0;
   CK(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device));
@@ -650,7 +771,25 @@ int resnet_create(const resnet_config* cfg, int device, resnet_actor** out) {
   const size_t o_h = off; off = al(off + B * RN_HID * es);
   const size_t o_heads = off; off = al(off + B * HEADS * 4);
   const size_t o_dbg = off;
-  if (cfg->debug) off = al(off + B * RN_DBG_FRAME * es);
+  if (cfg->debug || cfg->train) off = al(off + B * RN_DBG_FRAME * es);
+  // train: the pools' winning taps, the LayerNorm statistics, the data gradients' weights, gz, gy, the
+  // gradient at every conv's output, the weight gradients' partial sums per frame group
+  h->wg_groups = (int)(B < (size_t)(h->n_cu / 4) ? B : h->n_cu / 4 > 0 ? h->n_cu / 4 : 1);
+  size_t o_amax = 0, o_ln = 0, o_wd[RN_CONVS] = {}, o_wfct = 0, o_gz = 0, o_gy = 0, o_gws = 0, o_slab = 0;
+  if (cfg->train) {
+    o_amax = o_dbg + B * RN_DBG_FRAME * 4;  // (where the trunk looks for them: train_amax)
+    o_ln = o_amax + B * RN_AMAX_FRAME;
+    off = al(o_ln + B * 2 * 4);
+    for (int id = 1; id < RN_CONVS; ++id) {
+      const ConvGeo g = conv_geo(id);
+      o_wd[id] = off; off = al(off + (size_t)g.cout * g.cin * 9 * 4);
+    }
+    o_wfct = off; off = al(off + (size_t)RN_HID * RN_FEAT * 4);
+    o_gz = off; off = al(off + B * RN_HID * 4);
+    o_gy = off; off = al(off + B * RN_FEAT * 4);
+    o_gws = off; off = al(off + B * RN_DBG_FRAME * 4);
+    o_slab = off; off = al(off + (size_t)h->wg_groups * RESNET_BODY_PARAMS * 4);
+  }
   const hipError_t e = hipMalloc((void**)&h->ws, off);
   if (e != hipSuccess) {
     delete h;
@@ -663,7 +802,18 @@ int resnet_create(const resnet_config* cfg, int device, resnet_actor** out) {
   h->part = (float*)(h->ws + o_part);
   h->h = h->ws + o_h;
   h->heads = (float*)(h->ws + o_heads);
-  h->dbg = cfg->debug ? h->ws + o_dbg : nullptr;
+  h->dbg = cfg->debug || cfg->train ? h->ws + o_dbg : nullptr;
+  if (cfg->train) {
+    h->amax = (uint8_t*)(h->ws + o_amax);
+    h->lnstat = (float*)(h->ws + o_ln);
+    h->wd[0] = nullptr;
+    for (int id = 1; id < RN_CONVS; ++id) h->wd[id] = (float*)(h->ws + o_wd[id]);
+    h->wfct = (float*)(h->ws + o_wfct);
+    h->gz = (float*)(h->ws + o_gz);
+    h->gy = (float*)(h->ws + o_gy);
+    h->gws = (float*)(h->ws + o_gws);
+    h->slab = (float*)(h->ws + o_slab);
+  }
   *out = h;
   return 0;
 }
@@ -693,6 +843,7 @@ int resnet_refresh_weights(resnet_actor* h, void* stream) {
   const int r = RN_BY_TYPE(h, launch_pack, h, (hipStream_t)stream);
   if (r) return r;
   h->packed = true;
+  h->trained_n = 0;
   return 0;
 }
 
@@ -705,6 +856,33 @@ int resnet_forward(resnet_actor* h, const uint8_t* obs, int n, float* logits, fl
   split_heads_kernel<<<cdiv((long)n * HEADS, 256), 256, 0, st>>>(h->heads, n, h->cfg.num_actions, logits, values);
   CK_LAUNCH("split_heads");
   return 0;
+}
+
+int resnet_forward_train(resnet_actor* h, const uint8_t* obs, int n, float* logits, float* values, void* stream) {
+  if (int r = check_ready(h, obs, n)) return r;
+  if (!logits || !values) return fail(IMPALA_E_INVALID, "null pointer");
+  if (!h->cfg.train) return fail(IMPALA_E_INVALID, "resnet_forward_train needs a handle created with train = 1");
+  CK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (int r = launch_forward<float, true>(h, obs, n, st)) return r;
+  split_heads_kernel<<<cdiv((long)n * HEADS, 256), 256, 0, st>>>(h->heads, n, h->cfg.num_actions, logits, values);
+  CK_LAUNCH("split_heads");
+  h->trained_n = n;
+  return 0;
+}
+
+int resnet_backward(resnet_actor* h, const uint8_t* obs, int n, const float* dlogits, const float* dvalues,
+                    float* grad_flat, int accumulate, void* stream) {
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  if (!h->cfg.train) return fail(IMPALA_E_INVALID, "resnet_backward needs a handle created with train = 1");
+  if (h->trained_n == 0)
+    return fail(IMPALA_E_INVALID, "resnet_backward needs a resnet_forward_train since the last refresh or forward");
+  if (n != h->trained_n) return fail(IMPALA_E_INVALID, "n differs from the last resnet_forward_train's");
+  if (int r = check_ready(h, obs, n)) return r;
+  if (!dlogits || !dvalues || !grad_flat) return fail(IMPALA_E_INVALID, "null pointer");
+  if (accumulate != 0 && accumulate != 1) return fail(IMPALA_E_INVALID, "accumulate must be 0 or 1");
+  CK(hipSetDevice(h->device));
+  return launch_backward(h, obs, n, dlogits, dvalues, grad_flat, accumulate, (hipStream_t)stream);
 }
 
 int resnet_act(resnet_actor* h, const uint8_t* obs, int n, const uint8_t* deterministic, int deterministic_all,

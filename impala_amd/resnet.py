@@ -1,8 +1,10 @@
 """The IMPALA ResNet actor-critic on the HIP library: the reference's
 ``AtariActorCritic`` (models/models.py:61-76) with ``ImpalaCNNLarge`` (models/common.py:11-83) as
-its body -- the actor path, ``forward`` and ``act``.  Every compute entry is one call of
-include/resnet_hip.h; the compute path is the HIP library only.  The learner cannot train this
-network yet, so there is no ``conf/`` entry for it.
+its body -- the actor path, ``forward`` and ``act``, and the backward pass:
+``forward_train`` returns outputs attached to the autograd graph, and ``loss.backward()`` runs
+``resnet_backward`` into ``model.flat_grad``.  Every compute entry is one call of
+include/resnet_hip.h; the compute path is the HIP library only.  The one-call learner step (loss
+head, clip and Adam fused) is not built, so there is no ``conf/`` entry for this network yet.
 """
 from __future__ import annotations
 
@@ -75,7 +77,7 @@ class ResnetEngine(_lib.NativeHandle):
         heads=(_lib.RESNET_DBG_HEADS, "f32", (16,)))
 
     def __init__(self, model: "ImpalaResNetModel", batch_size: int = 128,
-                 dtype: Optional[str] = None, debug: bool = False):
+                 dtype: Optional[str] = None, debug: bool = False, train: bool = False):
         dtype = dtype or model.compute_dtype
         if dtype not in ("fp32", "bf16"):
             raise ValueError("dtype: 'fp32' or 'bf16'")
@@ -86,7 +88,7 @@ class ResnetEngine(_lib.NativeHandle):
             raise RuntimeError("resnet ABI version mismatch (rebuild: python -m impala_amd.build)")
         cfg = default_config()
         cfg.batch_size, cfg.num_actions = int(batch_size), model.action_dim
-        cfg.dtype, cfg.debug = (1 if dtype == "bf16" else 0), int(bool(debug))
+        cfg.dtype, cfg.debug, cfg.train = (1 if dtype == "bf16" else 0), int(bool(debug)), int(bool(train))
         self.N, self.A, self.bf16 = cfg.batch_size, cfg.num_actions, dtype == "bf16"
         self._open("resnet_create", C.byref(cfg), self.device_index(self.device))
         check(lib().resnet_bind_params(self._h, _lib.ptr(model.flat)), "resnet_bind_params", _ERR)
@@ -109,6 +111,42 @@ class ResnetEngine(_lib.NativeHandle):
         check(lib().resnet_forward(self._h, _lib.ptr(obs), n, _lib.ptr(logits), _lib.ptr(values),
                                    _lib.stream_ptr(None)), "resnet_forward", _ERR)
         return logits, values
+
+    def forward_train(self, obs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``forward``'s outputs, the same bits, with what ``backward`` needs left in the handle
+        (an engine created with ``train=True``)."""
+        self._fresh()
+        self._obs = obs.contiguous()  # the backward reads the frames again (the stem's gradient)
+        n = self._obs.shape[0]
+        logits = torch.empty(n, self.A, device=self.device)
+        values = torch.empty(n, 1, device=self.device)
+        check(lib().resnet_forward_train(self._h, _lib.ptr(self._obs), n, _lib.ptr(logits),
+                                         _lib.ptr(values), _lib.stream_ptr(None)),
+              "resnet_forward_train", _ERR)
+        return logits, values
+
+    def backward(self, dlogits: torch.Tensor, dvalues: torch.Tensor,
+                 out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+        """The gradient of ``sum(dlogits * logits) + sum(dvalues * values)`` of the last
+        ``forward_train`` with respect to the flat parameters, written (or, with ``accumulate``,
+        added) to ``out`` [param_count] fp32 (a new buffer without one)."""
+        if self._version != self.model._version:
+            raise RuntimeError("the parameters changed since forward_train")
+        obs = getattr(self, "_obs", None)
+        if obs is None:
+            raise RuntimeError("backward needs a forward_train first")
+        n = obs.shape[0]
+        dl = dlogits.to(self.device, torch.float32).reshape(n, self.A).contiguous()
+        dv = dvalues.to(self.device, torch.float32).reshape(n).contiguous()
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate needs the buffer to add to")
+            out = torch.empty(self.model.flat.numel(), device=self.device)
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != self.model.flat.numel():
+            raise ValueError("out: a contiguous fp32 tensor of param_count elements")
+        check(lib().resnet_backward(self._h, _lib.ptr(obs), n, _lib.ptr(dl), _lib.ptr(dv), _lib.ptr(out),
+                                    int(bool(accumulate)), _lib.stream_ptr(None)), "resnet_backward", _ERR)
+        return out
 
     def act(self, obs: torch.Tensor, deterministic, seed: int, counter: int):
         """-> (action [n, 1] i64, logits [n, A], values [n, 1]) on the device; ``deterministic``
@@ -146,6 +184,34 @@ class ResnetEngine(_lib.NativeHandle):
             kind, shape, n, self.bf16, self.device)
 
 
+class _ResnetGrad(torch.autograd.Function):
+    """``ImpalaResNetModel.forward_train`` on the autograd graph, in chunks of the training
+    engine's batch.  An engine holds the activations of one chunk at a time, so a chunk's forward
+    runs again at the head of its backward; the chunks' gradients are summed in a staging buffer
+    (``resnet_backward``'s ``accumulate``) and added to ``model.flat_grad`` once."""
+
+    @staticmethod
+    def forward(ctx, anchor, model, obs):
+        ctx.model, ctx.obs, ctx.version = model, obs, model._version
+        eng = model.train_engine()
+        outs = [eng.forward_train(c) for c in model._chunks(obs, eng.N)]
+        return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+
+    @staticmethod
+    def backward(ctx, dlogits, dvalues):
+        model, eng = ctx.model, ctx.model.train_engine()
+        if ctx.version != model._version:
+            raise RuntimeError("the parameters changed between forward_train and backward")
+        if model._grad_stage is None:
+            model._grad_stage = torch.empty_like(model.flat_grad)
+        for i in range(0, ctx.obs.shape[0], eng.N):
+            eng.forward_train(ctx.obs[i:i + eng.N])
+            eng.backward(dlogits[i:i + eng.N], dvalues[i:i + eng.N], out=model._grad_stage, accumulate=i > 0)
+        model._bind_grads()
+        model.flat_grad.add_(model._grad_stage)
+        return None, None, None
+
+
 class ImpalaResNetModel(FlatModule):
     """``AtariPPOModel``'s surface over the IMPALA ResNet body on an MI355X:
     ``forward(obs_u8 [N,3,64,64]) -> (logits [N,A], v [N,1])`` through ``resnet_forward`` and
@@ -153,7 +219,7 @@ class ImpalaResNetModel(FlatModule):
     (models/distributed_models.py:21-32) through ``resnet_act``."""
 
     def __init__(self, obs_shape: Tuple[int, ...] = OBS_SHAPE, n_act: int = 15, device="cuda",
-                 dtype: Optional[str] = None, seed: Optional[int] = None):
+                 dtype: Optional[str] = None, seed: Optional[int] = None, train_batch: int = 160):
         super().__init__()
         if tuple(obs_shape) != OBS_SHAPE:
             # models/common.py:81-83 hard-codes output_dim 2048 => 64x64x3 only
@@ -165,6 +231,8 @@ class ImpalaResNetModel(FlatModule):
         self._specs = param_specs(self.action_dim)
         self._views, = self._attach_segments(torch.device(device))
         self._infer_engine = None
+        self._train_engine, self._train_batch = None, int(train_batch)  # 160: IMPALA's 8 x 20 frames
+        self._anchor = self._grad_stage = None
         self._act_seed = int.from_bytes(os.urandom(8), "little") >> 2
         self._act_calls = 0
         self.reset_parameters(seed)
@@ -186,9 +254,50 @@ class ImpalaResNetModel(FlatModule):
             self._infer_engine = ResnetEngine(self, batch_size=128)
         return self._infer_engine
 
-    def _chunks(self, x: torch.Tensor):
-        N = self._engine().N
+    def _chunks(self, x: torch.Tensor, N: Optional[int] = None):
+        N = N or self._engine().N
         return [x[i:i + N] for i in range(0, x.shape[0], N)]
+
+    def train_engine(self, batch_size: Optional[int] = None) -> ResnetEngine:
+        """The training engine (fp32); with ``batch_size``, one of that many frames a chunk."""
+        if batch_size is not None and int(batch_size) != self._train_batch:
+            self._train_batch, self._train_engine = int(batch_size), None
+        if self._train_engine is None:
+            self._train_engine = ResnetEngine(self, self._train_batch, "fp32", train=True)
+        return self._train_engine
+
+    def _bind_grads(self) -> None:
+        """Every parameter's ``.grad`` is its view of ``flat_grad``: zeroed where an optimizer's
+        ``zero_grad`` had set it to None, taking over a gradient held elsewhere."""
+        with torch.no_grad():
+            for p, g in self._grad_pairs():
+                if p.grad is None:
+                    g.zero_()
+                elif p.grad.data_ptr() != g.data_ptr():
+                    g.copy_(p.grad)
+                else:
+                    continue
+                p.grad = g
+
+    def _grad_pairs(self):
+        off, named = 0, dict(self.named_parameters())
+        for k, s in self._specs:
+            n = 1
+            for d in s:
+                n *= d
+            yield named[k], self.flat_grad[off:off + n].view(s)
+            off += n
+
+    def forward_train(self, obs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (logits [N, A], values [N, 1]) attached to the autograd graph: ``loss.backward()``
+        adds the gradient into ``flat_grad`` -- every parameter's ``.grad`` is a view of it -- as
+        torch accumulates.  N above the training engine's batch runs in chunks, each chunk's
+        backward accumulating."""
+        if obs.device.type != "cuda" or self.flat.device.type != "cuda":
+            raise RuntimeError("ImpalaResNetModel.forward_train runs on the HIP path only (cuda device)")
+        if self._anchor is None:
+            self._anchor = torch.zeros((), device=self.flat.device, requires_grad=True)
+        return _ResnetGrad.apply(self._anchor, self, obs.contiguous())
 
     def forward(self, obs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         if obs.device.type != "cuda" or self.flat.device.type != "cuda":

@@ -1,5 +1,6 @@
 /* resnet_hip.h — C-ABI of the MI355X-native IMPALA ResNet actor-critic: the actor path (forward and
- * act) of the reference's AtariActorCritic over ImpalaCNNLarge (in libimpala_hip.so).
+ * act) and the backward pass of the reference's AtariActorCritic over ImpalaCNNLarge (in
+ * libimpala_hip.so).
  *
  * The reference (paths relative to the d3sm0/impala repository):
  *   body        models/common.py:11-83   ResidualBlock, ImpalaCNNBlock, ImpalaCNNLarge
@@ -38,7 +39,7 @@
 extern "C" {
 #endif
 
-#define RESNET_ABI_VERSION 1
+#define RESNET_ABI_VERSION 2
 
 #define RESNET_FEATURES 2048
 #define RESNET_HIDDEN 256
@@ -52,6 +53,8 @@ typedef struct resnet_config {
   int num_actions; /* 1..15 */
   int dtype;       /* IMPALA_DTYPE_F32 / IMPALA_DTYPE_BF16 */
   int debug;       /* 1: the trunk also stores its stage tensors (resnet_debug_read) */
+  int train;       /* 1: the handle also holds, for batch_size frames, what resnet_forward_train saves and
+                    *    the workspace of resnet_backward; fp32 only */
 } resnet_config;
 
 /* Stage tensors of the last forward (resnet_debug_read), per frame.  The body's are channels-last
@@ -73,8 +76,8 @@ int resnet_config_default(resnet_config* cfg);
 /* 630,352 for A = 15 */
 size_t resnet_param_count(int num_actions);
 
-/* Invalid configurations (batch_size < 1, num_actions outside [1, 15], unknown dtype, debug not 0 / 1)
- * are refused before any HIP call. */
+/* Invalid configurations (batch_size < 1, num_actions outside [1, 15], unknown dtype, debug or train not
+ * 0 / 1, train = 1 with bf16) are refused before any HIP call. */
 int resnet_create(const resnet_config* cfg, int device, resnet_actor** out);
 int resnet_destroy(resnet_actor* h);
 
@@ -93,6 +96,21 @@ int resnet_forward(resnet_actor* h, const uint8_t* obs, int n, float* logits, fl
 int resnet_act(resnet_actor* h, const uint8_t* obs, int n, const uint8_t* deterministic,
                int deterministic_all, uint64_t seed, uint64_t counter, int64_t* actions,
                float* logits, float* values, void* stream);
+
+/* Training (a handle created with train = 1).  resnet_forward_train is resnet_forward -- the same bits --
+ * and leaves in the handle what the backward reads: the 15 stage tensors, one byte per pooled element
+ * naming the window's winning tap 0..8 (row-major; of equal values the first), the LayerNorm's mean and
+ * rstd per frame, y, h and the projection's partial sums.
+ * resnet_backward writes (accumulate = 0) or adds with one fp32 rounding per element (accumulate = 1) the
+ * gradient of  sum dlogits * logits + sum dvalues * values  with respect to the flat parameters, in
+ * their order, to grad_flat [resnet_param_count] fp32.  dlogits [n][A], dvalues [n] fp32; obs and n are
+ * those of the handle's last resnet_forward_train, with no resnet_refresh_weights, resnet_forward or
+ * resnet_act on the handle since: another n, no such call, or a train = 0 handle is IMPALA_E_INVALID
+ * before any launch.  Sums over frames have one fixed order: equal inputs give equal bits. */
+int resnet_forward_train(resnet_actor* h, const uint8_t* obs, int n, float* logits, float* values,
+                         void* stream);
+int resnet_backward(resnet_actor* h, const uint8_t* obs, int n, const float* dlogits,
+                    const float* dvalues, float* grad_flat, int accumulate, void* stream);
 
 /* Test / inspection entry, valid on a handle created with debug = 1 only: the tensor `which`
  * (RESNET_DBG_*) as the last forward / act left it, its leading `bytes` copied to dst (device or
