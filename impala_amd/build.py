@@ -29,8 +29,8 @@ def hip_units():
     dqn_inplace.hip: the DQN step's three batch-reading kernels instantiated for a replay ring read in
     place, kept out likewise; iqn.hip: the kernels of the distributional (IQN) actor path and
     training step, kept out likewise; iqn_replay.hip: the two ingest kernels of the IQN learner's
-    device-side replay, kept out likewise; resnet.hip: the IMPALA ResNet actor path, kernels and
-    handle, kept out likewise)."""
+    device-side replay, kept out likewise; resnet.hip: the IMPALA ResNet, forward, act and backward, kernels and
+    handle, kept out likewise; of the other units' kernels it takes csrc/act_kernels.h's two)."""
     return [os.path.join(SRC_DIR, f)
             for f in ("impala.hip", "sac.hip", "dqn_replay.hip", "ppo_replay.hip", "dqn_inplace.hip",
                       "iqn.hip", "iqn_replay.hip", "resnet.hip")]

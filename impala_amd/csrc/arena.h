@@ -1,5 +1,6 @@
 // Workspace carving for the handles (create_learner, dqn_create, iqn_create, iqn_alloc_step, the
-// replay's buffers, sac.hip's carve).  Plain C++, no HIP: tests/arena_check.cpp compiles it alone.
+// replay's buffers, sac.hip's carve, resnet_layout.h's resnet_carve).  Plain C++, no HIP:
+// tests/arena_check.cpp compiles it alone.
 //
 // A handle's carve is one function that assigns its pointers straight from take() and is run
 // twice: on a null base, where every take() returns null and `used` ends at the bytes needed, and

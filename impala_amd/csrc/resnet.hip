@@ -9,7 +9,7 @@
 //   resnet_fc_kernel     Linear(2048, 256) split 16 (N tiles) x 8 (K chunks) over 128 workgroups,
 //                        each streaming its own 1/128 of the weights once; partial sums [8][n][256]
 //   resnet_heads_kernel  one wave per frame: the K chunks summed in order, bias, GELU, h, the heads
-//   act_heads_kernel / split_heads_kernel (kernels.h)
+//   act_heads_kernel / split_heads_kernel (act_kernels.h)
 //
 // Convolutions are implicit GEMMs D[oc][pixel] = sum_k W[oc][k] X[pixel][k], k = tap * Cin + ci:
 // the weights are the A operand (fragment-major in HBM, a wave's fragments in registers for the
@@ -22,41 +22,21 @@
 #include <string>
 
 #include "../../include/resnet_hip.h"
-#include "adam.h"
+#include "arena.h"
 #include "common.h"
-#include "conv1.h"
 #include "gemm.h"
-#include "head_math.h"
 #include "host.h"
 #include "net.h"
-#include "ops.h"
 
 namespace {
-// act_heads_kernel and split_heads_kernel, this unit's own copies (what kernels.h includes is
-// included above, at global scope)
-#include "kernels.h"
+// this unit's own copies of act_heads_kernel and split_heads_kernel, and the unit's layout (what the
+// two headers include is included above, at global scope)
+#include "act_kernels.h"
+#include "resnet_layout.h"
 
 constexpr int RN_THREADS = 512, RN_WAVES = 8;
-constexpr int RN_FEAT = RESNET_FEATURES, RN_HID = RESNET_HIDDEN;
-constexpr int RN_CONVS = 15;
-constexpr int RN_KSPLIT = 8, RN_KCHUNK = RN_FEAT / RN_KSPLIT;  // the FC's K chunks
-// fp32 side vector (floats): conv biases [15][32], LayerNorm affine in kernel order, bfc, wh, bh
-constexpr int RV_CB = 0, RV_LNG = RN_CONVS * 32, RV_LNB = RV_LNG + RN_FEAT, RV_BFC = RV_LNB + RN_FEAT,
-              RV_WH = RV_BFC + RN_HID, RV_BH = RV_WH + HEADS * RN_HID, RV_TOTAL = RV_BH + HEADS;
-// debug tensors: elements per frame of id 0..14, and the element offset of an id's block (x frames)
-__host__ __device__ constexpr int dbg_size(int id) { return id < 5 ? 32 * 32 * 16 : id < 10 ? 16 * 16 * 32 : 8 * 8 * 32; }
-__host__ __device__ constexpr int dbg_off(int id) {
-  return id < 5 ? id * 16384 : id < 10 ? 81920 + (id - 5) * 8192 : 122880 + (id - 10) * 2048;
-}
-constexpr int RN_DBG_FRAME = 133120;
-static_assert(dbg_off(14) + dbg_size(14) == RN_DBG_FRAME, "a frame's stage tensors");
-
-// geometry of conv `id` (5 per stage: the pooled conv, then conv0, conv1 of the two blocks)
-struct ConvGeo { int cin, cout; };
-constexpr ConvGeo conv_geo(int id) { return id == 0 ? ConvGeo{3, 16} : id < 5 ? ConvGeo{16, 16} : id == 5 ? ConvGeo{16, 32} : ConvGeo{32, 32}; }
-constexpr int kernel_cin(int cin) { return cin == 3 ? 4 : cin; }  // the stem's pixels are 4 bytes
+constexpr int RN_KCHUNK = RN_FEAT / RN_KSPLIT;
 template <typename T, int CIN> constexpr int conv_nks() { return (9 * CIN + Frag<T>::KSTEP - 1) / Frag<T>::KSTEP; }
-inline int conv_nks_rt(int cin, int kstep) { return (9 * cin + kstep - 1) / kstep; }
 
 // ---- LDS map (bytes) of one frame, T the compute type.  S1..S3: a stage's tensor with its halo.
 template <typename T> struct Lds {
@@ -82,20 +62,36 @@ struct TrunkArgs {
   int n, B;
   const void* w[RN_CONVS];  // fragment-major weights of the compute type
   const float* vecs;
-  void* y;    // [n][2048] compute type, kernel order p*32 + c
-  void* dbg;  // debug / train only
+  void* y;        // [n][2048] compute type, kernel order p*32 + c
+  void* stages;   // debug / train only: the stage tensors
+  uint8_t* amax;  // train only: the winning tap of every pooled element
+  float* lnstat;  // train only: (mean, rstd) of the LayerNorm per frame
 };
-// train only, behind dbg's B frames: the winning tap of every pooled element, then (mean, rstd) of the
-// LayerNorm per frame
-template <typename T> DEV uint8_t* train_amax(const TrunkArgs& a) {
-  return reinterpret_cast<uint8_t*>(a.dbg) + (size_t)a.B * RN_DBG_FRAME * sizeof(T);
-}
-// the pools' winning taps: bytes per frame, and a stage's offset in a frame's block ([HO][HO][C] each)
-constexpr int RN_AMAX_FRAME = 16384 + 8192 + 2048;
-__host__ __device__ constexpr int amax_off(int stage) { return stage == 0 ? 0 : stage == 1 ? 16384 : 24576; }
 
 DEV void lds_zero(char* p, int bytes) {
   for (int i = threadIdx.x * 16; i < bytes; i += RN_THREADS * 16) *reinterpret_cast<i32x4*>(p + i) = i32x4{0, 0, 0, 0};
+}
+
+// eight per-wave partial sums, in order
+DEV float sum8(const float* red) { return ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7])); }
+
+// frame f's image into img [66][66] (zeroed): bytes of three planes -> pixels (c0, c1, c2, 0) as dwords
+// inside the zero border
+DEV void load_image(const uint8_t* __restrict__ obs, int f, uint32_t* img) {
+  const int tid = threadIdx.x;
+  if (tid < 256) {
+    const int yy = tid >> 2, x0 = (tid & 3) * 16;
+    const uint8_t* src = obs + (size_t)f * 12288 + yy * 64 + x0;
+    const i32x4 p0 = *reinterpret_cast<const i32x4*>(src), p1 = *reinterpret_cast<const i32x4*>(src + 4096),
+                p2 = *reinterpret_cast<const i32x4*>(src + 8192);
+    uint32_t* dst = img + (yy + 1) * 66 + x0 + 1;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int sh = 8 * (j & 3);
+      dst[j] = (((uint32_t)p0[j >> 2] >> sh) & 255u) | ((((uint32_t)p1[j >> 2] >> sh) & 255u) << 8) |
+               ((((uint32_t)p2[j >> 2] >> sh) & 255u) << 16);
+    }
+  }
 }
 
 DEV f32x4 relu_v(f32x4 v) { return __builtin_elementwise_max(v, f32x4{0.f, 0.f, 0.f, 0.f}); }
@@ -294,12 +290,12 @@ DEV void res_blocks(T* x, T* t, const TrunkArgs& a, int id0, int f) {
                                   EpiStore<T, H, C>{t, a.vecs + RV_CB + 32 * i0});
     __syncthreads();
     if constexpr (DEBUG)
-      dump<T, H, C>(t, reinterpret_cast<T*>(a.dbg) + (size_t)a.B * dbg_off(i0) + (size_t)f * dbg_size(i0));
+      dump<T, H, C>(t, reinterpret_cast<T*>(a.stages) + stage_at(a.B, i0, f));
     conv_lds<T, C, C, H, H, true>(t, reinterpret_cast<const T*>(a.w[i1]), 0,
                                   EpiResidual<T, H, C>{x, a.vecs + RV_CB + 32 * i1});
     __syncthreads();
     if constexpr (DEBUG)
-      dump<T, H, C>(x, reinterpret_cast<T*>(a.dbg) + (size_t)a.B * dbg_off(i1) + (size_t)f * dbg_size(i1));
+      dump<T, H, C>(x, reinterpret_cast<T*>(a.stages) + stage_at(a.B, i1, f));
   }
 }
 
@@ -308,29 +304,17 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_trunk_kernel(const TrunkArg
   using L = Lds<T>;
   __shared__ __attribute__((aligned(16))) char lds[L::TOTAL];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  T* const dbg = reinterpret_cast<T*>(a.dbg);
   float* const red = reinterpret_cast<float*>(lds + L::RED);
   for (int f = blockIdx.x; f < a.n; f += gridDim.x) {
-    auto dbg_at = [&](int id) { return dbg + (size_t)a.B * dbg_off(id) + (size_t)f * dbg_size(id); };
-    // ---- the image: bytes of three planes -> pixels (c0, c1, c2, 0) inside a zero border
+    auto dbg_at = [&](int id) { return reinterpret_cast<T*>(a.stages) + stage_at(a.B, id, f); };
+    auto win_at = [&](int stage) { return TRAIN ? a.amax + (size_t)f * RN_AMAX_FRAME + amax_off(stage) : nullptr; };
+    // ---- the image
     T* x1 = reinterpret_cast<T*>(lds + L::X1);
     uint32_t* img = reinterpret_cast<uint32_t*>(lds + L::IMG_AT);
     lds_zero(lds + L::X1, L::S1);
     lds_zero(lds + L::IMG_AT, L::IMG);
     __syncthreads();
-    if (tid < 256) {
-      const int yy = tid >> 2, x0 = (tid & 3) * 16;
-      const uint8_t* src = a.obs + (size_t)f * 12288 + yy * 64 + x0;
-      const i32x4 p0 = *reinterpret_cast<const i32x4*>(src), p1 = *reinterpret_cast<const i32x4*>(src + 4096),
-                  p2 = *reinterpret_cast<const i32x4*>(src + 8192);
-      uint32_t* dst = img + (yy + 1) * 66 + x0 + 1;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int sh = 8 * (j & 3);
-        dst[j] = (((uint32_t)p0[j >> 2] >> sh) & 255u) | ((((uint32_t)p1[j >> 2] >> sh) & 255u) << 8) |
-                 ((((uint32_t)p2[j >> 2] >> sh) & 255u) << 16);
-      }
-    }
+    load_image(a.obs, f, img);
     __syncthreads();
     {  // ---- stem: conv 3 -> 16 at 64 x 64 in strips of 8 rows, pooled to x1 [32][32][16]
       float* strip = reinterpret_cast<float*>(lds + L::STRIP0_AT);
@@ -338,7 +322,7 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_trunk_kernel(const TrunkArg
         conv_stem<T, 8>(img, reinterpret_cast<const T*>(a.w[0]), r0,
                         EpiStrip<64, 16, 9>{strip, a.vecs + RV_CB, 1.f / 255.f});
         __syncthreads();
-        pool_rows<T, 64, 16, 8, TRAIN>(strip, x1, r0, TRAIN ? train_amax<T>(a) + (size_t)f * RN_AMAX_FRAME + amax_off(0) : nullptr);
+        pool_rows<T, 64, 16, 8, TRAIN>(strip, x1, r0, win_at(0));
         __syncthreads();
       }
     }
@@ -357,7 +341,7 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_trunk_kernel(const TrunkArg
         conv_lds<T, 16, 32, 32, 4, false>(x1, reinterpret_cast<const T*>(a.w[5]), r0,
                                           EpiStrip<32, 32, 5>{strip, a.vecs + RV_CB + 32 * 5, 1.f});
         __syncthreads();
-        pool_rows<T, 32, 32, 4, TRAIN>(strip, x2, r0, TRAIN ? train_amax<T>(a) + (size_t)f * RN_AMAX_FRAME + amax_off(1) : nullptr);
+        pool_rows<T, 32, 32, 4, TRAIN>(strip, x2, r0, win_at(1));
         __syncthreads();
       }
     }
@@ -377,7 +361,7 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_trunk_kernel(const TrunkArg
         conv_lds<T, 32, 32, 16, 8, false>(x2, reinterpret_cast<const T*>(a.w[10]), r0,
                                           EpiStrip<16, 32, 9>{strip, a.vecs + RV_CB + 32 * 10, 1.f});
         __syncthreads();
-        pool_rows<T, 16, 32, 8, TRAIN>(strip, x3, r0, TRAIN ? train_amax<T>(a) + (size_t)f * RN_AMAX_FRAME + amax_off(2) : nullptr);
+        pool_rows<T, 16, 32, 8, TRAIN>(strip, x3, r0, win_at(2));
         __syncthreads();
       }
     }
@@ -394,21 +378,18 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_trunk_kernel(const TrunkArg
       const float s = wave_sum((v[0] + v[1]) + (v[2] + v[3]));
       if (lane == 0) red[wave] = s;
       __syncthreads();
-      const float mean = (((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]))) *
-                         (1.f / RN_FEAT);
+      const float mean = sum8(red) * (1.f / RN_FEAT);
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] -= mean;
       const float sq = wave_sum((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
       if (lane == 0) red[8 + wave] = sq;
       __syncthreads();
-      const float var = (((red[8] + red[9]) + (red[10] + red[11])) + ((red[12] + red[13]) + (red[14] + red[15]))) *
-                        (1.f / RN_FEAT);
+      const float var = sum8(red + 8) * (1.f / RN_FEAT);
       const float rstd = 1.f / sqrtf(var + LN_EPS);
       if constexpr (TRAIN) {
         if (tid == 0) {
-          float* lnstat = reinterpret_cast<float*>(train_amax<T>(a) + (size_t)a.B * RN_AMAX_FRAME);
-          lnstat[2 * f] = mean;
-          lnstat[2 * f + 1] = rstd;
+          a.lnstat[2 * f] = mean;
+          a.lnstat[2 * f + 1] = rstd;
         }
       }
       float g[4], b[4], o[4];
@@ -468,7 +449,7 @@ __global__ __launch_bounds__(256) void resnet_heads_kernel(const float* __restri
 #pragma unroll
   for (int i = 0; i < RN_HID / 64; ++i) {
     const int j = lane + 64 * i;
-    float z = part[(size_t)f * RN_HID + j];
+    float z = part[(size_t)f * RN_HID + j];  // (resnet_head_bwd_kernel re-sums z in this order)
 #pragma unroll
     for (int ks = 1; ks < RN_KSPLIT; ++ks) z += part[((size_t)ks * B + f) * RN_HID + j];
     z += vecs[RV_BFC + j];
@@ -512,18 +493,14 @@ __global__ __launch_bounds__(256) void resnet_pack_fc_kernel(const float* __rest
   const int o = 16 * nt + (lane & 15), k = ks * RN_KCHUNK + s * F::KSTEP + (lane >> 4) * F::KPL + j;
   dst[e] = (T)w[(size_t)o * RN_FEAT + (k & 31) * 64 + (k >> 5)];
 }
-struct VecSrc {
-  int cb[RN_CONVS];  // offsets in the flat buffer
-  int lng, lnb, bfc, wa, ba, wc, bc;
-};
-__global__ __launch_bounds__(256) void resnet_pack_vec_kernel(const float* __restrict__ flat, const VecSrc o, int A,
+__global__ __launch_bounds__(256) void resnet_pack_vec_kernel(const float* __restrict__ flat, const GradOff o, int A,
                                                               float* __restrict__ vecs) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= RV_TOTAL) return;
   float v = 0.f;
   if (i < RV_LNG) {
     const int id = i >> 5, c = i & 31;
-    v = c < conv_geo(id).cout ? flat[o.cb[id] + c] : 0.f;
+    v = c < conv_geo(id).cout ? flat[o.b[id] + c] : 0.f;
   } else if (i < RV_BFC) {  // kernel order p*32 + c <- canonical c*64 + p
     const int k = (i - RV_LNG) & (RN_FEAT - 1);
     v = flat[(i < RV_LNB ? o.lng : o.lnb) + (k & 31) * 64 + (k >> 5)];
@@ -539,41 +516,19 @@ __global__ __launch_bounds__(256) void resnet_pack_vec_kernel(const float* __res
   vecs[i] = v;
 }
 
-size_t body_offsets(int (&w)[RN_CONVS], int (&b)[RN_CONVS]) {
-  size_t o = 0;
-  for (int id = 0; id < RN_CONVS; ++id) {
-    const ConvGeo g = conv_geo(id);
-    w[id] = (int)o; o += (size_t)g.cout * g.cin * 9;
-    b[id] = (int)o; o += g.cout;
-  }
-  return o;
-}
-
 #include "resnet_bwd.h"
 
 }  // namespace
 
-struct resnet_actor {
+struct resnet_actor : ResnetBufs {  // the buffers: one allocation, ws (resnet_carve)
   resnet_config cfg;
   int device, n_cu;
   const float* flat = nullptr;
   bool packed = false;
-  char* ws = nullptr;  // one allocation: everything below
-  void* w[RN_CONVS];
-  void* wfc;
-  float* vecs;
-  void* y;
-  float* part;
-  void* h;
-  float* heads;
-  void* dbg;
-  // train = 1 only (fp32): what resnet_forward_train saves beside dbg, and the backward's workspace
+  char* ws = nullptr;
+  // train = 1 only
   int trained_n = 0;  // frames of the last resnet_forward_train; 0: none, or the weights were refreshed since
-  int wg_groups = 0;  // frame groups of the weight-gradient kernels
-  uint8_t* amax;
-  float* lnstat;
-  float* wd[RN_CONVS];
-  float *wfct, *gz, *gy, *gws, *slab;
+  int wg_groups = 0;  // frame groups of the weight-gradient kernels (resnet_wg_groups)
 };
 
 namespace {
@@ -590,48 +545,29 @@ int check_ready(resnet_actor* h, const uint8_t* obs, int n) {
   return 0;
 }
 
-GradOff flat_offsets(int A) {
-  GradOff g;
-  size_t o = body_offsets(g.w, g.b);
-  g.lng = (int)o; o += RN_FEAT;
-  g.lnb = (int)o; o += RN_FEAT;
-  g.wfc = (int)o; o += (size_t)RN_HID * RN_FEAT;
-  g.bfc = (int)o; o += RN_HID;
-  g.wa = (int)o; o += (size_t)A * RN_HID;
-  g.ba = (int)o; o += A;
-  g.wc = (int)o; o += RN_HID;
-  g.bc = (int)o;
-  return g;
-}
-
 template <typename T> int launch_pack(resnet_actor* h, hipStream_t st) {
   const int A = h->cfg.num_actions;
   const GradOff go = flat_offsets(A);
-  const int* wo = go.w;
-  const size_t wfc = go.wfc;
-  VecSrc vs;
-  for (int id = 0; id < RN_CONVS; ++id) vs.cb[id] = go.b[id];
-  vs.lng = go.lng; vs.lnb = go.lnb; vs.bfc = go.bfc; vs.wa = go.wa; vs.ba = go.ba; vs.wc = go.wc; vs.bc = go.bc;
   for (int id = 0; id < RN_CONVS; ++id) {
     const ConvGeo g = conv_geo(id);
     const int ck = kernel_cin(g.cin), nks = conv_nks_rt(ck, Frag<T>::KSTEP);
     const int total = g.cout * nks * Frag<T>::KSTEP;
-    resnet_pack_conv_kernel<T><<<cdiv(total, 256), 256, 0, st>>>(h->flat + wo[id], (T*)h->w[id], g.cin, ck, nks, total);
+    resnet_pack_conv_kernel<T><<<cdiv(total, 256), 256, 0, st>>>(h->flat + go.w[id], (T*)h->w[id], g.cin, ck, nks, total);
     CK_LAUNCH("resnet_pack_conv");
   }
-  resnet_pack_fc_kernel<T><<<RN_HID * RN_FEAT / 256, 256, 0, st>>>(h->flat + wfc, (T*)h->wfc);
+  resnet_pack_fc_kernel<T><<<RN_HID * RN_FEAT / 256, 256, 0, st>>>(h->flat + go.wfc, (T*)h->wfc);
   CK_LAUNCH("resnet_pack_fc");
-  resnet_pack_vec_kernel<<<cdiv(RV_TOTAL, 256), 256, 0, st>>>(h->flat, vs, A, h->vecs);
+  resnet_pack_vec_kernel<<<cdiv(RV_TOTAL, 256), 256, 0, st>>>(h->flat, go, A, h->vecs);
   CK_LAUNCH("resnet_pack_vec");
   if constexpr (sizeof(T) == 4) {
     if (h->cfg.train) {  // the data gradients' layouts: taps flipped, Cin / Cout swapped; Wfc transposed
       for (int id = 1; id < RN_CONVS; ++id) {
         const ConvGeo g = conv_geo(id);
         const int total = g.cout * g.cin * 9;
-        resnet_pack_dgrad_kernel<<<cdiv(total, 256), 256, 0, st>>>(h->flat + wo[id], h->wd[id], g.cin, g.cout, total);
+        resnet_pack_dgrad_kernel<<<cdiv(total, 256), 256, 0, st>>>(h->flat + go.w[id], h->wd[id], g.cin, g.cout, total);
         CK_LAUNCH("resnet_pack_dgrad");
       }
-      resnet_pack_fct_kernel<<<RN_HID * RN_FEAT / 256, 256, 0, st>>>(h->flat + wfc, h->wfct);
+      resnet_pack_fct_kernel<<<RN_HID * RN_FEAT / 256, 256, 0, st>>>(h->flat + go.wfc, h->wfct);
       CK_LAUNCH("resnet_pack_fct");
     }
   }
@@ -646,7 +582,9 @@ template <typename T, bool TRAIN = false> int launch_forward(resnet_actor* h, co
   for (int id = 0; id < RN_CONVS; ++id) a.w[id] = h->w[id];
   a.vecs = h->vecs;
   a.y = h->y;
-  a.dbg = h->dbg;
+  a.stages = h->stages;
+  a.amax = h->amax;
+  a.lnstat = h->lnstat;
   h->trained_n = 0;  // this call rewrites y and the projection's sums
   const int grid = n < h->n_cu ? n : h->n_cu;
   if (TRAIN) resnet_trunk_kernel<T, true, TRAIN><<<grid, RN_THREADS, 0, st>>>(a);
@@ -664,7 +602,7 @@ int launch_backward(resnet_actor* h, const uint8_t* obs, int n, const float* dl,
                     hipStream_t st) {
   const int A = h->cfg.num_actions, B = h->cfg.batch_size;
   const GradOff go = flat_offsets(A);
-  const float* sav = (const float*)h->dbg;
+  const float* sav = (const float*)h->stages;
   resnet_head_bwd_kernel<<<cdiv(n, 4), 256, 0, st>>>(h->part, h->vecs, dl, dv, h->gz, n, B, A);
   CK_LAUNCH("resnet_head_bwd");
   resnet_head_wgrad_kernel<<<HEADS + 1, 256, 0, st>>>((const float*)h->h, h->gz, dl, dv, grad, go, n, A, acc);
@@ -673,7 +611,7 @@ int launch_backward(resnet_actor* h, const uint8_t* obs, int n, const float* dl,
   CK_LAUNCH("resnet_fc_wgrad");
   resnet_fc_dgrad_kernel<<<RN_FEAT / 16, 256, 0, st>>>(h->gz, h->wfct, h->gy, n);
   CK_LAUNCH("resnet_fc_dgrad");
-  resnet_ln_affine_kernel<<<RN_FEAT / 256, 256, 0, st>>>(h->gy, sav + (size_t)B * dbg_off(14), h->lnstat, grad, go.lng,
+  resnet_ln_affine_kernel<<<RN_FEAT / 256, 256, 0, st>>>(h->gy, sav + stage_at(B, 14, 0), h->lnstat, grad, go.lng,
                                                          go.lnb, n, acc);
   CK_LAUNCH("resnet_ln_affine");
   BwdArgs b;
@@ -732,10 +670,7 @@ int resnet_config_default(resnet_config* cfg) {
   return 0;
 }
 
-size_t resnet_param_count(int A) {
-  return (size_t)RESNET_BODY_PARAMS + 2 * RN_FEAT + (size_t)RN_HID * RN_FEAT + RN_HID + (size_t)A * RN_HID + A +
-         RN_HID + 1;
-}
+size_t resnet_param_count(int A) { return flat_total(A); }
 
 int resnet_create(const resnet_config* cfg, int device, resnet_actor** out) {
   if (!cfg || !out) return fail(IMPALA_E_INVALID, "null pointer");
@@ -755,65 +690,13 @@ int resnet_create(const resnet_config* cfg, int device, resnet_actor** out) {
   h->cfg = *cfg;
   h->device = device;
   h->n_cu = cu > 0 ? cu : 1;
-  const size_t es = elt(h), B = (size_t)cfg->batch_size;
-  const int kstep = es == 2 ? 32 : 16;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  size_t off = 0, wo[RN_CONVS];
-  for (int id = 0; id < RN_CONVS; ++id) {
-    const ConvGeo g = conv_geo(id);
-    wo[id] = off;
-    off = al(off + (size_t)g.cout * conv_nks_rt(kernel_cin(g.cin), kstep) * kstep * es);
-  }
-  const size_t o_wfc = off; off = al(off + (size_t)RN_HID * RN_FEAT * es);
-  const size_t o_vecs = off; off = al(off + (size_t)RV_TOTAL * 4);
-  const size_t o_y = off; off = al(off + B * RN_FEAT * es);
-  const size_t o_part = off; off = al(off + (size_t)RN_KSPLIT * B * RN_HID * 4);
-  const size_t o_h = off; off = al(off + B * RN_HID * es);
-  const size_t o_heads = off; off = al(off + B * HEADS * 4);
-  const size_t o_dbg = off;
-  if (cfg->debug || cfg->train) off = al(off + B * RN_DBG_FRAME * es);
-  // train: the pools' winning taps, the LayerNorm statistics, the data gradients' weights, gz, gy, the
-  // gradient at every conv's output, the weight gradients' partial sums per frame group
-  h->wg_groups = (int)(B < (size_t)(h->n_cu / 4) ? B : h->n_cu / 4 > 0 ? h->n_cu / 4 : 1);
-  size_t o_amax = 0, o_ln = 0, o_wd[RN_CONVS] = {}, o_wfct = 0, o_gz = 0, o_gy = 0, o_gws = 0, o_slab = 0;
-  if (cfg->train) {
-    o_amax = o_dbg + B * RN_DBG_FRAME * 4;  // (where the trunk looks for them: train_amax)
-    o_ln = o_amax + B * RN_AMAX_FRAME;
-    off = al(o_ln + B * 2 * 4);
-    for (int id = 1; id < RN_CONVS; ++id) {
-      const ConvGeo g = conv_geo(id);
-      o_wd[id] = off; off = al(off + (size_t)g.cout * g.cin * 9 * 4);
-    }
-    o_wfct = off; off = al(off + (size_t)RN_HID * RN_FEAT * 4);
-    o_gz = off; off = al(off + B * RN_HID * 4);
-    o_gy = off; off = al(off + B * RN_FEAT * 4);
-    o_gws = off; off = al(off + B * RN_DBG_FRAME * 4);
-    o_slab = off; off = al(off + (size_t)h->wg_groups * RESNET_BODY_PARAMS * 4);
-  }
-  const hipError_t e = hipMalloc((void**)&h->ws, off);
+  h->wg_groups = resnet_wg_groups(cfg->batch_size, h->n_cu);
+  const hipError_t e = hipMalloc((void**)&h->ws, resnet_carve(*h, *cfg, h->n_cu, Arena{}));
   if (e != hipSuccess) {
     delete h;
     return fail((int)e, std::string("hipMalloc: ") + hipGetErrorString(e));
   }
-  for (int id = 0; id < RN_CONVS; ++id) h->w[id] = h->ws + wo[id];
-  h->wfc = h->ws + o_wfc;
-  h->vecs = (float*)(h->ws + o_vecs);
-  h->y = h->ws + o_y;
-  h->part = (float*)(h->ws + o_part);
-  h->h = h->ws + o_h;
-  h->heads = (float*)(h->ws + o_heads);
-  h->dbg = cfg->debug || cfg->train ? h->ws + o_dbg : nullptr;
-  if (cfg->train) {
-    h->amax = (uint8_t*)(h->ws + o_amax);
-    h->lnstat = (float*)(h->ws + o_ln);
-    h->wd[0] = nullptr;
-    for (int id = 1; id < RN_CONVS; ++id) h->wd[id] = (float*)(h->ws + o_wd[id]);
-    h->wfct = (float*)(h->ws + o_wfct);
-    h->gz = (float*)(h->ws + o_gz);
-    h->gy = (float*)(h->ws + o_gy);
-    h->gws = (float*)(h->ws + o_gws);
-    h->slab = (float*)(h->ws + o_slab);
-  }
+  resnet_carve(*h, *cfg, h->n_cu, Arena{h->ws});
   *out = h;
   return 0;
 }
@@ -847,28 +730,27 @@ int resnet_refresh_weights(resnet_actor* h, void* stream) {
   return 0;
 }
 
-int resnet_forward(resnet_actor* h, const uint8_t* obs, int n, float* logits, float* values, void* stream) {
+// resnet_forward and, with `train`, resnet_forward_train.  (Here, behind resnet_refresh_weights, and the
+// TRAIN launch named last: the kernels lie in the code object in the order the templates are first used.)
+static int forward_entry(resnet_actor* h, const uint8_t* obs, int n, float* logits, float* values, void* stream, bool train) {
   if (int r = check_ready(h, obs, n)) return r;
   if (!logits || !values) return fail(IMPALA_E_INVALID, "null pointer");
+  if (train && !h->cfg.train) return fail(IMPALA_E_INVALID, "resnet_forward_train needs a handle created with train = 1");
   CK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  if (int r = RN_BY_TYPE(h, launch_forward, h, obs, n, st)) return r;
+  if (int r = !train ? RN_BY_TYPE(h, launch_forward, h, obs, n, st) : launch_forward<float, true>(h, obs, n, st)) return r;
   split_heads_kernel<<<cdiv((long)n * HEADS, 256), 256, 0, st>>>(h->heads, n, h->cfg.num_actions, logits, values);
   CK_LAUNCH("split_heads");
+  if (train) h->trained_n = n;
   return 0;
 }
 
+int resnet_forward(resnet_actor* h, const uint8_t* obs, int n, float* logits, float* values, void* stream) {
+  return forward_entry(h, obs, n, logits, values, stream, false);
+}
+
 int resnet_forward_train(resnet_actor* h, const uint8_t* obs, int n, float* logits, float* values, void* stream) {
-  if (int r = check_ready(h, obs, n)) return r;
-  if (!logits || !values) return fail(IMPALA_E_INVALID, "null pointer");
-  if (!h->cfg.train) return fail(IMPALA_E_INVALID, "resnet_forward_train needs a handle created with train = 1");
-  CK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (int r = launch_forward<float, true>(h, obs, n, st)) return r;
-  split_heads_kernel<<<cdiv((long)n * HEADS, 256), 256, 0, st>>>(h->heads, n, h->cfg.num_actions, logits, values);
-  CK_LAUNCH("split_heads");
-  h->trained_n = n;
-  return 0;
+  return forward_entry(h, obs, n, logits, values, stream, true);
 }
 
 int resnet_backward(resnet_actor* h, const uint8_t* obs, int n, const float* dlogits, const float* dvalues,
@@ -906,7 +788,7 @@ int resnet_debug_read(resnet_actor* h, int which, void* dst, size_t bytes, void*
   const char* src;
   size_t cap;
   if (which >= 0 && which < RESNET_DBG_STAGES) {
-    src = (const char*)h->dbg + B * dbg_off(which) * es;
+    src = (const char*)h->stages + stage_at((int)B, which, 0) * es;
     cap = B * dbg_size(which) * es;
   } else if (which == RESNET_DBG_Y) {
     src = (const char*)h->y; cap = B * RN_FEAT * es;

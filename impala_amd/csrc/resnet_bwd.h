@@ -21,24 +21,19 @@
 // No floating-point atomics: every sum over frames has one fixed order.
 #pragma once
 
-struct GradOff {  // offsets in the flat buffer (state_dict order)
-  int w[RN_CONVS], b[RN_CONVS];
-  int lng, lnb, wfc, bfc, wa, ba, wc, bc;
-};
-
 struct BwdArgs {
   int n, B;
   const float* wd[RN_CONVS];  // data-gradient weights of convs 1..14, fragment-major
   const float* vecs;
-  const float* sav;      // the 15 saved stage tensors, the debug layout
+  const float* sav;      // the handle's stages, amax, lnstat as resnet_forward_train left them
   const uint8_t* amax;
   const float* lnstat;
   const float* gy;       // [n][2048], kernel order
-  float* gws;            // the gradient at every conv's output (post-pool for 0, 5, 10), the debug layout
+  float* gws;            // the gradient at every conv's output (post-pool for 0, 5, 10), the stage tensors' layout
 };
 
-DEV const float* sav_at(const BwdArgs& a, int id, int f) { return a.sav + (size_t)a.B * dbg_off(id) + (size_t)f * dbg_size(id); }
-DEV float* gws_at(const BwdArgs& a, int id, int f) { return a.gws + (size_t)a.B * dbg_off(id) + (size_t)f * dbg_size(id); }
+DEV const float* sav_at(const BwdArgs& a, int id, int f) { return a.sav + stage_at(a.B, id, f); }
+DEV float* gws_at(const BwdArgs& a, int id, int f) { return a.gws + stage_at(a.B, id, f); }
 
 // d heads of frame f, output o: the logits' cotangent, the value's at VCOL, 0 between
 DEV float dhead(const float* __restrict__ dl, const float* __restrict__ dv, int A, int f, int o) {
@@ -57,7 +52,7 @@ __global__ __launch_bounds__(256) void resnet_head_bwd_kernel(const float* __res
 #pragma unroll
   for (int i = 0; i < RN_HID / 64; ++i) {
     const int j = lane + 64 * i;
-    float z = part[(size_t)f * RN_HID + j];
+    float z = part[(size_t)f * RN_HID + j];  // (resnet_heads_kernel's sum, term for term)
 #pragma unroll
     for (int ks = 1; ks < RN_KSPLIT; ++ks) z += part[((size_t)ks * B + f) * RN_HID + j];
     z += vecs[RV_BFC + j];
@@ -330,8 +325,7 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_trunk_bwd_kernel(const BwdA
         red[8 + wave] = s2;
       }
       __syncthreads();
-      const float m1 = (((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]))) * (1.f / RN_FEAT);
-      const float m2 = (((red[8] + red[9]) + (red[10] + red[11])) + ((red[12] + red[13]) + (red[14] + red[15]))) * (1.f / RN_FEAT);
+      const float m1 = sum8(red) * (1.f / RN_FEAT), m2 = sum8(red + 8) * (1.f / RN_FEAT);
       f32x4 v;
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] = x[q] > 0.f ? rstd * (gg[q] - m1 - xh[q] * m2) : 0.f;
@@ -420,24 +414,11 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_wgrad_kernel(const WgArgs a
   for (int f = blockIdx.x; f < a.n; f += gridDim.x) {
     __syncthreads();  // the previous frame's reads are done
     if constexpr (STEM) {
-      uint32_t* img = reinterpret_cast<uint32_t*>(in);
       lds_zero(reinterpret_cast<char*>(in), IN_FLOATS * 4);
       __syncthreads();
-      if (tid < 256) {
-        const int yy = tid >> 2, x0 = (tid & 3) * 16;
-        const uint8_t* src = a.obs + (size_t)f * 12288 + yy * 64 + x0;
-        const i32x4 p0 = *reinterpret_cast<const i32x4*>(src), p1 = *reinterpret_cast<const i32x4*>(src + 4096),
-                    p2 = *reinterpret_cast<const i32x4*>(src + 8192);
-        uint32_t* dst = img + (yy + 1) * 66 + x0 + 1;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const int sh = 8 * (j & 3);
-          dst[j] = (((uint32_t)p0[j >> 2] >> sh) & 255u) | ((((uint32_t)p1[j >> 2] >> sh) & 255u) << 8) |
-                   ((((uint32_t)p2[j >> 2] >> sh) & 255u) << 16);
-        }
-      }
+      load_image(a.obs, f, reinterpret_cast<uint32_t*>(in));
     } else {
-      const float* src = a.sav + (size_t)a.B * dbg_off(id - 1) + (size_t)f * dbg_size(id - 1);
+      const float* src = a.sav + stage_at(a.B, id - 1, f);
       for (int i = tid; i < P * P * CIN / 4; i += RN_THREADS) {
         const int c0 = 4 * (i % (CIN / 4)), px = (i / (CIN / 4)) % P, py = i / (CIN / 4 * P);
         f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -448,7 +429,7 @@ __global__ __launch_bounds__(RN_THREADS) void resnet_wgrad_kernel(const WgArgs a
         *reinterpret_cast<f32x4*>(in + (py * P + px) * CIN + c0) = v;
       }
     }
-    const float* gsrc = a.gws + (size_t)a.B * dbg_off(id) + (size_t)f * dbg_size(id);
+    const float* gsrc = a.gws + stage_at(a.B, id, f);
     for (int r0 = 0; r0 < H; r0 += R) {
       if (r0) __syncthreads();  // the previous strip's reads are done
       if constexpr (POOLED) {

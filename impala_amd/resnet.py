@@ -101,13 +101,15 @@ class ResnetEngine(_lib.NativeHandle):
                   "resnet_refresh_weights", _ERR)
             self._version = self.model._version
 
+    def _outputs(self, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        return torch.empty(n, self.A, device=self.device), torch.empty(n, 1, device=self.device)
+
     def forward(self, obs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (logits [n, A], values [n, 1]) on the device."""
         self._fresh()
         obs = obs.contiguous()
         n = obs.shape[0]
-        logits = torch.empty(n, self.A, device=self.device)
-        values = torch.empty(n, 1, device=self.device)
+        logits, values = self._outputs(n)
         check(lib().resnet_forward(self._h, _lib.ptr(obs), n, _lib.ptr(logits), _lib.ptr(values),
                                    _lib.stream_ptr(None)), "resnet_forward", _ERR)
         return logits, values
@@ -118,8 +120,7 @@ class ResnetEngine(_lib.NativeHandle):
         self._fresh()
         self._obs = obs.contiguous()  # the backward reads the frames again (the stem's gradient)
         n = self._obs.shape[0]
-        logits = torch.empty(n, self.A, device=self.device)
-        values = torch.empty(n, 1, device=self.device)
+        logits, values = self._outputs(n)
         check(lib().resnet_forward_train(self._h, _lib.ptr(self._obs), n, _lib.ptr(logits),
                                          _lib.ptr(values), _lib.stream_ptr(None)),
               "resnet_forward_train", _ERR)
@@ -162,8 +163,7 @@ class ResnetEngine(_lib.NativeHandle):
         else:
             det_all = int(bool(deterministic.item() if torch.is_tensor(deterministic) else deterministic))
         action = torch.empty(n, 1, dtype=torch.int64, device=self.device)
-        logits = torch.empty(n, self.A, device=self.device)
-        values = torch.empty(n, 1, device=self.device)
+        logits, values = self._outputs(n)
         check(lib().resnet_act(self._h, _lib.ptr(obs), n, _lib.ptr(det), det_all, int(seed),
                                int(counter), _lib.ptr(action), _lib.ptr(logits), _lib.ptr(values),
                                _lib.stream_ptr(None)), "resnet_act", _ERR)
@@ -280,13 +280,9 @@ class ImpalaResNetModel(FlatModule):
                 p.grad = g
 
     def _grad_pairs(self):
-        off, named = 0, dict(self.named_parameters())
-        for k, s in self._specs:
-            n = 1
-            for d in s:
-                n *= d
-            yield named[k], self.flat_grad[off:off + n].view(s)
-            off += n
+        named = dict(self.named_parameters())
+        for k, (off, n, shape) in self._views.items():
+            yield named[k], self.flat_grad[off:off + n].view(shape)
 
     def forward_train(self, obs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (logits [N, A], values [N, 1]) attached to the autograd graph: ``loss.backward()``
