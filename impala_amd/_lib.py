@@ -102,8 +102,10 @@ RESNET_EXPORTS = (
     "resnet_create", "resnet_destroy", "resnet_bind_params", "resnet_refresh_weights",
     "resnet_forward", "resnet_act", "resnet_debug_read", "resnet_forward_train", "resnet_backward",
 )
-RESNET_ABI_VERSION = 2
+RESNET_ABI_VERSION = 3
 RESNET_DBG_Y, RESNET_DBG_H, RESNET_DBG_HEADS = 15, 16, 17
+(RESNET_DBG_GRAD0, RESNET_DBG_GY, RESNET_DBG_GZ, RESNET_DBG_AMAX, RESNET_DBG_LNSTAT,
+ RESNET_DBG_PART) = 32, 47, 48, 49, 50, 51
 IQN_ABI_VERSION = 3
 IQN_DBG_DPRE, IQN_DBG_DX, IQN_DBG_COS = 100, 101, 102
 IQN_MAX_TAU = 32
@@ -188,7 +190,7 @@ class IqnConfig(C.Structure):
 
 class ResnetConfig(C.Structure):
     _fields_ = [("batch_size", C.c_int), ("num_actions", C.c_int), ("dtype", C.c_int),
-                ("debug", C.c_int), ("train", C.c_int)]
+                ("debug", C.c_int), ("train", C.c_int), ("train_dtype", C.c_int)]
 
 
 class IqnOptim(C.Structure):

@@ -559,17 +559,15 @@ template <typename T> int launch_pack(resnet_actor* h, hipStream_t st) {
   CK_LAUNCH("resnet_pack_fc");
   resnet_pack_vec_kernel<<<cdiv(RV_TOTAL, 256), 256, 0, st>>>(h->flat, go, A, h->vecs);
   CK_LAUNCH("resnet_pack_vec");
-  if constexpr (sizeof(T) == 4) {
-    if (h->cfg.train) {  // the data gradients' layouts: taps flipped, Cin / Cout swapped; Wfc transposed
-      for (int id = 1; id < RN_CONVS; ++id) {
-        const ConvGeo g = conv_geo(id);
-        const int total = g.cout * g.cin * 9;
-        resnet_pack_dgrad_kernel<<<cdiv(total, 256), 256, 0, st>>>(h->flat + go.w[id], h->wd[id], g.cin, g.cout, total);
-        CK_LAUNCH("resnet_pack_dgrad");
-      }
-      resnet_pack_fct_kernel<<<RN_HID * RN_FEAT / 256, 256, 0, st>>>(h->flat + go.wfc, h->wfct);
-      CK_LAUNCH("resnet_pack_fct");
+  if (h->cfg.train) {  // the data gradients' layouts: taps flipped, Cin / Cout swapped; Wfc transposed
+    for (int id = 1; id < RN_CONVS; ++id) {
+      const ConvGeo g = conv_geo(id);
+      const int nks = conv_nks_rt(g.cout, Frag<T>::KSTEP), total = g.cin * nks * Frag<T>::KSTEP;
+      resnet_pack_dgrad_kernel<T><<<cdiv(total, 256), 256, 0, st>>>(h->flat + go.w[id], (T*)h->wd[id], g.cin, g.cout, nks, total);
+      CK_LAUNCH("resnet_pack_dgrad");
     }
+    resnet_pack_fct_kernel<T><<<RN_HID * RN_FEAT / 256, 256, 0, st>>>(h->flat + go.wfc, h->wfct);
+    CK_LAUNCH("resnet_pack_fct");
   }
   return 0;
 }
@@ -598,56 +596,69 @@ template <typename T, bool TRAIN = false> int launch_forward(resnet_actor* h, co
   return 0;
 }
 
+// one weight-gradient launch: the fp32 or the bf16 kernel of the same geometry
+template <typename T, int CIN, int COUT, int H, int R, bool POOLED, bool RELU, bool STEM>
+void launch_wgrad(const WgArgs<T>& w, int G, int convs, int id0, hipStream_t st) {
+  if constexpr (sizeof(T) == 2)
+    resnet_wgrad_bf16_kernel<CIN, COUT, H, R, POOLED, RELU, STEM><<<dim3(G, convs), RN_THREADS, 0, st>>>(w, id0);
+  else
+    resnet_wgrad_kernel<CIN, COUT, H, R, POOLED, RELU, STEM><<<dim3(G, convs), RN_THREADS, 0, st>>>(w, id0);
+}
+
+template <typename T>
 int launch_backward(resnet_actor* h, const uint8_t* obs, int n, const float* dl, const float* dv, float* grad, int acc,
                     hipStream_t st) {
   const int A = h->cfg.num_actions, B = h->cfg.batch_size;
   const GradOff go = flat_offsets(A);
-  const float* sav = (const float*)h->stages;
+  const T* sav = (const T*)h->stages;
   resnet_head_bwd_kernel<<<cdiv(n, 4), 256, 0, st>>>(h->part, h->vecs, dl, dv, h->gz, n, B, A);
   CK_LAUNCH("resnet_head_bwd");
-  resnet_head_wgrad_kernel<<<HEADS + 1, 256, 0, st>>>((const float*)h->h, h->gz, dl, dv, grad, go, n, A, acc);
+  resnet_head_wgrad_kernel<T><<<HEADS + 1, 256, 0, st>>>((const T*)h->h, h->gz, dl, dv, grad, go, n, A, acc);
   CK_LAUNCH("resnet_head_wgrad");
-  resnet_fc_wgrad_kernel<<<16 * (RN_FEAT / 256), 256, 0, st>>>(h->gz, (const float*)h->y, grad, go.wfc, n, acc);
+  resnet_fc_wgrad_kernel<T><<<16 * (RN_FEAT / 256), 256, 0, st>>>(h->gz, (const T*)h->y, grad, go.wfc, n, acc);
   CK_LAUNCH("resnet_fc_wgrad");
   resnet_fc_dgrad_kernel<<<RN_FEAT / 16, 256, 0, st>>>(h->gz, h->wfct, h->gy, n);
   CK_LAUNCH("resnet_fc_dgrad");
-  resnet_ln_affine_kernel<<<RN_FEAT / 256, 256, 0, st>>>(h->gy, sav + stage_at(B, 14, 0), h->lnstat, grad, go.lng,
-                                                         go.lnb, n, acc);
+  resnet_ln_affine_kernel<T><<<RN_FEAT / 256, 256, 0, st>>>(h->gy, sav + stage_at(B, 14, 0), h->lnstat, grad, go.lng,
+                                                            go.lnb, n, acc);
   CK_LAUNCH("resnet_ln_affine");
-  BwdArgs b;
+  BwdArgs<T> b;
   b.n = n;
   b.B = B;
-  for (int id = 0; id < RN_CONVS; ++id) b.wd[id] = h->wd[id];
+  for (int id = 0; id < RN_CONVS; ++id) b.wd[id] = (const T*)h->wd[id];
   b.vecs = h->vecs;
   b.sav = sav;
   b.amax = h->amax;
   b.lnstat = h->lnstat;
   b.gy = h->gy;
-  b.gws = h->gws;
-  resnet_trunk_bwd_kernel<<<n < h->n_cu ? n : h->n_cu, RN_THREADS, 0, st>>>(b);
+  b.gws = (T*)h->gws;
+  if constexpr (sizeof(T) == 2)  // two workgroups a CU
+    resnet_trunk_bwd_bf16_kernel<<<n < 2 * h->n_cu ? n : 2 * h->n_cu, RN_THREADS, 0, st>>>(b);
+  else
+    resnet_trunk_bwd_kernel<<<n < h->n_cu ? n : h->n_cu, RN_THREADS, 0, st>>>(b);
   CK_LAUNCH("resnet_trunk_bwd");
-  WgArgs w;
+  WgArgs<T> w;
   w.obs = obs;
   w.n = n;
   w.B = B;
   w.sav = sav;
-  w.gws = h->gws;
+  w.gws = (const T*)h->gws;
   w.amax = h->amax;
   w.slab = h->slab;
   w.go = go;
   const int G = n < h->wg_groups ? n : h->wg_groups;
-  //                  CIN COUT  H  R  pooled relu  stem
-  resnet_wgrad_kernel<4, 16, 64, 8, true, false, true><<<dim3(G, 1), RN_THREADS, 0, st>>>(w, 0);
+  //             CIN COUT  H  R  pooled relu  stem
+  launch_wgrad<T, 4, 16, 64, 8, true, false, true>(w, G, 1, 0, st);
   CK_LAUNCH("resnet_wgrad stem");
-  resnet_wgrad_kernel<16, 16, 32, 8, false, true, false><<<dim3(G, 4), RN_THREADS, 0, st>>>(w, 1);
+  launch_wgrad<T, 16, 16, 32, 8, false, true, false>(w, G, 4, 1, st);
   CK_LAUNCH("resnet_wgrad stage 1");
-  resnet_wgrad_kernel<16, 32, 32, 8, true, false, false><<<dim3(G, 1), RN_THREADS, 0, st>>>(w, 5);
+  launch_wgrad<T, 16, 32, 32, 8, true, false, false>(w, G, 1, 5, st);
   CK_LAUNCH("resnet_wgrad conv 5");
-  resnet_wgrad_kernel<32, 32, 16, 16, false, true, false><<<dim3(G, 4), RN_THREADS, 0, st>>>(w, 6);
+  launch_wgrad<T, 32, 32, 16, 16, false, true, false>(w, G, 4, 6, st);
   CK_LAUNCH("resnet_wgrad stage 2");
-  resnet_wgrad_kernel<32, 32, 16, 16, true, false, false><<<dim3(G, 1), RN_THREADS, 0, st>>>(w, 10);
+  launch_wgrad<T, 32, 32, 16, 16, true, false, false>(w, G, 1, 10, st);
   CK_LAUNCH("resnet_wgrad conv 10");
-  resnet_wgrad_kernel<32, 32, 8, 8, false, true, false><<<dim3(G, 4), RN_THREADS, 0, st>>>(w, 11);
+  launch_wgrad<T, 32, 32, 8, 8, false, true, false>(w, G, 4, 11, st);
   CK_LAUNCH("resnet_wgrad stage 3");
   resnet_wreduce_kernel<<<cdiv(RESNET_BODY_PARAMS, 256), 256, 0, st>>>(h->slab, G, grad, acc);
   CK_LAUNCH("resnet_wreduce");
@@ -666,7 +677,7 @@ const char* resnet_last_error(void) { return impala_last_error(); }
 
 int resnet_config_default(resnet_config* cfg) {
   if (!cfg) return fail(IMPALA_E_INVALID, "null config");
-  *cfg = resnet_config{128, RESNET_MAX_ACTIONS, IMPALA_DTYPE_F32, 0, 0};
+  *cfg = resnet_config{128, RESNET_MAX_ACTIONS, IMPALA_DTYPE_F32, 0, 0, IMPALA_DTYPE_F32};
   return 0;
 }
 
@@ -680,8 +691,10 @@ int resnet_create(const resnet_config* cfg, int device, resnet_actor** out) {
   if (cfg->dtype != IMPALA_DTYPE_F32 && cfg->dtype != IMPALA_DTYPE_BF16) return fail(IMPALA_E_INVALID, "unknown dtype");
   if (cfg->debug != 0 && cfg->debug != 1) return fail(IMPALA_E_INVALID, "debug must be 0 or 1");
   if (cfg->train != 0 && cfg->train != 1) return fail(IMPALA_E_INVALID, "train must be 0 or 1");
-  if (cfg->train && cfg->dtype != IMPALA_DTYPE_F32)
-    return fail(IMPALA_E_INVALID, "train = 1 needs dtype fp32: the backward pass is fp32 only");
+  if (cfg->train_dtype != IMPALA_DTYPE_F32 && cfg->train_dtype != IMPALA_DTYPE_BF16)
+    return fail(IMPALA_E_INVALID, "unknown train_dtype");
+  if (cfg->train && cfg->train_dtype != cfg->dtype)
+    return fail(IMPALA_E_INVALID, "train = 1 needs train_dtype == dtype: resnet_forward_train is resnet_forward, the same bits");
   CK(hipSetDevice(device));
   int cu = 0;
   CK(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device));
@@ -738,7 +751,10 @@ static int forward_entry(resnet_actor* h, const uint8_t* obs, int n, float* logi
   if (train && !h->cfg.train) return fail(IMPALA_E_INVALID, "resnet_forward_train needs a handle created with train = 1");
   CK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  if (int r = !train ? RN_BY_TYPE(h, launch_forward, h, obs, n, st) : launch_forward<float, true>(h, obs, n, st)) return r;
+  if (int r = !train                                ? RN_BY_TYPE(h, launch_forward, h, obs, n, st)
+              : h->cfg.dtype == IMPALA_DTYPE_BF16 ? launch_forward<__bf16, true>(h, obs, n, st)
+                                                  : launch_forward<float, true>(h, obs, n, st))
+    return r;
   split_heads_kernel<<<cdiv((long)n * HEADS, 256), 256, 0, st>>>(h->heads, n, h->cfg.num_actions, logits, values);
   CK_LAUNCH("split_heads");
   if (train) h->trained_n = n;
@@ -764,7 +780,7 @@ int resnet_backward(resnet_actor* h, const uint8_t* obs, int n, const float* dlo
   if (!dlogits || !dvalues || !grad_flat) return fail(IMPALA_E_INVALID, "null pointer");
   if (accumulate != 0 && accumulate != 1) return fail(IMPALA_E_INVALID, "accumulate must be 0 or 1");
   CK(hipSetDevice(h->device));
-  return launch_backward(h, obs, n, dlogits, dvalues, grad_flat, accumulate, (hipStream_t)stream);
+  return RN_BY_TYPE(h, launch_backward, h, obs, n, dlogits, dvalues, grad_flat, accumulate, (hipStream_t)stream);
 }
 
 int resnet_act(resnet_actor* h, const uint8_t* obs, int n, const uint8_t* deterministic, int deterministic_all,
@@ -782,7 +798,8 @@ int resnet_act(resnet_actor* h, const uint8_t* obs, int n, const uint8_t* determ
 
 int resnet_debug_read(resnet_actor* h, int which, void* dst, size_t bytes, void* stream) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
-  if (!h->cfg.debug) return fail(IMPALA_E_INVALID, "resnet_debug_read needs a handle created with debug = 1");
+  if (!h->cfg.debug && !h->cfg.train)
+    return fail(IMPALA_E_INVALID, "resnet_debug_read needs a handle created with debug = 1 or train = 1");
   if (!dst) return fail(IMPALA_E_INVALID, "null pointer");
   const size_t es = elt(h), B = (size_t)h->cfg.batch_size;
   const char* src;
@@ -796,6 +813,21 @@ int resnet_debug_read(resnet_actor* h, int which, void* dst, size_t bytes, void*
     src = (const char*)h->h; cap = B * RN_HID * es;
   } else if (which == RESNET_DBG_HEADS) {
     src = (const char*)h->heads; cap = B * HEADS * 4;
+  } else if (which >= RESNET_DBG_GRAD0 && which <= RESNET_DBG_PART && !h->cfg.train) {
+    return fail(IMPALA_E_INVALID, "the backward's tensors need a handle created with train = 1");
+  } else if (which >= RESNET_DBG_GRAD0 && which < RESNET_DBG_GRAD0 + RN_CONVS) {
+    src = (const char*)h->gws + stage_at((int)B, which - RESNET_DBG_GRAD0, 0) * es;
+    cap = B * dbg_size(which - RESNET_DBG_GRAD0) * es;
+  } else if (which == RESNET_DBG_GY) {
+    src = (const char*)h->gy; cap = B * RN_FEAT * 4;
+  } else if (which == RESNET_DBG_GZ) {
+    src = (const char*)h->gz; cap = B * RN_HID * 4;
+  } else if (which == RESNET_DBG_AMAX) {
+    src = (const char*)h->amax; cap = B * RN_AMAX_FRAME;
+  } else if (which == RESNET_DBG_LNSTAT) {
+    src = (const char*)h->lnstat; cap = B * 2 * 4;
+  } else if (which == RESNET_DBG_PART) {
+    src = (const char*)h->part; cap = (size_t)RN_KSPLIT * B * RN_HID * 4;
   } else {
     return fail(IMPALA_E_INVALID, "unknown debug tensor");
   }

@@ -82,13 +82,16 @@ struct ResnetBufs {
   void* h;            // [B][256] T
   float* heads;       // [B][16]
   void* stages;       // debug or train: the stage tensors [15][B][H][H][C] T
-  // train only (fp32): the pools' winning taps [B][RN_AMAX_FRAME], (mean, rstd) [B][2], the data
-  // gradients' weights of convs 1..14, Wfc transposed, gz [B][256], gy [B][2048], the gradient at every
-  // conv's output (the stage tensors' layout), the weight gradients' partial sums per frame group
+  // train only: the pools' winning taps [B][RN_AMAX_FRAME], (mean, rstd) [B][2], the data gradients'
+  // weights of convs 1..14 (T, fragment-major), Wfc transposed (fp32, in bf16 mode the rounded values),
+  // gz [B][256], gy [B][2048], the gradient at every conv's output (T, the stage tensors' layout), the
+  // weight gradients' partial sums per frame group
   uint8_t* amax;
   float* lnstat;
-  float* wd[RN_CONVS];
-  float *wfct, *gz, *gy, *gws, *slab;
+  void* wd[RN_CONVS];
+  float *wfct, *gz, *gy;
+  void* gws;
+  float* slab;
 };
 // frame groups of the weight-gradient kernels
 inline int resnet_wg_groups(int B, int n_cu) { return B < n_cu / 4 ? B : n_cu / 4 > 0 ? n_cu / 4 : 1; }
@@ -112,11 +115,12 @@ inline size_t resnet_carve(ResnetBufs& b, const resnet_config& cfg, int n_cu, Ar
   if (cfg.train) {
     b.amax = (uint8_t*)a.take(B * RN_AMAX_FRAME);
     b.lnstat = F(B * 2 * 4);
-    for (int id = 1; id < RN_CONVS; ++id) b.wd[id] = F((size_t)conv_geo(id).cout * conv_geo(id).cin * 9 * 4);
+    for (int id = 1; id < RN_CONVS; ++id)  // rows cin, K = 9 cout up to whole K-steps
+      b.wd[id] = a.take((size_t)conv_geo(id).cin * conv_nks_rt(conv_geo(id).cout, kstep) * kstep * es);
     b.wfct = F((size_t)RN_HID * RN_FEAT * 4);
     b.gz = F(B * RN_HID * 4);
     b.gy = F(B * RN_FEAT * 4);
-    b.gws = F(B * RN_DBG_FRAME * 4);
+    b.gws = a.take(B * RN_DBG_FRAME * es);
     b.slab = F(groups * RESNET_BODY_PARAMS * 4);
   }
   return Arena::align(a.used);

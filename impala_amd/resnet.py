@@ -2,7 +2,7 @@
 ``AtariActorCritic`` (models/models.py:61-76) with ``ImpalaCNNLarge`` (models/common.py:11-83) as
 its body -- the actor path, ``forward`` and ``act``, and the backward pass:
 ``forward_train`` returns outputs attached to the autograd graph, and ``loss.backward()`` runs
-``resnet_backward`` into ``model.flat_grad``.  Every compute entry is one call of
+``resnet_backward`` into ``model.flat_grad``, in fp32 or (``train_dtype="bf16"``) in bf16.  Every compute entry is one call of
 include/resnet_hip.h; the compute path is the HIP library only.  The one-call learner step (loss
 head, clip and Adam fused) is not built, so there is no ``conf/`` entry for this network yet.
 """
@@ -59,6 +59,10 @@ def resnet_init_flat(action_dim: int) -> torch.Tensor:
     return torch.cat([t.detach().reshape(-1) for l in layers for t in (l.weight, l.bias)])
 
 
+def _stage_shape(i: int) -> Tuple[int, int, int]:
+    return (32, 32, 16) if i < 5 else (16, 16, 32) if i < 10 else (8, 8, 32)
+
+
 def default_config() -> _lib.ResnetConfig:
     cfg = _lib.ResnetConfig()
     check(lib().resnet_config_default(C.byref(cfg)), "resnet_config_default", _ERR)
@@ -71,10 +75,17 @@ class ResnetEngine(_lib.NativeHandle):
     # name -> (debug tensor id, element kind, shape of one frame); the body's stage tensors are
     # channels-last [H, H, C], "y" in the kernel order p*32 + c
     DEBUG_TENSORS = dict(
-        [(f"s{i}", (i, "T", (32, 32, 16) if i < 5 else (16, 16, 32) if i < 10 else (8, 8, 32)))
-         for i in range(15)],
+        [(f"s{i}", (i, "T", _stage_shape(i))) for i in range(15)],
         y=(_lib.RESNET_DBG_Y, "T", (FEATURES,)), h=(_lib.RESNET_DBG_H, "T", (HIDDEN,)),
         heads=(_lib.RESNET_DBG_HEADS, "f32", (16,)))
+    # a ``train=True`` engine after a ``backward``: the gradient at every convolution's output (at its
+    # pool's output for 0, 5, 10), at y and at the pre-GELU z, the pools' winning taps, the LayerNorm's
+    # (mean, rstd); "part" is not per frame: the whole [8, batch_size, 256] (``frames=None``)
+    TRAIN_TENSORS = dict(
+        [(f"g{i}", (_lib.RESNET_DBG_GRAD0 + i, "T", _stage_shape(i))) for i in range(15)],
+        gy=(_lib.RESNET_DBG_GY, "f32", (FEATURES,)), gz=(_lib.RESNET_DBG_GZ, "f32", (HIDDEN,)),
+        amax=(_lib.RESNET_DBG_AMAX, "u32", ((16384 + 8192 + 2048) // 4,)),
+        lnstat=(_lib.RESNET_DBG_LNSTAT, "f32", (2,)), part=(_lib.RESNET_DBG_PART, "f32", (8 * HIDDEN,)))
 
     def __init__(self, model: "ImpalaResNetModel", batch_size: int = 128,
                  dtype: Optional[str] = None, debug: bool = False, train: bool = False):
@@ -89,6 +100,7 @@ class ResnetEngine(_lib.NativeHandle):
         cfg = default_config()
         cfg.batch_size, cfg.num_actions = int(batch_size), model.action_dim
         cfg.dtype, cfg.debug, cfg.train = (1 if dtype == "bf16" else 0), int(bool(debug)), int(bool(train))
+        cfg.train_dtype = cfg.dtype if train else 0  # forward_train is forward, the same bits
         self.N, self.A, self.bf16 = cfg.batch_size, cfg.num_actions, dtype == "bf16"
         self._open("resnet_create", C.byref(cfg), self.device_index(self.device))
         check(lib().resnet_bind_params(self._h, _lib.ptr(model.flat)), "resnet_bind_params", _ERR)
@@ -170,11 +182,14 @@ class ResnetEngine(_lib.NativeHandle):
         return action, logits, values
 
     def debug_tensor(self, name: str, frames: Optional[int] = None):
-        """The tensor ``name`` of the last forward / act (``resnet_debug_read``; a host sync; a
-        handle created with ``debug=True``) as a float32 numpy array [frames, ...]."""
-        if name not in self.DEBUG_TENSORS:
-            raise ValueError(f"unknown debug tensor {name!r}: one of {sorted(self.DEBUG_TENSORS)}")
-        which, kind, shape = self.DEBUG_TENSORS[name]
+        """The tensor ``name`` of the last forward / act or, the g* and the names after them, of the
+        last ``backward`` (``resnet_debug_read``; a host sync; a handle created with ``debug=True``
+        or ``train=True``) as a float32 numpy array [frames, ...]; "amax" as uint32 words of four
+        bytes each (``.view(np.uint8)``)."""
+        known = {**self.DEBUG_TENSORS, **self.TRAIN_TENSORS}
+        if name not in known:
+            raise ValueError(f"unknown debug tensor {name!r}: one of {sorted(known)}")
+        which, kind, shape = known[name]
         n = self.N if frames is None else int(frames)
         if not 1 <= n <= self.N:
             raise ValueError(f"frames must be in [1, {self.N}]")
@@ -219,7 +234,8 @@ class ImpalaResNetModel(FlatModule):
     (models/distributed_models.py:21-32) through ``resnet_act``."""
 
     def __init__(self, obs_shape: Tuple[int, ...] = OBS_SHAPE, n_act: int = 15, device="cuda",
-                 dtype: Optional[str] = None, seed: Optional[int] = None, train_batch: int = 160):
+                 dtype: Optional[str] = None, seed: Optional[int] = None, train_batch: int = 160,
+                 train_dtype: str = "fp32"):
         super().__init__()
         if tuple(obs_shape) != OBS_SHAPE:
             # models/common.py:81-83 hard-codes output_dim 2048 => 64x64x3 only
@@ -228,6 +244,9 @@ class ImpalaResNetModel(FlatModule):
             raise ValueError("n_act must be in [1, 15]")
         self.action_dim = int(n_act)
         self.compute_dtype = dtype or "fp32"
+        if train_dtype not in ("fp32", "bf16"):
+            raise ValueError("train_dtype: 'fp32' or 'bf16'")
+        self.train_dtype = train_dtype  # of forward_train / loss.backward(), whatever forward and act run in
         self._specs = param_specs(self.action_dim)
         self._views, = self._attach_segments(torch.device(device))
         self._infer_engine = None
@@ -258,12 +277,17 @@ class ImpalaResNetModel(FlatModule):
         N = N or self._engine().N
         return [x[i:i + N] for i in range(0, x.shape[0], N)]
 
-    def train_engine(self, batch_size: Optional[int] = None) -> ResnetEngine:
-        """The training engine (fp32); with ``batch_size``, one of that many frames a chunk."""
+    def train_engine(self, batch_size: Optional[int] = None, dtype: Optional[str] = None) -> ResnetEngine:
+        """The training engine, of ``train_dtype``; with ``batch_size`` or ``dtype``, one of that
+        many frames a chunk or of that type from here on."""
+        if dtype is not None and dtype != self.train_dtype:
+            if dtype not in ("fp32", "bf16"):
+                raise ValueError("dtype: 'fp32' or 'bf16'")
+            self.train_dtype, self._train_engine = dtype, None
         if batch_size is not None and int(batch_size) != self._train_batch:
             self._train_batch, self._train_engine = int(batch_size), None
         if self._train_engine is None:
-            self._train_engine = ResnetEngine(self, self._train_batch, "fp32", train=True)
+            self._train_engine = ResnetEngine(self, self._train_batch, self.train_dtype, train=True)
         return self._train_engine
 
     def _bind_grads(self) -> None:
@@ -321,4 +345,4 @@ class ImpalaResNetModel(FlatModule):
 
     def clone_to(self, device) -> "ImpalaResNetModel":
         return self._frozen_clone(ImpalaResNetModel(OBS_SHAPE, self.action_dim, device=device,
-                                                    dtype=self.compute_dtype))
+                                                    dtype=self.compute_dtype, train_dtype=self.train_dtype))

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define RESNET_ABI_VERSION 2
+#define RESNET_ABI_VERSION 3
 
 #define RESNET_FEATURES 2048
 #define RESNET_HIDDEN 256
@@ -54,7 +54,9 @@ typedef struct resnet_config {
   int dtype;       /* IMPALA_DTYPE_F32 / IMPALA_DTYPE_BF16 */
   int debug;       /* 1: the trunk also stores its stage tensors (resnet_debug_read) */
   int train;       /* 1: the handle also holds, for batch_size frames, what resnet_forward_train saves and
-                    *    the workspace of resnet_backward; fp32 only */
+                    *    the workspace of resnet_backward */
+  int train_dtype; /* the type of resnet_forward_train / resnet_backward; train = 1 needs train_dtype == dtype
+                    *    (resnet_forward_train is resnet_forward, the same bits).  Default fp32. */
 } resnet_config;
 
 /* Stage tensors of the last forward (resnet_debug_read), per frame.  The body's are channels-last
@@ -69,6 +71,20 @@ typedef struct resnet_config {
 #define RESNET_DBG_Y 15
 #define RESNET_DBG_H 16
 #define RESNET_DBG_HEADS 17
+/* On a handle created with train = 1 (debug = 1 is not needed), after a resnet_backward, what the backward
+ * computed and read; ids 0..17 are valid on such a handle too (as the last resnet_forward_train left them):
+ *   32 + id      the gradient at convolution id's output (at its pool's output for 0, 5, 10): stage tensor
+ *                id's layout, the compute type
+ *   GY           the gradient at y [2048] fp32, kernel order;  GZ  at the pre-GELU z [256] fp32
+ *   AMAX         the pools' winning taps, u8: [32][32][16], [16][16][32], [8][8][32] per frame
+ *   LNSTAT       the LayerNorm's (mean, rstd) fp32 per frame
+ *   PART         the projection's partial sums fp32, not per frame: the whole [8][batch_size][256] */
+#define RESNET_DBG_GRAD0 32
+#define RESNET_DBG_GY 47
+#define RESNET_DBG_GZ 48
+#define RESNET_DBG_AMAX 49
+#define RESNET_DBG_LNSTAT 50
+#define RESNET_DBG_PART 51
 
 int resnet_abi_version(void);
 const char* resnet_last_error(void);
@@ -77,7 +93,7 @@ int resnet_config_default(resnet_config* cfg);
 size_t resnet_param_count(int num_actions);
 
 /* Invalid configurations (batch_size < 1, num_actions outside [1, 15], unknown dtype, debug or train not
- * 0 / 1, train = 1 with bf16) are refused before any HIP call. */
+ * 0 / 1, train = 1 with train_dtype != dtype) are refused before any HIP call. */
 int resnet_create(const resnet_config* cfg, int device, resnet_actor** out);
 int resnet_destroy(resnet_actor* h);
 
@@ -97,7 +113,8 @@ int resnet_act(resnet_actor* h, const uint8_t* obs, int n, const uint8_t* determ
                int deterministic_all, uint64_t seed, uint64_t counter, int64_t* actions,
                float* logits, float* values, void* stream);
 
-/* Training (a handle created with train = 1).  resnet_forward_train is resnet_forward -- the same bits --
+/* Training (a handle created with train = 1), in fp32 or -- bf16 operands, saved tensors and gradients
+ * between the layers, fp32 accumulation and fp32 grad_flat -- in bf16.  resnet_forward_train is resnet_forward -- the same bits --
  * and leaves in the handle what the backward reads: the 15 stage tensors, one byte per pooled element
  * naming the window's winning tap 0..8 (row-major; of equal values the first), the LayerNorm's mean and
  * rstd per frame, y, h and the projection's partial sums.
@@ -112,7 +129,7 @@ int resnet_forward_train(resnet_actor* h, const uint8_t* obs, int n, float* logi
 int resnet_backward(resnet_actor* h, const uint8_t* obs, int n, const float* dlogits,
                     const float* dvalues, float* grad_flat, int accumulate, void* stream);
 
-/* Test / inspection entry, valid on a handle created with debug = 1 only: the tensor `which`
+/* Test / inspection entry, valid on a handle created with debug = 1 or train = 1: the tensor `which`
  * (RESNET_DBG_*) as the last forward / act left it, its leading `bytes` copied to dst (device or
  * host) on `stream`; bytes in (0, batch_size frames]. */
 int resnet_debug_read(resnet_actor* h, int which, void* dst, size_t bytes, void* stream);

@@ -191,7 +191,29 @@ def act1_lds_stores(LDA1, es=2):
     return out
 
 
+def resnet_wgrad_tr_reads(C, H, dealt=True, tap=4, half=0, es=2):
+    """resnet_wgrad_bf16_kernel's operand reads from a channels-last halo tensor [H+2][H+2][C] at a
+    tap's offset (the gradient strip is the same pattern without the halo): the two
+    ds_read_b64_tr_b16 of every K-step of 32 pixels of 8 image rows.  dealt: lane group grp takes
+    pixels 4 grp .. and 16 + 4 grp .. (the kernel); else 8 grp .. 8 grp + 7 (lds_frag_k's order)."""
+    out, P = [], H + 2
+    for k in range(8 * H // 32):
+        for rd in range(2):
+            addrs = []
+            for lane in range(64):
+                grp, rq, pp = lane >> 4, (lane & 15) >> 2, lane & 3
+                pl = 32 * k + (4 * grp + rq + 16 * rd if dealt else 8 * grp + rq + 4 * rd)
+                pix = (pl // H + tap // 3) * P + pl % H + tap % 3
+                addrs.append((pix * C + 16 * half + 4 * pp) * es)
+            out.append(addrs)
+    return out
+
+
 if __name__ == "__main__":
+    for C, H in ((16, 32), (32, 16), (32, 8)):
+        for dealt in (False, True):
+            reads = [a for tap in range(9) for half in range(C // 16) for a in resnet_wgrad_tr_reads(C, H, dealt, tap, half)]
+            print(report(f"resnet wgrad C {C} H {H} {'dealt' if dealt else 'lds_frag_k order'}", "ds_read_b64_tr_b16", reads))
     for LDI in (48, 52, 56, 60, 64, 72, 80, 88):
         print(f"--- LDI {LDI}")
         print(report("stash frame", "ds_write_b64", stash_writes(LDI)))

@@ -1,18 +1,19 @@
 #!/usr/bin/env python3
 """What the ResNet's forward_train + backward costs on the HIP path, with the same network in torch
-float32 on the device beside it (profiles/resnet_backward).
+float32 on the device beside it (profiles/resnet_backward, profiles/resnet_backward_bf16).
 
 Per n (160: the IMPALA config's 8 x 20 frames; 1280: 64 x 20), observations already in HBM, A = 15,
 standard-normal cotangents:
-  hip    device-event ms per ``ResnetEngine.forward_train`` + ``backward`` of --steps back-to-back calls
+  hip    device-event ms per ``ResnetEngine.forward_train`` + ``backward`` of --steps back-to-back calls,
+         one path per --dtype: ``hip`` the fp32 engine, ``hip_bf16`` the bf16 one
   torch  the yardstick: the network restated with tests/resnet_oracle.py's functions on float32
          device tensors, forward + ``torch.autograd.grad``, timed the same way
 in --runs alternating runs; ``spread`` is (max - min) / min over a path's runs.  One JSON line per n.
-With --once hip|torch that path runs alone at --n, --steps calls after the warm-up, for a kernel
+With --once hip|hip_bf16|torch that path runs alone at --n, --steps calls after the warm-up, for a kernel
 trace of its own.
 
 usage: python tools/resnet_grad_time.py [--steps 20] [--warmup 5] [--runs 3] [--n 160 1280]
-                                        [--once hip|torch] [--out FILE]"""
+                                        [--dtype fp32 bf16] [--once hip|hip_bf16|torch] [--out FILE]"""
 import argparse
 import json
 import os
@@ -61,7 +62,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--n", type=int, nargs="+", default=[160, 1280])
-    ap.add_argument("--once", default=None, choices=("hip", "torch"))
+    ap.add_argument("--dtype", nargs="+", default=["fp32"], choices=("fp32", "bf16"))
+    ap.add_argument("--once", default=None, choices=("hip", "hip_bf16", "torch"))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -74,13 +76,18 @@ def main():
         obs = torch.randint(0, 256, (n, 3, 64, 64), dtype=torch.uint8, device=dev, generator=gen)
         dl = torch.randn(n, A, device=dev, generator=gen)
         dv = torch.randn(n, device=dev, generator=gen)
-        eng = ResnetEngine(model, n, "fp32", train=True)
         grad = torch.empty_like(model.flat)
 
-        def hip():
-            eng.forward_train(obs)
-            eng.backward(dl, dv, out=grad)
-        paths = {"hip": hip, "torch": torch_step(P, obs, dl, dv)}
+        def hip(dtype):
+            eng = ResnetEngine(model, n, dtype, train=True)
+
+            def step():
+                eng.forward_train(obs)
+                eng.backward(dl, dv, out=grad)
+            return step
+        dtypes = args.dtype + (["bf16"] if args.once == "hip_bf16" and "bf16" not in args.dtype else [])
+        paths = {"hip" if d == "fp32" else "hip_bf16": hip(d) for d in dtypes}
+        paths["torch"] = torch_step(P, obs, dl, dv)
         if args.once:
             out = {"n": n, "path": args.once, "calls": args.steps,
                    "event_ms": event(paths[args.once], args.steps, args.warmup)}
@@ -94,7 +101,7 @@ def main():
         line = json.dumps(out)
         print(line, flush=True)
         lines.append(line)
-        del eng
+        del paths
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
