@@ -1,6 +1,6 @@
 """Build the HIP extension in-tree: ``python -m impala_amd.build``.
 
-Compiles ``impala_amd/csrc/{impala,sac,dqn_replay,ppo_replay,dqn_inplace,iqn,iqn_replay,resnet}.hip`` for gfx950 into ``impala_amd/libimpala_hip.so`` with
+Compiles ``impala_amd/csrc/{impala,sac,dqn_replay,ppo_replay,dqn_inplace,iqn,resnet}.hip`` for gfx950 into ``impala_amd/libimpala_hip.so`` with
 hipcc (cross-compiles without a GPU).  The .so is git-ignored and travels with the tree.
 """
 from __future__ import annotations
@@ -24,16 +24,15 @@ def sources():
 def hip_units():
     """The translation units linked into the one library (impala.hip: IMPALA / PPO learner and,
     through csrc/dqn.h on the same launchers, the Ape-X DQN learner; sac.hip: SAC learner;
-    dqn_replay.hip: the kernels of the DQN learner's device-side replay, kept out of impala.hip's
-    code object; ppo_replay.hip: the PPO actor's lambda-return ingest kernel, kept out likewise;
+    dqn_replay.hip: the kernels of the device-side replay of the DQN and IQN learners, kept out of
+    impala.hip's code object; ppo_replay.hip: the PPO actor's lambda-return ingest kernel, kept out likewise;
     dqn_inplace.hip: the DQN step's three batch-reading kernels instantiated for a replay ring read in
     place, kept out likewise; iqn.hip: the kernels of the distributional (IQN) actor path and
-    training step, kept out likewise; iqn_replay.hip: the two ingest kernels of the IQN learner's
-    device-side replay, kept out likewise; resnet.hip: the IMPALA ResNet, forward, act and backward, kernels and
+    training step, kept out likewise; resnet.hip: the IMPALA ResNet, forward, act and backward, kernels and
     handle, kept out likewise; of the other units' kernels it takes csrc/act_kernels.h's two)."""
     return [os.path.join(SRC_DIR, f)
             for f in ("impala.hip", "sac.hip", "dqn_replay.hip", "ppo_replay.hip", "dqn_inplace.hip",
-                      "iqn.hip", "iqn_replay.hip", "resnet.hip")]
+                      "iqn.hip", "resnet.hip")]
 
 
 # Per-unit flags.  impala.hip's kernels start on 1 KB boundaries of the code object (the

@@ -1,11 +1,14 @@
-// Host side of the device-side prioritized replay of the Ape-X DQN learner (include/dqn_hip.h,
-// dqn_replay_*).  Included at the end of impala.hip after dqn.h: dqn_train_step_replay enqueues
-// the step exactly as dqn_train_step does, and the batch gather is gather_rows_kernel with its
-// device index; dqn_train_step_replay_rows skips the gather and switches the core handle's key
-// map on (ObsKeys, conv1.h), so the step reads the sampled ring rows in place through the kernels
-// of csrc/dqn_inplace.hip.  The replay's own kernels live in csrc/dqn_replay.hip (a translation unit of its
-// own, so impala.hip's code object does not change with them) behind csrc/dqn_replay_launch.h;
-// the ring's bookkeeping and the argument checks are csrc/dqn_replay_host.h.
+// Host side of the device-side prioritized replay: one ring with W targets per row.  dqn_replay
+// (include/dqn_hip.h, the Ape-X DQN learner's) is that ring at W = 1; iqn_replay (include/iqn_hip.h,
+// csrc/iqn_replay.h) is it at W = n_tau.  Every entry point that exists under both prefixes has one
+// body here, which takes the prefix for its messages.  Included at the end of impala.hip after
+// dqn.h: dqn_train_step_replay enqueues the step exactly as dqn_train_step does, and the batch
+// gather is gather_rows_kernel with its device index; dqn_train_step_replay_rows skips the gather
+// and switches the core handle's key map on (ObsKeys, conv1.h), so the step reads the sampled ring
+// rows in place through the kernels of csrc/dqn_inplace.hip.  The replay's own kernels live in
+// csrc/dqn_replay.hip (a translation unit of its own, so impala.hip's code object does not change
+// with them) behind csrc/dqn_replay_launch.h; the ring's bookkeeping and the argument checks are
+// csrc/dqn_replay_host.h.
 #pragma once
 #include "../../include/dqn_hip.h"
 #include "dqn_replay_host.h"
@@ -13,9 +16,10 @@
 
 struct dqn_replay {
   dqn_replay_host::Ring ring;
+  int W = 1;  // targets per row
   double alpha = 0.0;
   int device = 0;
-  // caller-owned (dqn_replay_bind)
+  // caller-owned (<abi>_replay_bind); targets [cap][W]
   uint8_t* obs = nullptr;
   int64_t* actions = nullptr;
   float* targets = nullptr;
@@ -25,7 +29,7 @@ struct dqn_replay {
   double* weights = nullptr;
   double* bsum = nullptr;
   float* maxp = nullptr;
-  // library-owned gather buffer of one batch (dqn_train_step_replay)
+  // library-owned gather buffer of one batch (dqn_train_step_replay, iqn_train_step_replay)
   char* gbuf = nullptr;
   int g_rows = 0;
   uint8_t* g_obs = nullptr;
@@ -56,12 +60,15 @@ const char* first_null(std::initializer_list<NamedPtr> ps) {
 #define CK_PTRS(entry, ...)                                                             \
   do {                                                                                  \
     if (const char* a_ = first_null({__VA_ARGS__}))                                     \
-      return fail(IMPALA_E_INVALID, std::string(entry ": null pointer: ") + a_);        \
+      return fail(IMPALA_E_INVALID, (entry) + std::string(": null pointer: ") + a_);    \
   } while (0)
 
-int replay_check(const dqn_replay* r, bool bound) {
+// "<abi>_replay_<name>": abi is "dqn" or "iqn", the prefix the caller came in under
+std::string replay_entry(const char* abi, const char* name) { return std::string(abi) + "_replay_" + name; }
+
+int replay_check(const char* abi, const dqn_replay* r, bool bound) {
   if (!r) return fail(IMPALA_E_INVALID, "null replay handle");
-  if (bound && !r->obs) return fail(IMPALA_E_STATE, "dqn_replay_bind() not called");
+  if (bound && !r->obs) return fail(IMPALA_E_STATE, replay_entry(abi, "bind") + "() not called");
   return 0;
 }
 
@@ -89,7 +96,7 @@ int replay_enqueue_gather(dqn_replay* r, const int64_t* keys, int n, uint8_t* ob
                           hipStream_t st) {
   const void* src[3] = {r->obs, r->actions, r->targets};
   void* dst[3] = {obs, act, tgt};
-  const size_t rb[3] = {kObsRowBytes, sizeof(int64_t), sizeof(float)};
+  const size_t rb[3] = {kObsRowBytes, sizeof(int64_t), sizeof(float) * (size_t)r->W};
   return gather_launch(src, dst, rb, 3, keys, nullptr, n, st);
 }
 
@@ -108,7 +115,7 @@ int replay_ensure_gather(dqn_replay* r, int n) {
     r->g_obs = (uint8_t*)a.take((size_t)n * kObsRowBytes);
     r->g_act = (int64_t*)a.take((size_t)n * 8);
     r->g_keys = (int64_t*)a.take((size_t)n * 8);
-    r->g_tgt = (float*)a.take((size_t)n * 4);
+    r->g_tgt = (float*)a.take((size_t)n * r->W * 4);
     r->g_prob = (float*)a.take((size_t)n * 4);
     r->g_prio = (float*)a.take((size_t)n * 4);
     return Arena::align(a.used);
@@ -138,21 +145,22 @@ int replay_ensure_scratch(dqn_replay* r, int n) {
   return 0;
 }
 
-}  // namespace
+// ---- the bodies of the entry points that exist under both prefixes.  Every one refuses in the
+// same order: scalars, named null pointers, the handle, then what needs the ring. ----
 
-extern "C" {
-
-int dqn_replay_block(void) { return DQN_REPLAY_BLOCK; }
-
-int dqn_replay_create(int64_t capacity, double priority_exponent, int device, dqn_replay** out) {
-  CK_PTRS("dqn_replay_create", {"out", out});
+// R: dqn_replay, or the iqn_replay derived from it
+template <class R> int replay_create(const char* abi, int64_t capacity, int W, double priority_exponent, int device,
+                                     R** out) {
+  const std::string entry = replay_entry(abi, "create");
+  if (const char* m = dqn_replay_host::check_create(capacity, W, priority_exponent))
+    return fail(IMPALA_E_INVALID, entry + ": " + m);
+  if (device < 0) return fail(IMPALA_E_INVALID, entry + ": device must be >= 0");
+  CK_PTRS(entry, {"out", out});
   *out = nullptr;
-  if (const char* m = dqn_replay_host::check_create(capacity, priority_exponent))
-    return fail(IMPALA_E_INVALID, std::string("dqn_replay_create: ") + m);
-  if (device < 0) return fail(IMPALA_E_INVALID, "dqn_replay_create: device must be >= 0");
-  dqn_replay* r = new (std::nothrow) dqn_replay();
+  R* r = new (std::nothrow) R();
   if (!r) return fail(IMPALA_E_INVALID, "out of host memory");
   r->ring.cap = capacity;
+  r->W = W;
   r->alpha = priority_exponent;
   r->device = device;
   auto carve = [&](Arena a) {
@@ -171,13 +179,13 @@ int dqn_replay_create(int64_t capacity, double priority_exponent, int device, dq
   if (e != hipSuccess) {
     if (r->state) (void)hipFree(r->state);
     delete r;
-    return fail((int)e, std::string("dqn_replay_create: ") + hipGetErrorString(e));
+    return fail((int)e, entry + ": " + hipGetErrorString(e));
   }
   *out = r;
   return 0;
 }
 
-int dqn_replay_destroy(dqn_replay* r) {
+template <class R> int replay_destroy(R* r) {
   if (!r) return 0;
   (void)hipSetDevice(r->device);
   (void)hipDeviceSynchronize();
@@ -188,12 +196,13 @@ int dqn_replay_destroy(dqn_replay* r) {
   return 0;
 }
 
-int dqn_replay_bind(dqn_replay* r, uint8_t* obs, int64_t* actions, float* targets, float* priorities,
-                    void* stream) {
+int replay_bind(const char* abi, dqn_replay* r, uint8_t* obs, int64_t* actions, float* targets, float* priorities,
+                void* stream) {
   // (arguments first, then the handle: every check is reachable without a device)
-  CK_PTRS("dqn_replay_bind", {"obs", obs}, {"actions", actions}, {"targets", targets}, {"priorities", priorities});
-  if (((uintptr_t)obs & 15) != 0) return fail(IMPALA_E_INVALID, "dqn_replay_bind: obs must be 16-byte aligned");
-  if (int e = replay_check(r, false)) return e;
+  const std::string entry = replay_entry(abi, "bind");
+  CK_PTRS(entry, {"obs", obs}, {"actions", actions}, {"targets", targets}, {"priorities", priorities});
+  if (((uintptr_t)obs & 15) != 0) return fail(IMPALA_E_INVALID, entry + ": obs must be 16-byte aligned");
+  if (int e = replay_check(abi, r, false)) return e;
   CK(hipSetDevice(r->device));
   hipStream_t st = (hipStream_t)stream;
   CK(hipMemsetAsync(r->weights, 0, (size_t)r->ring.cap * 8, st));
@@ -203,68 +212,67 @@ int dqn_replay_bind(dqn_replay* r, uint8_t* obs, int64_t* actions, float* target
   return 0;
 }
 
-int dqn_replay_state(const dqn_replay* r, int64_t* size, int64_t* cursor) {
-  CK_PTRS("dqn_replay_state", {"size", size}, {"cursor", cursor});
-  if (int e = replay_check(r, false)) return e;
+int replay_state(const char* abi, const dqn_replay* r, int64_t* size, int64_t* cursor) {
+  CK_PTRS(replay_entry(abi, "state"), {"size", size}, {"cursor", cursor});
+  if (int e = replay_check(abi, r, false)) return e;
   *size = r->ring.size;
   *cursor = r->ring.cursor;
   return 0;
 }
 
-int dqn_replay_extend(dqn_replay* r, const uint8_t* obs, const int64_t* actions, const float* targets,
-                      const float* priorities, int64_t n, int64_t* keys_out, void* stream) {
-  if (const char* m = dqn_replay_host::check_extend(nullptr, n))
-    return fail(IMPALA_E_INVALID, std::string("dqn_replay_extend: ") + m);
-  CK_PTRS("dqn_replay_extend", {"obs", obs}, {"actions", actions}, {"targets", targets});
-  if (int e = replay_check(r, true)) return e;
-  if (const char* m = dqn_replay_host::check_extend(&r->ring, n))
-    return fail(IMPALA_E_INVALID, std::string("dqn_replay_extend: ") + m);
+int replay_extend(const char* abi, dqn_replay* r, const uint8_t* obs, const int64_t* actions, const float* targets,
+                  const float* priorities, int64_t n, int64_t* keys_out, void* stream) {
+  const std::string entry = replay_entry(abi, "extend");
+  if (const char* m = dqn_replay_host::check_extend(nullptr, n)) return fail(IMPALA_E_INVALID, entry + ": " + m);
+  CK_PTRS(entry, {"obs", obs}, {"actions", actions}, {"targets", targets});
+  if (int e = replay_check(abi, r, true)) return e;
+  if (const char* m = dqn_replay_host::check_extend(&r->ring, n)) return fail(IMPALA_E_INVALID, entry + ": " + m);
   CK(hipSetDevice(r->device));
   hipStream_t st = (hipStream_t)stream;
   if (int e = replay_copy_obs(r, obs, n, st)) return e;
   CK_KERNEL("replay_extend",
-            dqn_replay_dev::launch_extend(actions, targets, priorities, n, r->ring.cursor, r->ring.cap, r->alpha,
-                                          r->actions, r->targets, r->priorities, r->weights, r->maxp, keys_out, st));
+            dqn_replay_dev::launch_extend(actions, targets, priorities, n, r->W, r->ring.cursor, r->ring.cap,
+                                          r->alpha, r->actions, r->targets, r->priorities, r->weights, r->maxp,
+                                          keys_out, st));
   dqn_replay_host::advance(r->ring, n);
   return 0;
 }
 
-int dqn_replay_extend_rollout(dqn_replay* r, const uint8_t* obs, const int64_t* actions, const float* rewards,
-                              const uint8_t* done, const float* q_pi, const float* q_star, int64_t L,
-                              int n_step, float gamma, int64_t* keys_out, void* stream) {
+int replay_extend_rollout(const char* abi, dqn_replay* r, const uint8_t* obs, const int64_t* actions,
+                          const float* rewards, const uint8_t* done, const float* q_pi, const float* q_star,
+                          int64_t L, int n_step, float gamma, int64_t* keys_out, void* stream) {
+  const std::string entry = replay_entry(abi, "extend_rollout");
   if (const char* m = dqn_replay_host::check_rollout(nullptr, L, n_step, gamma))
-    return fail(IMPALA_E_INVALID, std::string("dqn_replay_extend_rollout: ") + m);
-  CK_PTRS("dqn_replay_extend_rollout", {"obs", obs}, {"actions", actions}, {"rewards", rewards}, {"done", done},
-          {"q_pi", q_pi}, {"q_star", q_star});
-  if (int e = replay_check(r, true)) return e;
+    return fail(IMPALA_E_INVALID, entry + ": " + m);
+  CK_PTRS(entry, {"obs", obs}, {"actions", actions}, {"rewards", rewards}, {"done", done}, {"q_pi", q_pi},
+          {"q_star", q_star});
+  if (int e = replay_check(abi, r, true)) return e;
   if (const char* m = dqn_replay_host::check_rollout(&r->ring, L, n_step, gamma))
-    return fail(IMPALA_E_INVALID, std::string("dqn_replay_extend_rollout: ") + m);
+    return fail(IMPALA_E_INVALID, entry + ": " + m);
   CK(hipSetDevice(r->device));
   hipStream_t st = (hipStream_t)stream;
   const int64_t K = L - 1;
   if (int e = replay_copy_obs(r, obs, K, st)) return e;
   CK_KERNEL("replay_rollout",
-            dqn_replay_dev::launch_rollout(actions, rewards, done, q_pi, q_star, K, n_step, gamma, r->ring.cursor,
-                                           r->ring.cap, r->alpha, r->actions, r->targets, r->priorities,
-                                           r->weights, r->maxp, keys_out, st));
+            dqn_replay_dev::launch_rollout(actions, rewards, done, q_pi, q_star, K, r->W, n_step, gamma,
+                                           r->ring.cursor, r->ring.cap, r->alpha, r->actions, r->targets,
+                                           r->priorities, r->weights, r->maxp, keys_out, st));
   dqn_replay_host::advance(r->ring, K);
   return 0;
 }
 
-int dqn_replay_sample(dqn_replay* r, uint64_t seed, uint64_t counter, int64_t n, int64_t* keys,
-                      float* probabilities, uint8_t* obs_out, int64_t* actions_out, float* targets_out,
-                      void* stream) {
-  if (const char* m = dqn_replay_host::check_sample(nullptr, n))
-    return fail(IMPALA_E_INVALID, std::string("dqn_replay_sample: ") + m);
-  CK_PTRS("dqn_replay_sample", {"keys", keys}, {"probabilities", probabilities});
+int replay_sample(const char* abi, dqn_replay* r, uint64_t seed, uint64_t counter, int64_t n, int64_t* keys,
+                  float* probabilities, uint8_t* obs_out, int64_t* actions_out, float* targets_out, void* stream) {
+  const std::string entry = replay_entry(abi, "sample");
+  if (const char* m = dqn_replay_host::check_sample(nullptr, n)) return fail(IMPALA_E_INVALID, entry + ": " + m);
+  CK_PTRS(entry, {"keys", keys}, {"probabilities", probabilities});
   const bool gather = obs_out || actions_out || targets_out;
   if (gather && (!obs_out || !actions_out || !targets_out))
-    return fail(IMPALA_E_INVALID, "dqn_replay_sample: obs_out, actions_out, targets_out: all or none");
+    return fail(IMPALA_E_INVALID, entry + ": obs_out, actions_out, targets_out: all or none");
   if (gather && ((uintptr_t)obs_out & 15) != 0)
-    return fail(IMPALA_E_INVALID, "dqn_replay_sample: obs_out must be 16-byte aligned");
-  if (int e = replay_check(r, true)) return e;
-  if (const char* m = dqn_replay_host::check_sample(&r->ring, n))
-    return fail(IMPALA_E_STATE, std::string("dqn_replay_sample: ") + m);
+    return fail(IMPALA_E_INVALID, entry + ": obs_out must be 16-byte aligned");
+  if (int e = replay_check(abi, r, true)) return e;
+  if (const char* m = dqn_replay_host::check_sample(&r->ring, n)) return fail(IMPALA_E_STATE, entry + ": " + m);
   CK(hipSetDevice(r->device));
   hipStream_t st = (hipStream_t)stream;
   if (int e = replay_enqueue_draws(r, seed, counter, (int)n, keys, probabilities, st)) return e;
@@ -272,19 +280,74 @@ int dqn_replay_sample(dqn_replay* r, uint64_t seed, uint64_t counter, int64_t n,
   return replay_enqueue_gather(r, keys, (int)n, obs_out, actions_out, targets_out, st);
 }
 
-int dqn_replay_update(dqn_replay* r, const int64_t* keys, const float* priorities, int64_t n, void* stream) {
-  if (const char* m = dqn_replay_host::check_update(n))
-    return fail(IMPALA_E_INVALID, std::string("dqn_replay_update: ") + m);
-  CK_PTRS("dqn_replay_update", {"keys", keys}, {"priorities", priorities});
-  if (int e = replay_check(r, true)) return e;
+int replay_update(const char* abi, dqn_replay* r, const int64_t* keys, const float* priorities, int64_t n,
+                  void* stream) {
+  const std::string entry = replay_entry(abi, "update");
+  if (const char* m = dqn_replay_host::check_update(n)) return fail(IMPALA_E_INVALID, entry + ": " + m);
+  CK_PTRS(entry, {"keys", keys}, {"priorities", priorities});
+  if (int e = replay_check(abi, r, true)) return e;
   CK(hipSetDevice(r->device));
   return replay_enqueue_update(r, keys, priorities, (int)n, (hipStream_t)stream);
+}
+
+int replay_weights(const char* abi, dqn_replay* r, double* weights_out, float* max_priority_out, void* stream) {
+  CK_PTRS(replay_entry(abi, "weights"), {"weights_out", weights_out});
+  if (int e = replay_check(abi, r, false)) return e;
+  CK(hipSetDevice(r->device));
+  hipStream_t st = (hipStream_t)stream;
+  CK(hipMemcpyAsync(weights_out, r->weights, (size_t)r->ring.cap * 8, hipMemcpyDeviceToDevice, st));
+  if (max_priority_out) CK(hipMemcpyAsync(max_priority_out, r->maxp, 4, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dqn_replay_block(void) { return DQN_REPLAY_BLOCK; }
+
+int dqn_replay_create(int64_t capacity, double priority_exponent, int device, dqn_replay** out) {
+  return replay_create("dqn", capacity, 1, priority_exponent, device, out);
+}
+
+int dqn_replay_destroy(dqn_replay* r) { return replay_destroy(r); }
+
+int dqn_replay_bind(dqn_replay* r, uint8_t* obs, int64_t* actions, float* targets, float* priorities,
+                    void* stream) {
+  return replay_bind("dqn", r, obs, actions, targets, priorities, stream);
+}
+
+int dqn_replay_state(const dqn_replay* r, int64_t* size, int64_t* cursor) {
+  return replay_state("dqn", r, size, cursor);
+}
+
+int dqn_replay_extend(dqn_replay* r, const uint8_t* obs, const int64_t* actions, const float* targets,
+                      const float* priorities, int64_t n, int64_t* keys_out, void* stream) {
+  return replay_extend("dqn", r, obs, actions, targets, priorities, n, keys_out, stream);
+}
+
+int dqn_replay_extend_rollout(dqn_replay* r, const uint8_t* obs, const int64_t* actions, const float* rewards,
+                              const uint8_t* done, const float* q_pi, const float* q_star, int64_t L,
+                              int n_step, float gamma, int64_t* keys_out, void* stream) {
+  return replay_extend_rollout("dqn", r, obs, actions, rewards, done, q_pi, q_star, L, n_step, gamma, keys_out,
+                               stream);
+}
+
+int dqn_replay_sample(dqn_replay* r, uint64_t seed, uint64_t counter, int64_t n, int64_t* keys,
+                      float* probabilities, uint8_t* obs_out, int64_t* actions_out, float* targets_out,
+                      void* stream) {
+  return replay_sample("dqn", r, seed, counter, n, keys, probabilities, obs_out, actions_out, targets_out, stream);
+}
+
+int dqn_replay_update(dqn_replay* r, const int64_t* keys, const float* priorities, int64_t n, void* stream) {
+  return replay_update("dqn", r, keys, priorities, n, stream);
 }
 
 int dqn_train_step_replay(dqn_learner* h, dqn_replay* r, uint64_t seed, uint64_t counter, int64_t* keys_out,
                           float* priorities_out, void* stream) {
   if (int e = dqn_check(h, true, false)) return e;
-  if (int e = replay_check(r, true)) return e;
+  if (int e = replay_check("dqn", r, true)) return e;
+  if (r->W != 1) return fail(IMPALA_E_INVALID, "dqn_train_step_replay: the replay holds rows of targets");
   impala_learner* c = h->core;
   if (r->device != c->device)
     return fail(IMPALA_E_INVALID, "dqn_train_step_replay: the replay and the learner are on different devices");
@@ -311,7 +374,8 @@ int dqn_train_step_replay(dqn_learner* h, dqn_replay* r, uint64_t seed, uint64_t
 int dqn_train_step_replay_rows(dqn_learner* h, dqn_replay* r, uint64_t seed, uint64_t counter,
                                int64_t* keys_out, float* priorities_out, void* stream) {
   if (int e = dqn_check(h, true, false)) return e;
-  if (int e = replay_check(r, true)) return e;
+  if (int e = replay_check("dqn", r, true)) return e;
+  if (r->W != 1) return fail(IMPALA_E_INVALID, "dqn_train_step_replay_rows: the replay holds rows of targets");
   impala_learner* c = h->core;
   if (r->device != c->device)
     return fail(IMPALA_E_INVALID, "dqn_train_step_replay_rows: the replay and the learner are on different devices");
@@ -347,13 +411,7 @@ int dqn_train_step_replay_rows(dqn_learner* h, dqn_replay* r, uint64_t seed, uin
 }
 
 int dqn_replay_weights(dqn_replay* r, double* weights_out, float* max_priority_out, void* stream) {
-  CK_PTRS("dqn_replay_weights", {"weights_out", weights_out});
-  if (int e = replay_check(r, false)) return e;
-  CK(hipSetDevice(r->device));
-  hipStream_t st = (hipStream_t)stream;
-  CK(hipMemcpyAsync(weights_out, r->weights, (size_t)r->ring.cap * 8, hipMemcpyDeviceToDevice, st));
-  if (max_priority_out) CK(hipMemcpyAsync(max_priority_out, r->maxp, 4, hipMemcpyDeviceToDevice, st));
-  return 0;
+  return replay_weights("dqn", r, weights_out, max_priority_out, stream);
 }
 
 }  // extern "C"

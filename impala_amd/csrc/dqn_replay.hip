@@ -1,4 +1,5 @@
-// Kernels of the device-side prioritized replay (include/dqn_hip.h, dqn_replay_*) and their
+// Kernels of the device-side prioritized replay (include/dqn_hip.h, dqn_replay_*, and -- the
+// same ring with rows of W targets -- include/iqn_hip.h, iqn_replay_*) and their
 // launchers (csrc/dqn_replay_launch.h).  A translation unit of its own, so the code object of
 // impala.hip -- the learner steps' kernels and where they sit in it -- is the same with or
 // without the replay; the host side is csrc/dqn_replay.h, included at the end of impala.hip.
@@ -14,6 +15,7 @@
 #include "common.h"
 
 #include "../../include/dqn_hip.h"
+#include "dqn_replay_host.h"
 #include "dqn_replay_launch.h"
 
 namespace {
@@ -236,54 +238,80 @@ __global__ __launch_bounds__(256) void replay_update_kernel(const int64_t* __res
   if (threadIdx.x == 0) *maxp = fmaxf(*maxp, m);
 }
 
-// One thread per appended row: the small fields, the priority and the weight (obs rows travel by
-// device copies).  pin null: every row takes the running maximum.  The kernel only reads *maxp;
-// replay_raise_max_kernel, the next launch on the stream, raises it.
+// The two ingest kernels of a ring whose target rows are W floats wide (W = 1: dqn_replay; W =
+// n_tau: iqn_replay).  Both store with plain vector stores, add in one fixed order and use no
+// atomics: equal inputs give equal bits.  Neither writes *maxp; replay_raise_max_kernel, the next
+// launch on the stream, raises it from the ring priorities just written.
+//
+// One thread per target: row i / W of the append, column i % W (obs rows travel by device copies).
+// The thread of column 0 also writes the row's action, its priority (pin null: the running
+// maximum) and its float64 weight.
 __global__ __launch_bounds__(256) void replay_extend_kernel(const int64_t* __restrict__ act,
                                                             const float* __restrict__ tgt,
-                                                            const float* __restrict__ pin, long long n,
+                                                            const float* __restrict__ pin, long long n, int W,
                                                             long long cursor, long long cap, double alpha,
                                                             int64_t* __restrict__ r_act, float* __restrict__ r_tgt,
                                                             float* __restrict__ r_prio, double* __restrict__ w,
                                                             const float* __restrict__ maxp,
                                                             int64_t* __restrict__ keys_out) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const long long k = (cursor + i) % cap;
-  r_act[k] = act[i];
-  r_tgt[k] = tgt[i];
-  const float p = pin ? pin[i] : *maxp;
-  r_prio[k] = p;
-  w[k] = replay_weight(p, alpha);
-  if (keys_out) keys_out[i] = k;
+  if (i >= n * W) return;
+  const long long t = i / W;
+  const int k = (int)(i - t * W);
+  const long long row = (cursor + t) % cap;
+  r_tgt[row * W + k] = tgt[i];
+  if (k != 0) return;
+  r_act[row] = act[t];
+  const float p = pin ? pin[t] : *maxp;
+  r_prio[row] = p;
+  w[row] = replay_weight(p, alpha);
+  if (keys_out) keys_out[t] = row;
 }
 
-// One thread per transition: ApexActor._async_make_replay's targets and priorities for K = L - 1
-// transitions.  *maxp is left to replay_raise_max_kernel.
-__global__ __launch_bounds__(256) void replay_rollout_kernel(const int64_t* __restrict__ act,
-                                                             const float* __restrict__ rew,
-                                                             const uint8_t* __restrict__ done,
-                                                             const float* __restrict__ q_pi,
-                                                             const float* __restrict__ q_star, long long K,
-                                                             int n_step, float gamma, long long cursor,
-                                                             long long cap, double alpha, int64_t* __restrict__ r_act,
-                                                             float* __restrict__ r_tgt, float* __restrict__ r_prio,
-                                                             double* __restrict__ w, int64_t* __restrict__ keys_out) {
-  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= K) return;
-  const long long mm = min((long long)n_step, K - t);
-  float acc = q_star[t + mm];  // v_{t+m-1}
-  for (long long k = t + mm - 1; k >= t; --k) {
-    const float d = done[k] ? 0.f : gamma;  // gamma (1 - done), exactly
-    acc = fmaf(d, acc, rew[k]);             // one rounding per step
+// The fused ingest of one rollout (ApexActor._async_make_replay's targets and priorities): K = L - 1
+// transitions, `rows` whole transitions per workgroup, thread lr * W + k on column k of the
+// workgroup's transition lr.  Column k is iqn_nstep_kernel's recurrence (csrc/iqn.hip): v =
+// q_star[t + m][k], one fmaf per step.  The W targets of a transition meet in LDS, and its thread
+// of column 0 adds them from 0 in k order -- iqn_nstep_prio_kernel's sum -- so the priority does
+// not depend on W or on where the row sits in a wavefront.
+__global__ __launch_bounds__(256) void replay_rollout_kernel(
+    const int64_t* __restrict__ act, const float* __restrict__ rew, const uint8_t* __restrict__ done,
+    const float* __restrict__ q_pi, const float* __restrict__ q_star, long long K, int W, int rows, int n_step,
+    float gamma, long long cursor, long long cap, double alpha, int64_t* __restrict__ r_act,
+    float* __restrict__ r_tgt, float* __restrict__ r_prio, double* __restrict__ w,
+    int64_t* __restrict__ keys_out) {
+  __shared__ float tg[256];
+  const int tid = threadIdx.x;
+  const int lr = tid / W, k = tid - lr * W;
+  const long long t = (long long)blockIdx.x * rows + lr;
+  const bool live = lr < rows && t < K;
+  long long row = 0;
+  float qp = 0.f;
+  int64_t ac = 0;
+  if (live) {
+    row = (cursor + t) % cap;
+    if (k == 0) {  // (loaded ahead of the barrier, under the recurrence)
+      qp = q_pi[t];
+      ac = act[t];
+    }
+    const long long mm = min((long long)n_step, K - t);
+    float acc = q_star[(t + mm) * W + k];  // v_{t+m-1}
+    for (long long s = t + mm - 1; s >= t; --s) {
+      const float d = done[s] ? 0.f : gamma;  // gamma (1 - done), exactly
+      acc = fmaf(d, acc, rew[s]);             // one rounding per step
+    }
+    r_tgt[row * W + k] = acc;
+    tg[tid] = acc;
   }
-  const float p = fabsf(acc - q_pi[t]);
-  const long long k = (cursor + t) % cap;
-  r_act[k] = act[t];
-  r_tgt[k] = acc;
-  r_prio[k] = p;
-  w[k] = replay_weight(p, alpha);
-  if (keys_out) keys_out[t] = k;
+  __syncthreads();
+  if (!live || k != 0) return;
+  float s = 0.f;
+  for (int j = 0; j < W; ++j) s += tg[tid + j];
+  const float p = fabsf(s / (float)W - qp);
+  r_act[row] = ac;
+  r_prio[row] = p;
+  w[row] = replay_weight(p, alpha);
+  if (keys_out) keys_out[t] = row;
 }
 
 // One workgroup (the one writer of *maxp): the maximum of the n ring priorities just written at
@@ -320,11 +348,11 @@ hipError_t launch_update(const int64_t* keys, const float* pin, int n, long long
   return hipGetLastError();
 }
 
-hipError_t launch_extend(const int64_t* act, const float* tgt, const float* pin, long long n, long long cursor,
-                         long long cap, double alpha, int64_t* r_act, float* r_tgt, float* r_prio, double* w,
-                         float* maxp, int64_t* keys_out, hipStream_t st) {
-  replay_extend_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(act, tgt, pin, n, cursor, cap, alpha, r_act,
-                                                                    r_tgt, r_prio, w, maxp, keys_out);
+hipError_t launch_extend(const int64_t* act, const float* tgt, const float* pin, long long n, int W,
+                         long long cursor, long long cap, double alpha, int64_t* r_act, float* r_tgt,
+                         float* r_prio, double* w, float* maxp, int64_t* keys_out, hipStream_t st) {
+  replay_extend_kernel<<<(unsigned)dqn_replay_host::extend_wgs(n, W), 256, 0, st>>>(
+      act, tgt, pin, n, W, cursor, cap, alpha, r_act, r_tgt, r_prio, w, maxp, keys_out);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !pin) return e;  // rows at the running maximum do not raise it
   replay_raise_max_kernel<<<1, 1024, 0, st>>>(r_prio, n, cursor, cap, maxp);
@@ -332,21 +360,16 @@ hipError_t launch_extend(const int64_t* act, const float* tgt, const float* pin,
 }
 
 hipError_t launch_rollout(const int64_t* act, const float* rew, const uint8_t* done, const float* q_pi,
-                          const float* q_star, long long K, int n_step, float gamma, long long cursor,
+                          const float* q_star, long long K, int W, int n_step, float gamma, long long cursor,
                           long long cap, double alpha, int64_t* r_act, float* r_tgt, float* r_prio, double* w,
                           float* maxp, int64_t* keys_out, hipStream_t st) {
-  replay_rollout_kernel<<<(unsigned)((K + 255) / 256), 256, 0, st>>>(act, rew, done, q_pi, q_star, K, n_step,
-                                                                     gamma, cursor, cap, alpha, r_act, r_tgt,
-                                                                     r_prio, w, keys_out);
+  const dqn_replay_host::RolloutShape sh = dqn_replay_host::rollout_shape(K, W);
+  replay_rollout_kernel<<<(unsigned)sh.wgs, 256, 0, st>>>(act, rew, done, q_pi, q_star, K, W, sh.rows, n_step,
+                                                          gamma, cursor, cap, alpha, r_act, r_tgt, r_prio, w,
+                                                          keys_out);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   replay_raise_max_kernel<<<1, 1024, 0, st>>>(r_prio, K, cursor, cap, maxp);
-  return hipGetLastError();
-}
-
-hipError_t launch_raise_max(const float* r_prio, long long n, long long cursor, long long cap, float* maxp,
-                            hipStream_t st) {
-  replay_raise_max_kernel<<<1, 1024, 0, st>>>(r_prio, n, cursor, cap, maxp);
   return hipGetLastError();
 }
 

@@ -1,7 +1,9 @@
-// Host bookkeeping of dqn_replay (include/dqn_hip.h): the ring's cursor / size arithmetic, the
-// split of an append into contiguous spans, the launch shapes of the two sampling kernels and
-// every argument check.  No HIP here, so tests/dqn_replay_check.cpp runs it on the CPU under
-// sanitizers; csrc/dqn_replay.h is its only other user.
+// Host bookkeeping of the prioritized ring behind dqn_replay (include/dqn_hip.h, W = 1 target per
+// row) and iqn_replay (include/iqn_hip.h, W = n_tau): the ring's cursor / size arithmetic, the
+// split of an append into contiguous spans, the launch shapes of the sampling and ingest kernels,
+// the split of a long priority update into launches and every argument check.  No HIP here, so
+// tests/dqn_replay_check.cpp and tests/iqn_replay_check.cpp run it on the CPU under sanitizers;
+// csrc/dqn_replay.{h,hip} and csrc/iqn_replay.h are its other users.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -15,6 +17,8 @@ constexpr int64_t kMaxBlocks = 4096;
 constexpr int64_t kMaxCapacity = kMaxBlocks * DQN_REPLAY_BLOCK;
 constexpr int kMaxSample = 1 << 20;
 constexpr int kScanThreads = 256;
+constexpr int kWg = 256;       // threads of a workgroup of both ingest kernels
+constexpr int kMaxWidth = 32;  // IQN_MAX_TAU (csrc/iqn_replay.h asserts that the two agree)
 
 struct Ring {
   int64_t cap = 0, size = 0, cursor = 0;
@@ -63,6 +67,16 @@ inline const char* check_create(int64_t capacity, double priority_exponent) {
   return nullptr;
 }
 
+inline const char* check_n_tau(int n_tau) {
+  if (n_tau < 1 || n_tau > kMaxWidth) return "n_tau must be in [1, 32]";
+  return nullptr;
+}
+
+inline const char* check_create(int64_t capacity, int n_tau, double priority_exponent) {
+  if (const char* m = check_n_tau(n_tau)) return m;
+  return check_create(capacity, priority_exponent);
+}
+
 // The checks below run twice: with r null before the handle is looked at (what the scalars alone
 // decide), then with the ring.
 inline const char* check_extend(const Ring* r, int64_t n) {
@@ -90,6 +104,31 @@ inline const char* check_update(int64_t n) {
   if (n < 1) return "n must be >= 1";
   if (n > DQN_MAX_BATCH) return "n must be <= DQN_MAX_BATCH (4096)";
   return nullptr;
+}
+
+// replay_extend_kernel: one thread per target, n * W of them
+inline int64_t extend_wgs(int64_t n, int W) { return (n * W + kWg - 1) / kWg; }
+
+// replay_rollout_kernel: a workgroup holds `rows` whole transitions, W consecutive threads each
+// (threads past rows * W idle), so a transition's targets never straddle two workgroups
+struct RolloutShape {
+  int rows;
+  int64_t wgs;
+};
+inline RolloutShape rollout_shape(int64_t K, int W) {
+  const int rows = kWg / W;
+  return RolloutShape{rows, (K + rows - 1) / rows};
+}
+
+// A priority update of n keys as launches of at most DQN_MAX_BATCH keys, in order: chunk i of
+// update_chunks(n) covers keys [off, off + len).
+struct Chunk {
+  int off, len;
+};
+inline int update_chunks(int n) { return n < 1 ? 0 : (n + DQN_MAX_BATCH - 1) / DQN_MAX_BATCH; }
+inline Chunk update_chunk(int n, int i) {
+  const int off = i * DQN_MAX_BATCH;
+  return Chunk{off, n - off < DQN_MAX_BATCH ? n - off : DQN_MAX_BATCH};
 }
 
 }  // namespace dqn_replay_host

@@ -1,5 +1,6 @@
 // Launchers of the replay kernels (csrc/dqn_replay.hip), called by the host side in
-// csrc/dqn_replay.h.  Each enqueues one kernel on `st` and returns hipGetLastError().
+// csrc/dqn_replay.h.  Each enqueues its kernel on `st` (the two ingests also the running maximum's)
+// and returns hipGetLastError().
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,16 +14,16 @@ hipError_t launch_draw(const double* w, const double* bsum, long long size, int 
                        uint64_t counter, int n, int64_t* keys, float* prob, hipStream_t st);
 hipError_t launch_update(const int64_t* keys, const float* pin, int n, long long cap, double alpha, float* prio,
                          double* w, float* maxp, hipStream_t st);
-hipError_t launch_extend(const int64_t* act, const float* tgt, const float* pin, long long n, long long cursor,
-                         long long cap, double alpha, int64_t* r_act, float* r_tgt, float* r_prio, double* w,
-                         float* maxp, int64_t* keys_out, hipStream_t st);
+// n rows of W targets appended at the cursor (across the wrap); pin null: rows take *maxp.  With
+// pin, replay_raise_max_kernel follows (rows at the running maximum do not raise it).
+hipError_t launch_extend(const int64_t* act, const float* tgt, const float* pin, long long n, int W,
+                         long long cursor, long long cap, double alpha, int64_t* r_act, float* r_tgt,
+                         float* r_prio, double* w, float* maxp, int64_t* keys_out, hipStream_t st);
+// K = L - 1 transitions of one rollout: targets [K][W], priorities, weights, actions at their ring
+// rows, then replay_raise_max_kernel
 hipError_t launch_rollout(const int64_t* act, const float* rew, const uint8_t* done, const float* q_pi,
-                          const float* q_star, long long K, int n_step, float gamma, long long cursor,
+                          const float* q_star, long long K, int W, int n_step, float gamma, long long cursor,
                           long long cap, double alpha, int64_t* r_act, float* r_tgt, float* r_prio, double* w,
                           float* maxp, int64_t* keys_out, hipStream_t st);
-// *maxp = max(*maxp, the n ring priorities at (cursor + i) % cap): what launch_extend and
-// launch_rollout end with, for an ingest kernel of another unit (csrc/iqn_replay.hip)
-hipError_t launch_raise_max(const float* r_prio, long long n, long long cursor, long long cap, float* maxp,
-                            hipStream_t st);
 
 }  // namespace dqn_replay_dev

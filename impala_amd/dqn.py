@@ -515,7 +515,9 @@ class PrioritizedReplay:
 
 class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
     """``PrioritizedReplay`` on the library's ``dqn_replay`` (include/dqn_hip.h): the same
-    constructor, attributes and methods, every one through a ``dqn_replay_*`` entry point.  The
+    constructor, attributes and methods, every one through a ``dqn_replay_*`` entry point
+    (``_call``: ``NativeQuantileReplay`` is this class on the ``iqn_replay_*`` ones, the same ring
+    with ``target_width`` targets per row).  The
     tensors ``s``, ``a``, ``target``, ``priorities`` are the bound ring arrays; the float64
     weights, their block sums and the running maximum priority belong to the library.
 
@@ -548,9 +550,8 @@ class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
         idx = self.device_index(device)
         self._open("dqn_replay_create", int(capacity), float(priority_exponent), idx)
         super().__init__(capacity, priority_exponent, torch.device("cuda", idx), seed)
-        check(lib().dqn_replay_bind(self._h, _lib.ptr(self.s), _lib.ptr(self.a),
-                                    _lib.ptr(self.target), _lib.ptr(self.priorities),
-                                    self._stream()), "dqn_replay_bind", _ERR)
+        self._call("bind", _lib.ptr(self.s), _lib.ptr(self.a), _lib.ptr(self.target),
+                   _lib.ptr(self.priorities), self._stream())
 
     def _init_sampler(self) -> None:
         """The weights, the running maximum priority, size and cursor belong to the library."""
@@ -574,42 +575,50 @@ class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
         return self._seed, c
 
     def extend(self, items, priorities=None) -> torch.Tensor:
-        s, a, t = _replay_columns(items)
+        W = self.target_width
+        s, a, t = _replay_columns(items, W)
         n = s.shape[0]
         if n > self.capacity:
             raise ValueError("more items than the ring holds")
         s = s.to(self.device, torch.uint8).contiguous()
         a = a.reshape(-1).to(self.device, torch.int64).contiguous()
-        t = t.reshape(-1).to(self.device, torch.float32).contiguous()
+        t = t.to(self.device, torch.float32).contiguous()
         p = None
         if priorities is not None:
             p = torch.as_tensor(priorities, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
             if p.numel() != n:
                 raise ValueError("one priority per item")
-        if a.numel() != n or t.numel() != n:
-            raise ValueError("s, a, target: one row per item")
+        if a.numel() != n or t.numel() != n * W:
+            raise ValueError(f"s, a, target: one row per item, {W} target(s) each")
         keys = torch.empty(n, dtype=torch.int64, device=self.device)
-        check(lib().dqn_replay_extend(self._h, _lib.ptr(s), _lib.ptr(a), _lib.ptr(t), _lib.ptr(p),
-                                      n, _lib.ptr(keys), self._stream()), "dqn_replay_extend", _ERR)
+        self._call("extend", _lib.ptr(s), _lib.ptr(a), _lib.ptr(t), _lib.ptr(p), n, _lib.ptr(keys),
+                   self._stream())
         return keys
+
+    @staticmethod
+    def _rollout_shapes(W: int, s, a, r, done, q_pi, q_star) -> int:
+        """The steps L of one rollout whose fields agree (no device needed)."""
+        L = int(s.shape[0])
+        if not all(x.numel() == L for x in (a, r, done, q_pi, q_star)):
+            raise ValueError("extend_rollout: every field has one entry per step")
+        return L
 
     def extend_rollout(self, s, a, r, done, q_pi, q_star, n_step: int = 3,
                        gamma: float = 0.99) -> torch.Tensor:
-        """One actor rollout of L steps -> L - 1 transitions with their n-step targets and initial
-        priorities ``|target - q_pi|`` (``dqn_replay_extend_rollout``).  Returns the keys written."""
-        L = s.shape[0]
+        """One actor rollout of L steps (``q_star [L]``, or ``[L, W]`` on a ring of W targets per
+        row) -> L - 1 transitions with their n-step targets, per quantile where W > 1, and initial
+        priorities ``|mean target - q_pi|`` (``<abi>_extend_rollout``; bit for bit
+        ``iqn_nstep_targets``').  Returns the keys written."""
+        L = self._rollout_shapes(self.target_width, s, a, r, done, q_pi, q_star)
         f32 = lambda x: x.reshape(-1).to(self.device, torch.float32).contiguous()
         s = s.to(self.device, torch.uint8).contiguous()
         a = a.reshape(-1).to(self.device, torch.int64).contiguous()
         d = done.reshape(-1).to(self.device).ne(0).to(torch.uint8).contiguous()
         r, q_pi, q_star = f32(r), f32(q_pi), f32(q_star)
-        if not all(x.numel() == L for x in (a, r, d, q_pi, q_star)):
-            raise ValueError("extend_rollout: every field has one entry per step")
         keys = torch.empty(max(L - 1, 0), dtype=torch.int64, device=self.device)
-        check(lib().dqn_replay_extend_rollout(
-            self._h, _lib.ptr(s), _lib.ptr(a), _lib.ptr(r), _lib.ptr(d), _lib.ptr(q_pi),
-            _lib.ptr(q_star), L, int(n_step), float(gamma), _lib.ptr(keys), self._stream()),
-            "dqn_replay_extend_rollout", _ERR)
+        self._call("extend_rollout", _lib.ptr(s), _lib.ptr(a), _lib.ptr(r), _lib.ptr(d),
+                   _lib.ptr(q_pi), _lib.ptr(q_star), L, int(n_step), float(gamma), _lib.ptr(keys),
+                   self._stream())
         return keys
 
     def weights(self) -> torch.Tensor:
@@ -630,8 +639,9 @@ class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
         return (w / w.sum()).float()
 
     def sample(self, n: int, gather: bool = True):
-        """-> (keys [n] i64, (s, a, target), probabilities [n]); with ``gather=False`` the middle
-        element is None and only keys and probabilities are produced."""
+        """-> (keys [n] i64, (s, a, target [n], or [n, W] from a ring of rows), probabilities [n]);
+        with ``gather=False`` the middle element is None and only keys and probabilities are
+        produced."""
         if self._size == 0:
             raise RuntimeError("sample from an empty replay")
         n = int(n)
@@ -641,12 +651,11 @@ class NativePrioritizedReplay(PrioritizedReplay, _lib.NativeHandle):
         if gather:
             rows = (torch.empty((n,) + OBS_SHAPE, dtype=torch.uint8, device=self.device),
                     torch.empty(n, dtype=torch.int64, device=self.device),
-                    torch.empty(n, dtype=torch.float32, device=self.device))
+                    torch.empty((n,) + self.target.shape[1:], dtype=torch.float32, device=self.device))
         seed, counter = self.next_draw()
         out = rows or (None, None, None)
-        check(lib().dqn_replay_sample(self._h, seed, counter, n, _lib.ptr(keys), _lib.ptr(probs),
-                                      _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]),
-                                      self._stream()), "dqn_replay_sample", _ERR)
+        self._call("sample", seed, counter, n, _lib.ptr(keys), _lib.ptr(probs), _lib.ptr(out[0]),
+                   _lib.ptr(out[1]), _lib.ptr(out[2]), self._stream())
         return keys, rows, probs
 
     def update(self, keys, priorities) -> None:

@@ -30,7 +30,7 @@ from impala_amd._lib import check, lib
 from impala_amd.core import Actor
 from impala_amd.dqn import (ApexActor, ApexDQNBuilder, ApexLearner, ConstantEpsFunc,
                             FlexibleEpsFunc, NativePrioritizedReplay, PrioritizedReplay, QEngine,
-                            QModel, _replay_columns)
+                            QModel)
 from impala_amd.flat import layer_init_truncated, spec_count
 from impala_amd.model import OBS_SHAPE
 
@@ -352,8 +352,7 @@ class NativeQuantileReplay(NativePrioritizedReplay):
     the same attributes and methods, every one through an ``iqn_replay_*`` entry point.  The
     tensors ``s``, ``a``, ``target`` ([capacity, W]) and ``priorities`` are the bound ring arrays;
     the float64 weights, their block sums and the running maximum priority belong to the library,
-    and sampling, ``update``, ``weights``, ``max_priority``, ``probabilities``, ``next_draw`` and
-    ``reset`` are ``NativePrioritizedReplay``'s on this handle.  ``extend_rollout`` is the
+    and every method is ``NativePrioritizedReplay``'s on this handle.  ``extend_rollout`` is the
     distributional actor's ``_make_replay`` (agents/dqn/learning.py:69-84) as one fused ingest."""
     _destroy, _last_error, _abi = "iqn_replay_destroy", _ERR, "iqn_replay"
     in_place = False  # (the IQN step reads a gathered batch; there is no in-place step)
@@ -376,27 +375,6 @@ class NativeQuantileReplay(NativePrioritizedReplay):
         self._call("bind", _lib.ptr(self.s), _lib.ptr(self.a), _lib.ptr(self.target),
                    _lib.ptr(self.priorities), self._stream())
 
-    def extend(self, items, priorities=None) -> torch.Tensor:
-        W = self.target_width
-        s, a, t = _replay_columns(items, W)
-        n = s.shape[0]
-        if n > self.capacity:
-            raise ValueError("more items than the ring holds")
-        s = s.to(self.device, torch.uint8).contiguous()
-        a = a.reshape(-1).to(self.device, torch.int64).contiguous()
-        t = t.to(self.device, torch.float32).contiguous()
-        p = None
-        if priorities is not None:
-            p = torch.as_tensor(priorities, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
-            if p.numel() != n:
-                raise ValueError("one priority per item")
-        if a.numel() != n or t.numel() != n * W:
-            raise ValueError(f"s, a, target: one row per item, target [n, {W}]")
-        keys = torch.empty(n, dtype=torch.int64, device=self.device)
-        self._call("extend", _lib.ptr(s), _lib.ptr(a), _lib.ptr(t), _lib.ptr(p), n, _lib.ptr(keys),
-                   self._stream())
-        return keys
-
     @staticmethod
     def _rollout_shapes(W: int, s, a, r, done, q_pi, q_star) -> int:
         """The steps L of one rollout whose fields agree (no device needed)."""
@@ -410,42 +388,6 @@ class NativeQuantileReplay(NativePrioritizedReplay):
         if tuple(q_star.shape) != (L, W):
             raise ValueError(f"extend_rollout: q_star [L, {W}]")
         return L
-
-    def extend_rollout(self, s, a, r, done, q_pi, q_star, n_step: int = 3,
-                       gamma: float = 0.99) -> torch.Tensor:
-        """One actor rollout of L steps (``q_star [L, W]``) -> L - 1 transitions with their
-        per-quantile n-step targets and initial priorities, bit for bit ``iqn_nstep_targets``'
-        (``iqn_replay_extend_rollout``).  Returns the keys written."""
-        L = self._rollout_shapes(self.target_width, s, a, r, done, q_pi, q_star)
-        f32 = lambda x: x.reshape(-1).to(self.device, torch.float32).contiguous()
-        s = s.to(self.device, torch.uint8).contiguous()
-        a = a.reshape(-1).to(self.device, torch.int64).contiguous()
-        d = done.reshape(-1).to(self.device).ne(0).to(torch.uint8).contiguous()
-        r, q_pi, q_star = f32(r), f32(q_pi), f32(q_star)
-        keys = torch.empty(L - 1, dtype=torch.int64, device=self.device)
-        self._call("extend_rollout", _lib.ptr(s), _lib.ptr(a), _lib.ptr(r), _lib.ptr(d),
-                   _lib.ptr(q_pi), _lib.ptr(q_star), L, int(n_step), float(gamma), _lib.ptr(keys),
-                   self._stream())
-        return keys
-
-    def sample(self, n: int, gather: bool = True):
-        """-> (keys [n] i64, (s, a, target [n, W]), probabilities [n]); with ``gather=False`` the
-        middle element is None and only keys and probabilities are produced."""
-        if self._size == 0:
-            raise RuntimeError("sample from an empty replay")
-        n = int(n)
-        keys = torch.empty(n, dtype=torch.int64, device=self.device)
-        probs = torch.empty(n, dtype=torch.float32, device=self.device)
-        rows = None
-        if gather:
-            rows = (torch.empty((n,) + OBS_SHAPE, dtype=torch.uint8, device=self.device),
-                    torch.empty(n, dtype=torch.int64, device=self.device),
-                    torch.empty(n, self.target_width, dtype=torch.float32, device=self.device))
-        seed, counter = self.next_draw()
-        out = rows or (None, None, None)
-        self._call("sample", seed, counter, n, _lib.ptr(keys), _lib.ptr(probs), _lib.ptr(out[0]),
-                   _lib.ptr(out[1]), _lib.ptr(out[2]), self._stream())
-        return keys, rows, probs
 
 
 class ApexDistributionalActor(ApexActor):

@@ -1,8 +1,9 @@
-// CPU check of impala_amd/csrc/iqn_replay_host.h (tests/test_iqn_replay_host.py): the width and
-// create checks, the launch shapes of the two ingest kernels against a per-thread model of their
-// indexing, and the split of a priority update into chunks.  Built with
-// -fsanitize=address,undefined; no GPU involved.
-#include "../impala_amd/csrc/iqn_replay_host.h"
+// CPU check of what impala_amd/csrc/dqn_replay_host.h holds for a ring of W targets per row
+// (tests/test_iqn_replay_host.py): the width and create checks, the launch shapes of the two
+// ingest kernels against a per-thread model of their indexing, and the split of a priority update
+// into chunks.  Built with -fsanitize=address,undefined; no GPU involved.
+#include "../include/iqn_hip.h"
+#include "../impala_amd/csrc/dqn_replay_host.h"
 
 #include <cstdio>
 #include <cstring>
@@ -17,7 +18,8 @@
   } while (0)
 
 int main() {
-  using namespace iqn_replay_host;
+  using namespace dqn_replay_host;
+  static_assert(kMaxWidth == IQN_MAX_TAU, "check_n_tau bounds n_tau by IQN_MAX_TAU");
   // the checks name the argument; n_tau comes first
   CHECK(check_n_tau(1) == nullptr && check_n_tau(IQN_MAX_TAU) == nullptr);
   CHECK(std::strstr(check_n_tau(0), "n_tau") && std::strstr(check_n_tau(IQN_MAX_TAU + 1), "n_tau"));

@@ -230,6 +230,50 @@ def test_large_ingest_over_many_workgroups_and_the_wrap():
     assert st == 1001 and b"capacity" in _lib.lib().iqn_last_error()
 
 
+# ---------------------------------------------------------------- 4b. one ring behind both handles
+def test_at_width_one_the_two_handles_are_the_same_ring():
+    """NativePrioritizedReplay and NativeQuantileReplay(W = 1), fed the same inputs, hold the same
+    bits: an extend with priorities, one without (the running maximum), a rollout of K = 100 from
+    cursor 96 of 128 (the wrap, the n-step truncation at its end, dones on the first step, on step
+    L - 2 and on adjacent steps, one transition whose target and q_pi are both exactly 0), an
+    update with a duplicate key (both copies the same priority: with different ones the value
+    that lands is undefined), and a draw."""
+    from impala_amd.dqn import NativePrioritizedReplay
+    dev = _dev()
+    rings = (NativePrioritizedReplay(128, priority_exponent=ALPHA, device=dev), _native(dev, 128, 1))
+    s, a, r, done, q_pi, q_star = _rollout(101, 1, 31)
+    r[40] = q_pi[40] = 0.0  # done[40]: the target is r[40]
+    rng = np.random.default_rng(5)
+    upd_keys = torch.from_numpy(rng.permutation(128)[:33])
+    upd_keys[17] = upd_keys[4]
+    upd_pri = torch.from_numpy(rng.uniform(0.0, 3.0, 33).astype(np.float32))
+    upd_pri[17] = upd_pri[4]
+    got = []
+    for rb in rings:
+        W1 = (1,) * (rb.target.dim() - 1)  # the quantile ring's rows are [n, 1]
+        s1, a1, t1 = _rows(90, 1)
+        k1 = rb.extend((s1, a1, t1.reshape((90,) + W1)), priorities=shape_priorities(90))
+        s2, a2, t2 = _rows(6, 1, start=100, seed=1)
+        k2 = rb.extend((s2, a2, t2.reshape((6,) + W1)))
+        assert (rb.size, rb._cursor) == (96, 96)
+        k3 = rb.extend_rollout(s, a, torch.from_numpy(r), torch.from_numpy(done), torch.from_numpy(q_pi),
+                               torch.from_numpy(q_star.reshape((101,) + W1)), n_step=3, gamma=0.99)
+        zero = (96 + 40) % 128
+        assert float(rb.target.reshape(128)[zero]) == 0.0 and float(rb.priorities[zero]) == 0.0
+        rb.update(upd_keys, upd_pri)
+        rb.reset(DRAW_SEED)
+        rb._counter = 7
+        sk, none, sp = rb.sample(33, gather=False)
+        torch.cuda.synchronize()
+        got.append(dict(keys=torch.cat([k1, k2, k3]), a=rb.a, target=rb.target.reshape(128),
+                        priorities=rb.priorities, weights=rb.weights(), max_priority=rb.max_priority(),
+                        state=torch.tensor([rb.size, rb._cursor]), sampled_keys=sk, probabilities=sp))
+    d, q = got
+    assert d["state"].tolist() == [128, 68] and d["keys"][96:].tolist() == [(96 + i) % 128 for i in range(100)]
+    for name in d:
+        assert torch.equal(d[name], q[name]), name
+
+
 # ---------------------------------------------------------------- 5. the one call and its parts
 STEP_CASES = [c for c in so.CASES if c[:3] in ((3, 8, 6), (2, 5, 15), (5, 32, 6))]
 

@@ -1,7 +1,7 @@
 """iqn_replay on the CPU: the C boundary (declared, bound, exported, ABI 3, every argument refused
 before any HIP call: scalars, then named null pointers, then the handle), the Python surface's
-refusals that need no device, and the new host bookkeeping (impala_amd/csrc/iqn_replay_host.h)
-under sanitizers in a stand-alone program."""
+refusals that need no device, and the host bookkeeping of a ring of W targets per row
+(impala_amd/csrc/dqn_replay_host.h) under sanitizers in a stand-alone program."""
 import ctypes as C
 import os
 import re
@@ -158,8 +158,8 @@ def test_scalar_arguments_are_refused_and_named():
 
 
 def test_host_bookkeeping_under_sanitizers(tmp_path):
-    """impala_amd/csrc/iqn_replay_host.h in a stand-alone program built with
-    -fsanitize=address,undefined on the CPU (no GPU, nothing loaded into python)."""
+    """impala_amd/csrc/dqn_replay_host.h's width, launch-shape and chunk helpers in a stand-alone
+    program built with -fsanitize=address,undefined on the CPU (no GPU, nothing loaded into python)."""
     cxx = shutil.which("clang++", path="/opt/rocm/lib/llvm/bin") or shutil.which("clang++") or \
         shutil.which("g++")
     if cxx is None:
