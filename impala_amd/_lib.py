@@ -101,11 +101,14 @@ RESNET_EXPORTS = (
     "resnet_abi_version", "resnet_last_error", "resnet_config_default", "resnet_param_count",
     "resnet_create", "resnet_destroy", "resnet_bind_params", "resnet_refresh_weights",
     "resnet_forward", "resnet_act", "resnet_debug_read", "resnet_forward_train", "resnet_backward",
+    "resnet_step_config_default", "resnet_step_init", "resnet_bind_state", "resnet_set_step",
+    "resnet_set_debug_vtrace", "resnet_loss_head", "resnet_compute_grads", "resnet_apply_update",
+    "resnet_train_step",
 )
-RESNET_ABI_VERSION = 3
+RESNET_ABI_VERSION = 4
 RESNET_DBG_Y, RESNET_DBG_H, RESNET_DBG_HEADS = 15, 16, 17
 (RESNET_DBG_GRAD0, RESNET_DBG_GY, RESNET_DBG_GZ, RESNET_DBG_AMAX, RESNET_DBG_LNSTAT,
- RESNET_DBG_PART) = 32, 47, 48, 49, 50, 51
+ RESNET_DBG_PART, RESNET_DBG_DLOGITS, RESNET_DBG_DVALUES, RESNET_DBG_TPART) = 32, 47, 48, 49, 50, 51, 52, 53, 54
 IQN_ABI_VERSION = 3
 IQN_DBG_DPRE, IQN_DBG_DX, IQN_DBG_COS = 100, 101, 102
 IQN_MAX_TAU = 32
@@ -191,6 +194,14 @@ class IqnConfig(C.Structure):
 class ResnetConfig(C.Structure):
     _fields_ = [("batch_size", C.c_int), ("num_actions", C.c_int), ("dtype", C.c_int),
                 ("debug", C.c_int), ("train", C.c_int), ("train_dtype", C.c_int)]
+
+
+class ResnetStepConfig(C.Structure):
+    _fields_ = [("batch_size", C.c_int), ("rollout_length", C.c_int), ("lr", C.c_float),
+                ("adam_beta1", C.c_float), ("adam_beta2", C.c_float), ("adam_eps", C.c_float),
+                ("max_grad_norm", C.c_float), ("entropy_coeff", C.c_float),
+                ("vtrace_lambda", C.c_float), ("clip_rho_threshold", C.c_float),
+                ("clip_pg_rho_threshold", C.c_float), ("vtrace_grad_mode", C.c_int)]
 
 
 class IqnOptim(C.Structure):
@@ -387,6 +398,14 @@ def _declare(lib):
     lib.resnet_debug_read.argtypes = [_P, C.c_int, _P, C.c_size_t, _P]
     lib.resnet_forward_train.argtypes = [_P, _P, C.c_int, _P, _P, _P]
     lib.resnet_backward.argtypes = [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P]
+    lib.resnet_step_config_default.argtypes = [C.POINTER(ResnetStepConfig)]
+    lib.resnet_step_init.argtypes = [_P, C.POINTER(ResnetStepConfig)]
+    lib.resnet_bind_state.argtypes = [_P, _P, _P, _P, _P, _P, _P]
+    lib.resnet_set_step.argtypes = [_P, C.c_int64, _P]
+    lib.resnet_set_debug_vtrace.argtypes = [_P, _P]
+    for name in ("resnet_loss_head", "resnet_compute_grads", "resnet_train_step"):
+        getattr(lib, name).argtypes = [_P, C.POINTER(ImpalaBatch), _P]
+    lib.resnet_apply_update.argtypes = [_P, _P]
     for name in RESNET_EXPORTS:
         getattr(lib, name).restype = (C.c_char_p if name == "resnet_last_error" else
                                       C.c_size_t if name == "resnet_param_count" else C.c_int)

@@ -137,6 +137,42 @@ class ImpalaBuilder(Builder):
         return model
 
 
+class ImpalaResNetBuilder(ImpalaBuilder):
+    """``ImpalaBuilder`` with the IMPALA paper's deep network (conf/agent/impala_resnet.yaml):
+    ``ImpalaResNetModel`` and its one-call learner; the replay and the actors are the parent's."""
+
+    def make_learner(self, model, rb):
+        from impala_amd.resnet import ImpalaResNetLearner
+        opt = ImpalaAdam(lr=float(self.cfg.agent.optimizer.lr),
+                         eps=float(self.cfg.agent.optimizer.eps))
+        kw = {}
+        if self._learner_cfg("honour_yaml_hparams", False):
+            kw = dict(max_grad_norm=float(self.cfg.agent.max_grad_norm),
+                      entropy_coeff=float(self.cfg.agent.entropy_cost),
+                      model_push_period=int(self.cfg.agent.model_push_period))
+        return ImpalaResNetLearner(self._learner_model if model is None else model, rb, opt,
+                                   batch_size=self.cfg.agent.batch_size,
+                                   learning_starts=self.cfg.agent.learning_starts,
+                                   rollout_length=self.cfg.agent.rollout_length,
+                                   dtype=self._learner_cfg("dtype", None),
+                                   vtrace_grad_mode=self._learner_cfg("vtrace_grad_mode", None), **kw)
+
+    def make_network(self, env_spec=None):
+        from impala_amd.resnet import ImpalaResNetModel
+        obs_shape, n_act = (3, 64, 64), 15
+        if env_spec is not None:
+            obs_shape = tuple(env_spec.observation_space.shape)
+            n_act = int(env_spec.action_space.n)
+        dtype = self._learner_cfg("dtype", "fp32")
+        model = ImpalaResNetModel(obs_shape, n_act, device=self.cfg.distributed.train_device, dtype=dtype,
+                                  train_batch=self.cfg.agent.batch_size * self.cfg.agent.rollout_length,
+                                  train_dtype=dtype)
+        self._learner_model = model
+        self._actor_model = model.clone_to(self.cfg.distributed.infer_device)
+        model.downstream = self._actor_model  # push() publishes the learner weights here
+        return model
+
+
 class PPOBuilder(Builder):
     """agents/ppo/builder.py:24-53 on the HIP learner."""
 

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 
@@ -40,6 +41,16 @@ int fail(int code, const std::string& msg) { return impala_internal::set_error(c
     if (e_ != hipSuccess)                                                              \
       return fail((int)e_, std::string("launch ") + name + ": " + hipGetErrorString(e_)); \
   } while (0)
+
+// recover the decimal constant a float config value was written as (0.9f -> 0.9), to eight significant
+// digits: the Adam launches' arguments of the IMPALA, PPO, DQN, IQN and ResNet handles (sac.hip keeps
+// its own seven-digit one: DESIGN.md §9 "Two `dec`s")
+inline double dec8(float x) {
+  if (x == 0.f) return 0.0;
+  const double e = std::floor(std::log10(std::fabs((double)x)));
+  const double s = std::pow(10.0, 7.0 - e);
+  return std::round((double)x * s) / s;
+}
 
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }

@@ -59,12 +59,8 @@ inline int next_pow2(int x) {
   return p;
 }
 // recover the decimal constant a float config value was written as (0.9f -> 0.9)
-inline double dec(float x) {
-  if (x == 0.f) return 0.0;
-  const double e = std::floor(std::log10(std::fabs((double)x)));
-  const double s = std::pow(10.0, 7.0 - e);
-  return std::round((double)x * s) / s;
-}
+// (host.h's dec8, shared with resnet.hip)
+inline double dec(float x) { return dec8(x); }
 
 struct Split {
   int S = 1, mps = 32;  // splits, m per split

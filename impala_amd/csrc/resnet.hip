@@ -1,5 +1,6 @@
 // The IMPALA ResNet actor-critic (include/resnet_hip.h): the actor path's kernels, the launchers and
-// the handle (the backward pass's kernels: resnet_bwd.h), a translation unit of its own -- the other units' code objects are the same with or
+// the handle (the backward pass's kernels: resnet_bwd.h; the learner step's: resnet_step.h,
+// §17), a translation unit of its own -- the other units' code objects are the same with or
 // without it.  DESIGN.md §15 has the design and the LDS map.
 //
 // One forward of n frames is four launches:
@@ -517,6 +518,7 @@ __global__ __launch_bounds__(256) void resnet_pack_vec_kernel(const float* __res
 }
 
 #include "resnet_bwd.h"
+#include "resnet_step.h"
 
 }  // namespace
 
@@ -529,6 +531,13 @@ struct resnet_actor : ResnetBufs {  // the buffers: one allocation, ws (resnet_c
   // train = 1 only
   int trained_n = 0;  // frames of the last resnet_forward_train; 0: none, or the weights were refreshed since
   int wg_groups = 0;  // frame groups of the weight-gradient kernels (resnet_wg_groups)
+  // the learner step (resnet_step_init, resnet_bind_state)
+  bool step_on = false;
+  resnet_step_config sc;
+  ResnetStepBufs sb;  // one allocation, step_ws (resnet_step_carve)
+  char* step_ws = nullptr;
+  float *params = nullptr, *grads = nullptr, *exp_avg = nullptr, *exp_avg_sq = nullptr, *metrics = nullptr;
+  float* vt_dbg = nullptr;
 };
 
 namespace {
@@ -668,6 +677,65 @@ int launch_backward(resnet_actor* h, const uint8_t* obs, int n, const float* dl,
 #define RN_BY_TYPE(h, fn, ...) \
   ((h)->cfg.dtype == IMPALA_DTYPE_BF16 ? fn<__bf16>(__VA_ARGS__) : fn<float>(__VA_ARGS__))
 
+// ---- the learner step
+// what every step entry refuses before its first launch; `batch`: the entry reads one
+int check_step(resnet_actor* h, const impala_batch* b, bool batch) {
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  if (!h->cfg.train) return fail(IMPALA_E_INVALID, "the learner step needs a handle created with train = 1");
+  if (!h->step_on) return fail(IMPALA_E_STATE, "resnet_step_init not called");
+  if (!h->grads) return fail(IMPALA_E_STATE, "resnet_bind_state not called");
+  if (batch) {
+    if (!b || !b->obs || !b->actions || !b->rewards || !b->discounts || !b->behaviour_logits)
+      return fail(IMPALA_E_INVALID, "null pointer");
+    if (((uintptr_t)b->obs & 15) != 0) return fail(IMPALA_E_INVALID, "obs must be 16-byte aligned");
+  }
+  if (!h->packed) return fail(IMPALA_E_STATE, "resnet_refresh_weights not called since the parameters were bound");
+  return 0;
+}
+
+int launch_loss_head(resnet_actor* h, const impala_batch* b, hipStream_t st) {
+  const resnet_step_config& c = h->sc;
+  VtHeadArgs a;
+  a.heads = h->heads;
+  a.act = b->actions; a.rew = b->rewards; a.disc = b->discounts; a.mu = b->behaviour_logits;
+  a.B = c.batch_size; a.T = c.rollout_length; a.A = h->cfg.num_actions; a.vt_mode = c.vtrace_grad_mode;
+  a.lam = c.vtrace_lambda; a.crho = c.clip_rho_threshold; a.cpg = c.clip_pg_rho_threshold;
+  a.ent_coef = c.entropy_coeff;
+  a.dl = h->sb.dl; a.dv = h->sb.dv; a.tpart = h->sb.tpart; a.vt_dbg = h->vt_dbg;
+  resnet_vtrace_head_kernel<<<cdiv(a.B, 4), 256, 0, st>>>(a);
+  CK_LAUNCH("resnet_vtrace_head");
+  return 0;
+}
+
+int launch_compute_grads(resnet_actor* h, const impala_batch* b, hipStream_t st) {
+  const int n = h->sc.batch_size * h->sc.rollout_length;
+  if (int r = h->cfg.dtype == IMPALA_DTYPE_BF16 ? launch_forward<__bf16, true>(h, b->obs, n, st)
+                                                : launch_forward<float, true>(h, b->obs, n, st))
+    return r;
+  h->trained_n = n;
+  if (int r = launch_loss_head(h, b, st)) return r;
+  return RN_BY_TYPE(h, launch_backward, h, b->obs, n, h->sb.dl, h->sb.dv, h->grads, 0, st);
+}
+
+int launch_apply_update(resnet_actor* h, hipStream_t st) {
+  const resnet_step_config& c = h->sc;
+  const int n = (int)flat_total(h->cfg.num_actions), nv = n >> 2;
+  resnet_sumsq_kernel<<<RN_SUMSQ_WGS, 256, 0, st>>>(h->grads, n, h->sb.sqpart, h->sb.step, h->sb.sc, dec8(c.lr),
+                                                    dec8(c.adam_beta1), dec8(c.adam_beta2));
+  CK_LAUNCH("resnet_sumsq");
+  RsAdamArgs a;
+  a.params = h->params; a.grads = h->grads; a.m = h->exp_avg; a.v = h->exp_avg_sq; a.metrics = h->metrics;
+  a.sqpart = h->sb.sqpart; a.sc = h->sb.sc; a.tpart = h->sb.tpart; a.step = h->sb.step;
+  a.n = n; a.B = c.batch_size; a.T = c.rollout_length;
+  a.b1 = dec8(c.adam_beta1); a.b2 = dec8(c.adam_beta2);
+  a.eps = c.adam_eps; a.max_norm = c.max_grad_norm; a.ent_coef = c.entropy_coeff;
+  resnet_adam_kernel<<<cdiv(nv + (flat_tail(h->cfg.num_actions) ? 1 : 0), 256), 256, 0, st>>>(a);
+  CK_LAUNCH("resnet_adam");
+  if (int r = RN_BY_TYPE(h, launch_pack, h, st)) return r;
+  h->trained_n = 0;  // what the last resnet_forward_train saved belongs to the parameters before the update
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -719,6 +787,7 @@ int resnet_destroy(resnet_actor* h) {
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
   (void)hipFree(h->ws);
+  (void)hipFree(h->step_ws);
   delete h;
   return 0;
 }
@@ -796,6 +865,97 @@ int resnet_act(resnet_actor* h, const uint8_t* obs, int n, const uint8_t* determ
   return 0;
 }
 
+int resnet_step_config_default(resnet_step_config* cfg) {
+  if (!cfg) return fail(IMPALA_E_INVALID, "null config");
+  *cfg = resnet_step_config{8, 20, 1e-4f, 0.9f, 0.999f, 1e-5f, 0.5f, 0.01f, 1.f, 1.f, 1.f, IMPALA_VTRACE_SG_ADVANTAGE};
+  return 0;
+}
+
+int resnet_step_init(resnet_actor* h, const resnet_step_config* cfg) {
+  if (!cfg) return fail(IMPALA_E_INVALID, "null config");
+  if (cfg->rollout_length < 2 || cfg->rollout_length > 64) return fail(IMPALA_E_INVALID, "rollout_length must be in [2, 64]");
+  if (cfg->batch_size < 1) return fail(IMPALA_E_INVALID, "batch_size must be >= 1");
+  if (cfg->vtrace_grad_mode < IMPALA_VTRACE_SG_ADVANTAGE || cfg->vtrace_grad_mode > IMPALA_VTRACE_SG_NONE)
+    return fail(IMPALA_E_INVALID, "unknown vtrace_grad_mode");
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  if (!h->cfg.train) return fail(IMPALA_E_INVALID, "the learner step needs a handle created with train = 1");
+  if ((long long)cfg->batch_size * cfg->rollout_length > h->cfg.batch_size)
+    return fail(IMPALA_E_INVALID, "batch_size * rollout_length exceeds the handle's batch_size");
+  CK(hipSetDevice(h->device));
+  if (h->step_ws) {
+    CK(hipDeviceSynchronize());
+    CK(hipFree(h->step_ws));
+    h->step_ws = nullptr;
+    h->step_on = false;
+  }
+  const int A = h->cfg.num_actions;
+  CK(hipMalloc((void**)&h->step_ws, resnet_step_carve(h->sb, cfg->batch_size, cfg->rollout_length, A, Arena{})));
+  resnet_step_carve(h->sb, cfg->batch_size, cfg->rollout_length, A, Arena{h->step_ws});
+  const int64_t zero = 0;
+  CK(hipMemcpy(h->sb.step, &zero, 8, hipMemcpyHostToDevice));
+  h->sc = *cfg;
+  h->step_on = true;
+  return 0;
+}
+
+int resnet_bind_state(resnet_actor* h, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                      float* metrics, void*) {
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  if (!h->cfg.train) return fail(IMPALA_E_INVALID, "the learner step needs a handle created with train = 1");
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !metrics) return fail(IMPALA_E_INVALID, "null pointer");
+  if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0)
+    return fail(IMPALA_E_INVALID, "the flat buffers must be 16-byte aligned");
+  if (params != h->flat) {
+    h->flat = params;
+    h->packed = false;
+  }
+  h->params = params; h->grads = grads; h->exp_avg = exp_avg; h->exp_avg_sq = exp_avg_sq; h->metrics = metrics;
+  return 0;
+}
+
+int resnet_set_step(resnet_actor* h, int64_t step, void* stream) {
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  if (!h->step_on) return fail(IMPALA_E_STATE, "resnet_step_init not called");
+  if (step < 0) return fail(IMPALA_E_INVALID, "step must be >= 0");
+  CK(hipSetDevice(h->device));
+  // (the source is read before the call returns: pageable host memory)
+  CK(hipMemcpyAsync(h->sb.step, &step, 8, hipMemcpyHostToDevice, (hipStream_t)stream));
+  return 0;
+}
+
+int resnet_set_debug_vtrace(resnet_actor* h, float* out) {
+  if (!h) return fail(IMPALA_E_INVALID, "null handle");
+  h->vt_dbg = out;
+  return 0;
+}
+
+int resnet_loss_head(resnet_actor* h, const impala_batch* batch, void* stream) {
+  if (int r = check_step(h, batch, true)) return r;
+  if (h->trained_n != h->sc.batch_size * h->sc.rollout_length)
+    return fail(IMPALA_E_STATE, "resnet_loss_head needs a resnet_forward_train of batch_size * rollout_length frames");
+  CK(hipSetDevice(h->device));
+  return launch_loss_head(h, batch, (hipStream_t)stream);
+}
+
+int resnet_compute_grads(resnet_actor* h, const impala_batch* batch, void* stream) {
+  if (int r = check_step(h, batch, true)) return r;
+  CK(hipSetDevice(h->device));
+  return launch_compute_grads(h, batch, (hipStream_t)stream);
+}
+
+int resnet_apply_update(resnet_actor* h, void* stream) {
+  if (int r = check_step(h, nullptr, false)) return r;
+  CK(hipSetDevice(h->device));
+  return launch_apply_update(h, (hipStream_t)stream);
+}
+
+int resnet_train_step(resnet_actor* h, const impala_batch* batch, void* stream) {
+  if (int r = check_step(h, batch, true)) return r;
+  CK(hipSetDevice(h->device));
+  if (int r = launch_compute_grads(h, batch, (hipStream_t)stream)) return r;
+  return launch_apply_update(h, (hipStream_t)stream);
+}
+
 int resnet_debug_read(resnet_actor* h, int which, void* dst, size_t bytes, void* stream) {
   if (!h) return fail(IMPALA_E_INVALID, "null handle");
   if (!h->cfg.debug && !h->cfg.train)
@@ -828,6 +988,14 @@ int resnet_debug_read(resnet_actor* h, int which, void* dst, size_t bytes, void*
     src = (const char*)h->lnstat; cap = B * 2 * 4;
   } else if (which == RESNET_DBG_PART) {
     src = (const char*)h->part; cap = (size_t)RN_KSPLIT * B * RN_HID * 4;
+  } else if (which >= RESNET_DBG_DLOGITS && which <= RESNET_DBG_TPART && !h->step_on) {
+    return fail(IMPALA_E_STATE, "the step's tensors need a resnet_step_init");
+  } else if (which == RESNET_DBG_DLOGITS) {
+    src = (const char*)h->sb.dl; cap = (size_t)h->sc.batch_size * h->sc.rollout_length * h->cfg.num_actions * 4;
+  } else if (which == RESNET_DBG_DVALUES) {
+    src = (const char*)h->sb.dv; cap = (size_t)h->sc.batch_size * h->sc.rollout_length * 4;
+  } else if (which == RESNET_DBG_TPART) {
+    src = (const char*)h->sb.tpart; cap = (size_t)h->sc.batch_size * RN_TPART * 4;
   } else {
     return fail(IMPALA_E_INVALID, "unknown debug tensor");
   }

@@ -125,3 +125,31 @@ inline size_t resnet_carve(ResnetBufs& b, const resnet_config& cfg, int n_cu, Ar
   }
   return Arena::align(a.used);
 }
+
+// ---- the learner step's workspace (resnet_step_init): its own allocation, carved the same way.
+// B trajectories of T frames, A actions.
+constexpr int RN_SUMSQ_WGS = 128;  // workgroups of resnet_sumsq_kernel = clip-norm partial sums
+constexpr int RN_TPART = 8;        // floats of a trajectory's metric partial sums (five used)
+struct ResnetStepBufs {
+  float* dl;      // [B T][A]: d loss / d logits, as resnet_head_bwd_kernel reads it
+  float* dv;      // [B T]:    d loss / d values
+  float* tpart;   // [B][RN_TPART]: sums over a trajectory of log pi(a) adv, err^2, H, KL, rho
+  float* sqpart;  // [RN_SUMSQ_WGS]
+  float* sc;      // [4]: Adam's step size lr / (1 - b1^t) and sqrt(1 - b2^t) of the step under way
+  int64_t* step;  // Adam's step count
+};
+inline size_t resnet_step_carve(ResnetStepBufs& b, int B, int T, int A, Arena a) {
+  auto F = [&](size_t bytes) { return (float*)a.take(bytes); };
+  const size_t n = (size_t)B * T;
+  b = ResnetStepBufs{};
+  b.dl = F(n * A * 4);
+  b.dv = F(n * 4);
+  b.tpart = F((size_t)B * RN_TPART * 4);
+  b.sqpart = F((size_t)RN_SUMSQ_WGS * 4);
+  b.sc = F(4 * 4);
+  b.step = (int64_t*)a.take(8);
+  return Arena::align(a.used);
+}
+// the flat buffer as 16-byte vectors and a scalar tail: 626,240 + 257 (A + 1) floats, a multiple of four
+// only where A = 3 (mod 4)
+inline int flat_tail(int A) { return (int)(flat_total(A) & 3); }

@@ -3,20 +3,23 @@
 its body -- the actor path, ``forward`` and ``act``, and the backward pass:
 ``forward_train`` returns outputs attached to the autograd graph, and ``loss.backward()`` runs
 ``resnet_backward`` into ``model.flat_grad``, in fp32 or (``train_dtype="bf16"``) in bf16.  Every compute entry is one call of
-include/resnet_hip.h; the compute path is the HIP library only.  The one-call learner step (loss
-head, clip and Adam fused) is not built, so there is no ``conf/`` entry for this network yet.
+include/resnet_hip.h; the compute path is the HIP library only.  ``ImpalaResNetLearner`` is the
+learner: one ``resnet_train_step`` a step (``conf/agent/impala_resnet.yaml``).
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import time
 from typing import List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from impala_amd import _lib
 from impala_amd._lib import check, lib
+from impala_amd.core import Learner
 from impala_amd.flat import FlatModule, layer_init_truncated, spec_count
 from impala_amd.model import OBS_SHAPE
 
@@ -181,12 +184,100 @@ class ResnetEngine(_lib.NativeHandle):
                                _lib.stream_ptr(None)), "resnet_act", _ERR)
         return action, logits, values
 
+    # ------------------------------------------------------------------ the learner step
+    def step_init(self, batch_size: int, rollout_length: int, *, lr: float = 1e-4, eps: float = 1e-5,
+                  betas: Tuple[float, float] = (0.9, 0.999), max_grad_norm: float = 0.5,
+                  entropy_coeff: float = 0.01, vtrace_lambda: float = 1.0, clip_rho: float = 1.0,
+                  clip_pg_rho: float = 1.0, vtrace_grad_mode=None) -> None:
+        """Set the engine (``train=True``) up for steps on ``batch_size`` trajectories of
+        ``rollout_length`` frames (``resnet_step_init``) and bind the state the steps update: the
+        model's ``flat`` and ``flat_grad``, and ``exp_avg`` / ``exp_avg_sq`` / ``metrics`` made here."""
+        cfg = _lib.ResnetStepConfig()
+        check(lib().resnet_step_config_default(C.byref(cfg)), "resnet_step_config_default", _ERR)
+        cfg.batch_size, cfg.rollout_length = int(batch_size), int(rollout_length)
+        cfg.lr, cfg.adam_eps, (cfg.adam_beta1, cfg.adam_beta2) = lr, eps, betas
+        cfg.max_grad_norm, cfg.entropy_coeff, cfg.vtrace_lambda = max_grad_norm, entropy_coeff, vtrace_lambda
+        cfg.clip_rho_threshold, cfg.clip_pg_rho_threshold = clip_rho, clip_pg_rho
+        cfg.vtrace_grad_mode = _lib.vtrace_grad_mode(vtrace_grad_mode)
+        check(lib().resnet_step_init(self._h, C.byref(cfg)), "resnet_step_init", _ERR)
+        self.B, self.T = cfg.batch_size, cfg.rollout_length
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.model.flat), torch.zeros_like(self.model.flat)
+        self.bind_metrics(torch.zeros(_lib.NUM_METRICS, device=self.device))
+
+    def bind_metrics(self, metrics: torch.Tensor) -> None:
+        """The vector [NUM_METRICS] the following steps write (host-side only: ``resnet_bind_state``)."""
+        self.metrics = metrics
+        check(lib().resnet_bind_state(self._h, _lib.ptr(self.model.flat), _lib.ptr(self.model.flat_grad),
+                                      _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(metrics),
+                                      _lib.stream_ptr(None)), "resnet_bind_state", _ERR)
+
+    def set_step(self, step: int) -> None:
+        check(lib().resnet_set_step(self._h, int(step), _lib.stream_ptr(None)), "resnet_set_step", _ERR)
+
+    def debug_vtrace(self, on: bool = True) -> Optional[torch.Tensor]:
+        """With ``on``, every following ``loss_head`` also writes its adv, err, q [3, B, T-1] and rho
+        [B, T] into the returned flat tensor (``resnet_set_debug_vtrace``)."""
+        self._vt = torch.zeros(3 * self.B * (self.T - 1) + self.B * self.T, device=self.device) if on else None
+        check(lib().resnet_set_debug_vtrace(self._h, _lib.ptr(self._vt)), "resnet_set_debug_vtrace", _ERR)
+        return self._vt
+
+    def _batch(self, obs, actions, rewards, discounts, behaviour_logits) -> _lib.ImpalaBatch:
+        """The library's batch struct of a collated device batch, shapes and types checked; the
+        tensors it points at stay referenced by the engine until the next batch."""
+        B, T, A = self.B, self.T, self.A
+        want = ((obs, torch.uint8, (B, T) + OBS_SHAPE), (actions, torch.int64, (B, T)),
+                (rewards, torch.float32, (B, T)), (discounts, torch.float32, (B, T)),
+                (behaviour_logits, torch.float32, (B, T, A)))
+        keep = []
+        for t, dt, shape in want:
+            if t.dtype != dt or t.device != self.device or t.numel() != int(np.prod(shape)):
+                raise ValueError(f"batch field: expected {dt} {shape} on {self.device}, got {t.dtype} "
+                                 f"{tuple(t.shape)} on {t.device}")
+            keep.append(t.contiguous())
+        self._obs = keep[0].view((B * T,) + OBS_SHAPE)  # (what ``backward`` reads after a ``forward_train``)
+        self._kept = keep
+        return _lib.ImpalaBatch(*[_lib.ptr(t) for t in keep])
+
+    def _step_call(self, name: str, *batch) -> None:
+        self._fresh()
+        args = (C.byref(self._batch(*batch)),) if batch else ()
+        check(getattr(lib(), name)(self._h, *args, _lib.stream_ptr(None)), name, _ERR)
+
+    def loss_head(self, *batch) -> None:
+        """``resnet_loss_head`` on the heads of the last ``forward_train`` (of the batch's B T frames): the
+        cotangents ("dlogits", "dvalues") and the metric sums ("tpart") stay in the handle."""
+        self._step_call("resnet_loss_head", *batch)
+
+    def compute_grads(self, *batch) -> None:
+        """forward_train, loss head and backward into ``model.flat_grad`` (``resnet_compute_grads``)."""
+        self._step_call("resnet_compute_grads", *batch)
+
+    def _updated(self) -> None:
+        """The library updated ``model.flat`` and re-packed this engine's weights: the model's other
+        engines re-pack before their next use."""
+        self.model.params_changed()
+        self._version = self.model._version
+
+    def apply_update(self) -> None:
+        """Clip, Adam and the re-pack (``resnet_apply_update``); ``metrics`` is written."""
+        self._step_call("resnet_apply_update")
+        self._updated()
+
+    def train_step(self, *batch) -> None:
+        """One learner step on (obs, actions, rewards, discounts, behaviour_logits), collated on the
+        device: ``resnet_train_step``."""
+        self._step_call("resnet_train_step", *batch)
+        self._updated()
+
     def debug_tensor(self, name: str, frames: Optional[int] = None):
         """The tensor ``name`` of the last forward / act or, the g* and the names after them, of the
         last ``backward`` (``resnet_debug_read``; a host sync; a handle created with ``debug=True``
         or ``train=True``) as a float32 numpy array [frames, ...]; "amax" as uint32 words of four
         bytes each (``.view(np.uint8)``)."""
-        known = {**self.DEBUG_TENSORS, **self.TRAIN_TENSORS}
+        # after a ``loss_head``: its cotangents (``frames`` = B T) and a row of metric sums per trajectory (B)
+        step = dict(dlogits=(_lib.RESNET_DBG_DLOGITS, "f32", (self.A,)), dvalues=(_lib.RESNET_DBG_DVALUES, "f32", ()),
+                    tpart=(_lib.RESNET_DBG_TPART, "f32", (8,)))
+        known = {**self.DEBUG_TENSORS, **self.TRAIN_TENSORS, **step}
         if name not in known:
             raise ValueError(f"unknown debug tensor {name!r}: one of {sorted(known)}")
         which, kind, shape = known[name]
@@ -346,3 +437,85 @@ class ImpalaResNetModel(FlatModule):
     def clone_to(self, device) -> "ImpalaResNetModel":
         return self._frozen_clone(ImpalaResNetModel(OBS_SHAPE, self.action_dim, device=device,
                                                     dtype=self.compute_dtype, train_dtype=self.train_dtype))
+
+
+class ImpalaResNetLearner(Learner):
+    """``ImpalaLearner``'s surface (agents/impala/learning.py:86-177) over the IMPALA ResNet: one
+    ``resnet_train_step`` per ``train_step`` -- forward, V-trace loss, backward, clip, Adam and the
+    re-pack.  The batch is the reference's list of trajectories (collated on the
+    device with torch) or a collated device batch; one replica, no staging ring, no prefetch."""
+
+    def __init__(self, model: ImpalaResNetModel, replay_buffer, optimizer=None, batch_size: int = 8,
+                 max_grad_norm: float = 0.5, entropy_coeff: float = 0.01,
+                 learning_starts: Optional[int] = None, model_push_period: int = 4,
+                 rollout_length: int = 20, dtype: Optional[str] = None, vtrace_grad_mode=None):
+        from impala_amd.learner import ImpalaAdam
+        self._model, self._replay_buffer = model, replay_buffer
+        self._optimizer = opt = ImpalaAdam.of(optimizer)
+        self._batch_size, self._rollout_length = int(batch_size), int(rollout_length)
+        self._learning_starts, self._model_push_period = learning_starts, model_push_period
+        self._step_count = self._step_counter = 0
+        self._adam_step = 0  # torch's state['step'], as the handle counts it on the device
+        self.can_train = True
+        self._engine = model.train_engine(self._batch_size * self._rollout_length, dtype)
+        self._engine.step_init(self._batch_size, self._rollout_length, lr=opt.lr, eps=opt.eps,
+                               betas=opt.betas, max_grad_norm=max_grad_norm, entropy_coeff=entropy_coeff,
+                               vtrace_grad_mode=vtrace_grad_mode)
+
+    @property
+    def engine(self) -> ResnetEngine:
+        return self._engine
+
+    @property
+    def samples_per_step(self) -> int:
+        return self._batch_size * self._rollout_length
+
+    def prepare(self):  # learning.py:116-117
+        self._replay_buffer.warm_up(self._learning_starts)
+
+    def train_step(self):  # learning.py:119-138
+        from impala_amd.learner import _collate
+        t0 = time.perf_counter()
+        _, batch, _ = self._replay_buffer.sample(self._batch_size)
+        tensors = _collate(batch, self._engine.device)
+        t1 = time.perf_counter()
+        metrics = self._train_step(tensors)
+        t2 = time.perf_counter()
+        update_time = 0
+        self._step_count += 1
+        self._step_counter = self._step_count
+        if self._step_count % self._model_push_period == 0:
+            start = time.perf_counter()
+            self._model.push()
+            update_time = time.perf_counter() - start
+        n_samples = self.samples_per_step
+        metrics["debug/replay_sample_per_second"] = n_samples / (max(t1 - t0, 1e-9) * 1000)
+        metrics["debug/gradient_per_second"] = n_samples / ((t2 - t1) * 1000)
+        metrics["debug/total_time"] = (time.perf_counter() - t0) * 1000
+        metrics["debug/forward_dt"] = (t2 - t1) * 1000 / self._batch_size
+        metrics["debug/update_time"] = update_time
+        return metrics
+
+    def _train_step(self, batch):  # learning.py:140-177
+        """-> the reference's metric keys as device scalars, views of this step's own vector."""
+        m = torch.empty(_lib.NUM_METRICS, dtype=torch.float32, device=self._engine.device)
+        self._engine.bind_metrics(m)
+        self._engine.train_step(*batch)
+        self._adam_step += 1
+        return dict(zip(_lib.METRIC_NAMES, m.unbind(0)))
+
+    # ---------------------------------------------------------------- checkpoint
+    def state_dict(self) -> dict:
+        e = self._engine
+        return {"model": {k: v.detach().clone() for k, v in self._model.state_dict().items()},
+                "optimizer": {"step": self._adam_step, "exp_avg": e.exp_avg.clone(),
+                              "exp_avg_sq": e.exp_avg_sq.clone()}}
+
+    def load_state_dict(self, sd: dict) -> None:
+        e, opt = self._engine, sd["optimizer"]
+        self._model.load_state_dict(sd["model"])
+        e._fresh()  # resnet_refresh_weights: the kernel-layout weights of the loaded parameters
+        e.exp_avg.copy_(opt["exp_avg"])
+        e.exp_avg_sq.copy_(opt["exp_avg_sq"])
+        self._adam_step = int(opt["step"])
+        e.set_step(self._adam_step)

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define RESNET_ABI_VERSION 3
+#define RESNET_ABI_VERSION 4
 
 #define RESNET_FEATURES 2048
 #define RESNET_HIDDEN 256
@@ -85,6 +85,13 @@ typedef struct resnet_config {
 #define RESNET_DBG_AMAX 49
 #define RESNET_DBG_LNSTAT 50
 #define RESNET_DBG_PART 51
+/* After a resnet_step_init, what resnet_loss_head left (rows of the step's B T frames, not batch_size):
+ *   DLOGITS      d loss / d logits fp32 [B T][A];  DVALUES  d loss / d values fp32 [B T]
+ *   TPART        per trajectory, 8 floats: the sums over its frames of log pi(a) adv and err^2 (the first
+ *                T - 1), of the entropy, the KL term and rho (all T), then zeros: [B][8] */
+#define RESNET_DBG_DLOGITS 52
+#define RESNET_DBG_DVALUES 53
+#define RESNET_DBG_TPART 54
 
 int resnet_abi_version(void);
 const char* resnet_last_error(void);
@@ -128,6 +135,61 @@ int resnet_forward_train(resnet_actor* h, const uint8_t* obs, int n, float* logi
                          void* stream);
 int resnet_backward(resnet_actor* h, const uint8_t* obs, int n, const float* dlogits,
                     const float* dvalues, float* grad_flat, int accumulate, void* stream);
+
+/* The learner step (agents/impala/learning.py:140-177 on this network), on a handle created with
+ * train = 1: the V-trace loss on the heads, the backward, clip_grad_norm_ and torch.optim.Adam (no weight
+ * decay, no amsgrad) and the re-pack of the kernel-layout weights, all enqueued by one call.  The batch is
+ * an impala_batch (impala_hip.h): obs u8 [B][T][3][64][64], actions i64 [B][T], rewards and discounts
+ * fp32 [B][T], behaviour logits fp32 [B][T][A]; frame b T + t.  Metrics: the IMPALA_M_* vector
+ * (IMPALA_M_TARGET zero).
+ *
+ *   resnet_step_init     B trajectories of T frames and the step's constants; allocates the step's
+ *                        workspace (again on a second call) and zeroes the step count.  IMPALA_E_INVALID
+ *                        before any HIP call unless 2 <= T <= 64, B >= 1, the gradient mode is an
+ *                        IMPALA_VTRACE_SG_*, the handle has train = 1 and B T <= its batch_size.
+ *   resnet_bind_state    caller-owned device buffers, 16-byte aligned: params, grads, exp_avg, exp_avg_sq
+ *                        [resnet_param_count] and metrics [IMPALA_NUM_METRICS].  params also becomes the
+ *                        buffer of resnet_bind_params (if it is another one, resnet_refresh_weights must
+ *                        follow).  Host-side only, whatever `stream`: a learner may call it before every
+ *                        step to hand the step a fresh metrics vector.
+ *   resnet_set_step      Adam's step count (torch's state['step']), for a resumed run.
+ *   resnet_set_debug_vtrace  as impala_set_debug_vtrace: while `out` is not NULL every resnet_loss_head also
+ *                        writes adv, err, q [3][B][T-1] and rho [B][T] there (3 B (T-1) + B T floats).
+ *   resnet_loss_head     on the heads of the last resnet_forward_train (of n = B T frames): d loss / d
+ *                        logits and d loss / d values into the handle's cotangent buffers, and the metric
+ *                        sums per trajectory.
+ *   resnet_compute_grads resnet_forward_train on batch->obs, resnet_loss_head, resnet_backward into the
+ *                        bound grads (written, not added): the gradient before the clip.
+ *   resnet_apply_update  the clip and Adam on the bound buffers -- params, exp_avg, exp_avg_sq in place,
+ *                        grads left clipped as p.grad is, the metrics vector written, the step count
+ *                        advanced -- then resnet_refresh_weights' launches.
+ *   resnet_train_step    resnet_compute_grads, then resnet_apply_update: the same launches in the same
+ *                        order, the same bits.
+ * Every sum has one fixed order: equal inputs give equal bits.  A call on a handle without train = 1 or
+ * with a null pointer is IMPALA_E_INVALID, one before resnet_step_init or resnet_bind_state (or, for
+ * resnet_loss_head, without a resnet_forward_train of B T frames) IMPALA_E_STATE, before any launch. */
+typedef struct resnet_step_config {
+  int batch_size;              /* B trajectories a step                                  */
+  int rollout_length;          /* T, 2..64                                               */
+  float lr, adam_beta1, adam_beta2, adam_eps; /* 1e-4, 0.9, 0.999, 1e-5 (builder.py:43-44) */
+  float max_grad_norm;         /* learning.py:93: 0.5                                    */
+  float entropy_coeff;         /* learning.py:94: 0.01                                   */
+  float vtrace_lambda;         /* 1.0                                                    */
+  float clip_rho_threshold;    /* 1.0                                                    */
+  float clip_pg_rho_threshold; /* 1.0                                                    */
+  int vtrace_grad_mode;        /* IMPALA_VTRACE_SG_*, default IMPALA_VTRACE_SG_ADVANTAGE */
+} resnet_step_config;
+
+int resnet_step_config_default(resnet_step_config* cfg);
+int resnet_step_init(resnet_actor* h, const resnet_step_config* cfg);
+int resnet_bind_state(resnet_actor* h, float* params, float* grads, float* exp_avg,
+                      float* exp_avg_sq, float* metrics, void* stream);
+int resnet_set_step(resnet_actor* h, int64_t step, void* stream);
+int resnet_set_debug_vtrace(resnet_actor* h, float* out);
+int resnet_loss_head(resnet_actor* h, const impala_batch* batch, void* stream);
+int resnet_compute_grads(resnet_actor* h, const impala_batch* batch, void* stream);
+int resnet_apply_update(resnet_actor* h, void* stream);
+int resnet_train_step(resnet_actor* h, const impala_batch* batch, void* stream);
 
 /* Test / inspection entry, valid on a handle created with debug = 1 or train = 1: the tensor `which`
  * (RESNET_DBG_*) as the last forward / act left it, its leading `bytes` copied to dst (device or
